@@ -14,6 +14,11 @@ starts N fresh rank processes itself, BEFORE it has imported torch or touched th
 exits non-zero if any of them failed.
 
 Rank 0 prints ONE JSON line; see README / DESIGN.md for the `roofline` and `cpu_baseline` objects.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline figure does not
+need: the host mirror of the candidate generator checked against the device, the PCIe-inclusive rate, the CPU baseline
+with its verdict comparison, the extras (configs 1, 3, 4, 5) and, for N > 1, the gathered-mask check and the all-gather
+timed on its own.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import importlib
@@ -103,6 +108,31 @@ def cpu_baseline(irt, robot, vox, states, budget_s=12.0):
                 build="oracle/tendon_oracle.c, gcc -O3 -march=native -fopenmp",
                 sample="first %d of the %d configurations of rank 0's batch, %.1f s wall, OpenMP schedule(dynamic,1)"
                        % (m, len(states), dt)), valid, m
+
+
+DUMP_BUDGET_BYTES = 60_000_000         # --dump-outputs stays under 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array (rows along axis 0, the same row count for all) as out_dir/<name>.npy, float32 / float64.  Over
+    DUMP_BUDGET_BYTES in all, the same fixed, seeded sample of rows is taken from every array, and its row indices are
+    written beside them as sample_rows.npy (and a sample_rows.npy of an earlier dump to the same directory is removed when
+    this one is whole)."""
+    n = len(next(iter(arrays.values())))
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or len(a) != n:
+            raise ValueError("dump_outputs: %s is %s with %d rows; want float32 / float64 with %d" % (name, a.dtype, len(a), n))
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rows, rows_path = None, os.path.join(out_dir, "sample_rows.npy")
+    if total > DUMP_BUDGET_BYTES:
+        m = max(1, int(n * DUMP_BUDGET_BYTES / (total + 8 * n)))    # (+ 8 bytes per row for the indices)
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=m, replace=False))
+        np.save(rows_path, rows.astype(np.float64))
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if rows is None else a[rows])
 
 
 def spawn_ranks(n_ranks):
@@ -589,8 +619,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch-log2", type=int, default=BATCH_LOG2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary metrics (configs 1, 3, 5 at full size; ~15 s on the GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: generator check, PCIe-inclusive rate, CPU "
+                         "baseline, extras, and for N > 1 the gathered-mask check and the all-gather alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's verdicts and tips of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the PCIe, CPU-baseline and extras legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary metrics (configs 1, 3, 5 at full size; ~15 s on the GPU)")
     ap.add_argument("--config4-log2", type=int, default=20, help="--workload config4: log2 of the candidate vertices (whole job)")
     ap.add_argument("--config4-k", type=int, default=10, help="--workload config4: neighbours per vertex")
     ap.add_argument("--workload", default="config2", choices=["config2", "roadmap", "config4"],
@@ -606,6 +641,8 @@ def main():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-launch HBM bytes of the dominant kernel from a separate rocprofv3 --pmc pass")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "config2":
+        ap.error("--dump-outputs writes the default workload's outputs (--workload config2)")
 
     if args.workload == "roadmap":
         import bench_roadmap
@@ -634,14 +671,15 @@ def main():
     n = 1 << args.batch_log2
     S, P, N = eng.state_size, eng.num_points, eng.n_tendons
     # every rank validates its own shard of the global candidate sequence (weak scaling)
-    # ... generated in HBM by the library's counter-based generator (tr_candidate_states_dev; nothing is uploaded); the host
-    # mirror of the same sequence feeds the CPU baseline and the verdict comparison below
+    # ... generated in HBM by the library's counter-based generator (tr_candidate_states_dev; nothing is uploaded); with --full
+    # the host mirror of the same sequence feeds the CPU baseline and the verdict comparison below
     box = irt.distributed.sampling_box(robot, tau_max=10.0)
     d_states = torch.empty(n * S, dtype=torch.float64, device="cuda")
     eng.candidate_states_dev(2024, rank * n, n, d_states, box=box)
-    states = irt.distributed.candidate_states(robot, seed=2024, start=rank * n, count=n, tau_max=10.0)
-    if not np.array_equal(d_states[: 4096 * S].cpu().numpy().reshape(4096, S), states[:4096]):
-        raise SystemExit("rank %d: device candidate generator differs from its host mirror" % rank)
+    if args.full:
+        states = irt.distributed.candidate_states(robot, seed=2024, start=rank * n, count=n, tau_max=10.0)
+        if not np.array_equal(d_states[: 4096 * S].cpu().numpy().reshape(4096, S), states[:4096]):
+            raise SystemExit("rank %d: device candidate generator differs from its host mirror" % rank)
     d_bits = torch.zeros(n // 64, dtype=torch.int64, device="cuda")
     d_tips = torch.zeros(n, 3, dtype=torch.float64, device="cuda")
     d_all = torch.zeros(world * (n // 64), dtype=torch.int64, device="cuda") if use_dist else None
@@ -673,10 +711,12 @@ def main():
     elapsed = time.perf_counter() - t0
     prof = eng.profile_read()
     eng.profile_end()
+    allgather_ms = None
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if use_dist and args.full:
         # every rank's shard of the gathered mask must be that rank's own verdicts
         gathered = (h_all if rehearsal else d_all.cpu()).numpy().view(np.uint64)
         mine = d_bits.cpu().numpy().view(np.uint64)
@@ -699,6 +739,8 @@ def main():
     valid_bits = d_bits.cpu().numpy().view(np.uint64)
     valid = irt.unpack_bits(valid_bits, n)
     checks = world * n * args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"valid": valid.astype(np.float32), "tips": d_tips.cpu().numpy()})
 
     if rank == 0:
         k1b, k2b = algorithmic_bytes_per_check(S, P, N)
@@ -782,7 +824,7 @@ def main():
                                    "256^3 voxel collision (64 seeded spheres r=0.02 in reach)" % args.batch_log2,
                        "rehearsal_shared_gpu": rehearsal, "batch_per_gpu": n, "parallelism": "shard%d+allgather(bitmask)" % world if use_dist else "single",
                        "collective": ("gloo(host)" if rehearsal else "rccl") if use_dist else None,
-                       "allgather_ms_per_step": allgather_ms if use_dist else None,
+                       "allgather_ms_per_step": allgather_ms,
                        "allgather_bytes_per_rank": n // 8 if use_dist else None,
                        "valid_fraction_rank0": float(valid.mean())},
             "roofline": roofline,
@@ -791,7 +833,7 @@ def main():
                         "fk_rk4_batch": {"avg_ms": k1_ms, "launches": k1["launches"], "bytes_per_check": k1b},
                         "backbone_voxel_sweep": {"avg_ms": k2_ms, "launches": k2["launches"], "bytes_per_check": k2b}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # PCIe-inclusive rate through the host-buffer entry point (pageable numpy arrays in, bits + tips out);
             # reported for DESIGN.md, never the headline value
             eng.validate_batch(states, True, False)           # first call creates the pinned staging buffers

@@ -102,9 +102,10 @@ def _bench(args, **env):
 def test_bench_rccl_path_with_one_rank():
     """bench.py under a launcher's environment with one rank: init_process_group("nccl") + all_gather_into_tensor of
     the device bitmask + the all_reduce of the timing, exactly the statements the N = 2, 4, 8 runs execute."""
-    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "15", "--no-cpu-baseline"],
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "15", "--full", "--no-cpu-baseline"],
                  RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     assert out["n_gpus"] == 1 and out["config"]["collective"] == "rccl" and out["value"] > 0
+    assert out["config"]["allgather_ms_per_step"] > 0         # --full: the gathered-mask check ran, then the all-gather alone
 
 
 def test_bench_gpus2_from_a_bare_command_shared_gpu():
@@ -112,13 +113,14 @@ def test_bench_gpus2_from_a_bare_command_shared_gpu():
     (rehearsal mode), so the numbers mean nothing; the control flow is the N > 1 one."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch-log2", "15", "--no-cpu-baseline"], env=dict(env, TENDON_BENCH_SHARED_GPU="1"),
+                        "--batch-log2", "15", "--full", "--no-cpu-baseline"], env=dict(env, TENDON_BENCH_SHARED_GPU="1"),
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["rehearsal_shared_gpu"] is True
+    assert out["config"]["allgather_ms_per_step"] > 0         # --full: each rank's shard of the gathered mask was checked
 
 
 def test_config4_workload_world1_rccl_and_world2_rehearsal_agree():
