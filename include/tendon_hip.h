@@ -176,6 +176,51 @@ int tr_fk_batch_retraction_dev(tr_ctx *ctx, const double *d_states, int64_t n, i
                                double *d_L, double *d_Li, uint8_t *d_converged, int32_t *d_n_points,
                                double *d_home_Li, void *stream);
 
+/* ---- tip positions, tip Jacobian, tip IK: tip_control::inverse_kinematics ------------------- */
+
+/* fk_shape(state).p.back() for n states (tip_control.cpp:96-104 before its retraction wrapper):
+ * tips n x 3, converged (optional) n.  One K1 launch with only the tips stored: the same instantiation
+ * tr_fk_batch runs, so the tips are the bits of tr_fk_batch's last point. */
+int tr_fk_tips(tr_ctx *ctx, const double *states, int64_t n, double *tips, uint8_t *converged);
+int tr_fk_tips_dev(tr_ctx *ctx, const double *d_states, int64_t n, double *d_tips, uint8_t *d_converged, void *stream);
+
+/* The central-difference tip Jacobian levmar forms inside tip_control::inverse_kinematics
+ * (tip_control.cpp:35-140 with opts[4] = -finite_difference_delta; 3rdparty/levmar-2.6/misc_core.c:175-211),
+ * through tip_control's FK wrapper (a retraction beyond L has its tip at (0, 0, L - s_start),
+ * tip_control.cpp:96-104): per column j, d_j = max(|1e-4 p_j|, delta),
+ * J[:, j] = (tip(p + d_j e_j) - tip(p - d_j e_j)) * (0.5 / d_j).  All n (2 S + 1) FK evaluations of a call are
+ * one K1 launch (chunked internally).  J: n x 3 x S row-major; tips (optional): n x 3, f(p) through the wrapper. */
+int tr_tip_jacobian(tr_ctx *ctx, const double *states, int64_t n, double delta, double *tips, double *J);
+int tr_tip_jacobian_dev(tr_ctx *ctx, const double *d_states, int64_t n, double delta, double *d_tips, double *d_J, void *stream);
+
+/* The arguments of tip_control::inverse_kinematics after the start and the goal (tip_control.h:88-100);
+ * a NULL tr_ik_params* means the defaults written there: 100, 0.1, 1e-9, 1e-4, 1e-4, 1e-6. */
+typedef struct {
+  int32_t max_iters;
+  double  mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta;
+} tr_ik_params;
+
+/* Batched tip_control::inverse_kinematics (tip_control.cpp:35-140), one start state per problem, n problems at once
+ * (VoxelCachedLazyPRM::roadmapIk runs k of them, motion-planning/VoxelCachedLazyPRM.cpp:3164-3205).  The optimiser is this
+ * library's own projected Levenberg-Marquardt with levmar's central-difference Jacobian, gain-ratio damping and the same four stop
+ * tests (it is not levmar's code path); every problem's state stays on the device, and one round -- one K1 launch of the
+ * 2 S + 1 evaluations of every still-active problem plus one LM-step launch -- advances all of them by an iteration.
+ *   initial_states  n x S (clipped to the bounds first)
+ *   des             n x 3 goal tips with row stride des_ld doubles, or one goal for all when des_ld == 0
+ *   lo, hi          S each; NULL = Bounds::from_robot (tip_control.cpp:160-185)
+ *   states_out      n x S solved states, rotation canonical in [-pi, pi) (util/angles.h:13-34)
+ *   tips_out, error_out, iters_out, fk_calls_out   IKResult::tip, error, iters, num_fk_calls (a multiple of 2 S + 1)
+ *   rounds_out      rounds run (a host pointer in both forms)
+ * Every output may be NULL.  A problem's result does not depend on the other problems of the call or on their order. */
+int tr_ik_batch(tr_ctx *ctx, const tr_ik_params *params, const double *initial_states, int64_t n, const double *des, int64_t des_ld,
+                const double *lo, const double *hi, double *states_out, double *tips_out, double *error_out,
+                int32_t *iters_out, int32_t *fk_calls_out, int64_t *rounds_out);
+/* Device form: device arrays, host lo / hi / params / rounds_out.  It synchronises `stream` once per round to read the number of
+ * problems still active (4 bytes through pinned memory); nothing else crosses the bus. */
+int tr_ik_batch_dev(tr_ctx *ctx, const tr_ik_params *params, const double *d_initial_states, int64_t n, const double *d_des,
+                    int64_t des_ld, const double *lo, const double *hi, double *d_states_out, double *d_tips_out,
+                    double *d_error_out, int32_t *d_iters_out, int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
+
 /* ---- state validity: StateValidityChecker::isValid -------------------------------------- */
 
 /* Batched AbstractValidityChecker::isValid (motion-planning/AbstractValidityChecker.cpp:124-133)

@@ -21,7 +21,9 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -116,6 +118,19 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     return std::move(shape_batch(state, 1)[0]);
   }
 
+  /// Central-difference tip Jacobians of n states through tip_control's FK wrapper (tr_tip_jacobian): n x 3 x S row-major;
+  /// `tips` (optional) receives f(p), n x 3
+  std::vector<double> tip_jacobian_batch(const std::vector<double> &states, size_t n, double delta = 1e-6,
+                                         std::vector<double> *tips = nullptr) const {
+    const size_t S = state_size();
+    if (states.size() != n * S) throw std::invalid_argument("State is not the right size");
+    tr_ctx *c = context();
+    std::vector<double> J(n * 3 * S);
+    if (tips) tips->resize(3 * n);
+    check(c, tr_tip_jacobian(c, states.data(), (int64_t)n, delta, tips ? tips->data() : nullptr, J.data()));
+    return J;
+  }
+
   /// forward_kinematics(state), TendonRobot.h:68-72
   std::vector<std::array<double, 3>> forward_kinematics(const std::vector<double> &state) const { return shape(state).p; }
 
@@ -181,6 +196,76 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
 };
 
 }  // namespace tendon
+
+/// tip_control (tip-control/tip_control.h:27-107) on the device: the FK callback is the engine's own (tr_ik_batch)
+namespace tip_control {
+
+struct IKResult {                   // tip_control.h:40-46
+  std::vector<double> state;        // solved robot state (rotation canonical in [-pi, pi))
+  std::array<double, 3> tip{};      // achieved tip
+  double error = 0.0;               // tip position error
+  int iters = 0;                    // LM iterations
+  int num_fk_calls = 0;             // forward-kinematics evaluations (a multiple of 2 S + 1)
+};
+
+struct Bounds {                     // tip_control.h:48-58
+  std::vector<double> lower, upper;
+  /// tip_control.cpp:160-185: tensions in [0, max_tension], rotation unbounded, retraction in [0, L]
+  static Bounds from_robot(const tendon::TendonRobot &robot) {
+    Bounds b;
+    const size_t N = robot.tendons.size(), S = robot.state_size();
+    b.lower.assign(S, 0.0); b.upper.assign(S, 0.0);
+    for (size_t i = 0; i < N; i++) b.upper[i] = robot.tendons[i].max_tension;
+    if (robot.enable_rotation) { b.lower[N] = std::numeric_limits<double>::lowest(); b.upper[N] = std::numeric_limits<double>::max(); }
+    if (robot.enable_retraction) b.upper[S - 1] = robot.specs.L;
+    return b;
+  }
+  void center_about_state(const std::vector<double> &state) {
+    for (size_t i = 0; i < lower.size() && i < state.size(); i++) { lower[i] -= state[i]; upper[i] -= state[i]; }
+  }
+};
+
+/// inverse_kinematics for n start states at once (rows of `initial_states`), to one goal (`des` of size 1) or one goal each
+/// (size n); all problems advance together, one K1 launch per round.  `bounds` null = Bounds::from_robot.
+inline std::vector<IKResult> inverse_kinematics_batch(const tendon::TendonRobot &robot, const std::vector<double> &initial_states, size_t n,
+                                                      const std::vector<std::array<double, 3>> &des, int max_iters = 100,
+                                                      double mu_init = 0.1, double stop_threshold_JT_err_inf = 1e-9,
+                                                      double stop_threshold_Dp = 1e-4, double stop_threshold_err = 1e-4,
+                                                      double finite_difference_delta = 1e-6, const Bounds *bounds = nullptr,
+                                                      int64_t *rounds = nullptr) {
+  const size_t S = robot.state_size();
+  if (initial_states.size() != n * S) throw std::invalid_argument("State is not the right size");
+  if (des.size() != 1 && des.size() != n) throw std::invalid_argument("one goal, or one goal per start state");
+  if (bounds && (bounds->lower.size() != S || bounds->upper.size() != S)) throw std::invalid_argument("State is not the right size");
+  tr_ctx *c = robot.context();
+  const tr_ik_params prm{max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta};
+  std::vector<double> d(3 * des.size()), st(n * S), tips(3 * n), err(n);
+  for (size_t i = 0; i < des.size(); i++) for (int k = 0; k < 3; k++) d[3 * i + k] = des[i][k];
+  std::vector<int32_t> iters(n), calls(n);
+  check(c, tr_ik_batch(c, &prm, initial_states.data(), (int64_t)n, d.data(), des.size() == 1 ? 0 : 3,
+                       bounds ? bounds->lower.data() : nullptr, bounds ? bounds->upper.data() : nullptr, st.data(), tips.data(),
+                       err.data(), iters.data(), calls.data(), rounds));
+  std::vector<IKResult> out(n);
+  for (size_t i = 0; i < n; i++) {
+    out[i].state.assign(st.begin() + i * S, st.begin() + (i + 1) * S);
+    out[i].tip = {tips[3 * i], tips[3 * i + 1], tips[3 * i + 2]};
+    out[i].error = err[i]; out[i].iters = iters[i]; out[i].num_fk_calls = calls[i];
+  }
+  return out;
+}
+
+/// tip_control::inverse_kinematics (tip_control.h:88-100) without the FKFunc: the engine's FK through tip_control's wrapper
+inline IKResult inverse_kinematics(const tendon::TendonRobot &robot, const std::vector<double> &initial_state, const std::array<double, 3> &des,
+                                   int max_iters = 100, double mu_init = 0.1, double stop_threshold_JT_err_inf = 1e-9,
+                                   double stop_threshold_Dp = 1e-4, double stop_threshold_err = 1e-4,
+                                   double finite_difference_delta = 1e-6, bool verbose = false) {
+  (void)verbose;
+  if (initial_state.size() != robot.state_size()) throw std::invalid_argument("State is not the right size");
+  return inverse_kinematics_batch(robot, initial_state, 1, {des}, max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp,
+                                  stop_threshold_err, finite_difference_delta)[0];
+}
+
+}  // namespace tip_control
 
 namespace collision {
 
@@ -835,6 +920,91 @@ class VoxelCachedLazyPRM {
   /// the next large batch of queries allocates it again).
   int64_t searchStateBytes() const { int64_t b = 0; if (rm_) rcheck(tr_roadmap_search_state_bytes(rm_, &b)); return b; }
   void reserveSearchState(int64_t n_queries) { sync(); rcheck(tr_roadmap_reserve_search_state(rm_, n_queries)); }
+  // ---- roadmapIk (VoxelCachedLazyPRM.h:356-446, .cpp:3095-3430) ----
+  enum RoadmapIkOpts { RMAP_IK_SIMPLE = 0x0, RMAP_IK_AUTO_ADD = 0x1, RMAP_IK_ACCURATE = 0x2, RMAP_IK_LAZY_ADD = 0x4 };
+  struct IKResult {
+    std::vector<double> controls;          // valid state at or close to the request
+    std::array<double, 3> tip_position{};  // tip position obtained by controls
+    std::vector<double> neighbor;          // the vertex state IK started from
+    size_t neighbor_vertex = 0;            // ... and its vertex number
+    double error = 0.0;                    // |tip_position - request|
+  };
+  /// RMAP_IK_SIMPLE: IK from the k vertices whose tips are nearest the request (vertices with a tip and not known invalid; the
+  /// unknown ones among them are checked, the invalid dropped and the search repeated), all k problems in ONE tr_ik_batch; the
+  /// solutions are validated in one isValidBatch; the first in neighbour order that is valid and within tolerance is returned,
+  /// else the valid one with the least error; if none is valid, each solution is replaced by the last valid state of
+  /// checkMotion(neighbor, solution) and the one whose tip is nearest the request is returned.  std::nullopt: no vertex to start
+  /// from.  AUTO_ADD, ACCURATE and LAZY_ADD are not offered (std::invalid_argument).  Vertices found invalid here are not
+  /// removed from the roadmap.
+  std::optional<IKResult> roadmapIk(const std::array<double, 3> &request, double tolerance = 1e-4, size_t k = 5, int opts = RMAP_IK_SIMPLE) {
+    if (opts != RMAP_IK_SIMPLE) throw std::invalid_argument("roadmapIk: only RMAP_IK_SIMPLE is supported");
+    absorb();
+    const auto &rb = vc_.robot();
+    auto tip_dist2 = [&](const double *t) {
+      double s = 0.0;
+      for (int q = 0; q < 3; q++) s += (t[q] - request[q]) * (t[q] - request[q]);
+      return s;
+    };
+    // 1-2. the k nearest vertices by tip among the valid ones
+    std::vector<size_t> cand;
+    for (size_t v = 0; v < milestoneCount(); v++) if (has_tip_[v] && vstat_[v] != 2) cand.push_back(v);
+    std::stable_sort(cand.begin(), cand.end(), [&](size_t a, size_t b) { return tip_dist2(&tips_[3 * a]) < tip_dist2(&tips_[3 * b]); });
+    std::vector<size_t> near;
+    std::vector<uint8_t> known(milestoneCount(), 0);
+    for (size_t v = 0; v < milestoneCount(); v++) known[v] = vstat_[v];
+    size_t next = 0;
+    while (near.size() < k && next < cand.size()) {
+      std::vector<size_t> unknown;
+      while (near.size() + unknown.size() < k && next < cand.size()) {
+        const size_t v = cand[next++];
+        if (known[v] == 1) near.push_back(v); else unknown.push_back(v);
+      }
+      if (unknown.empty()) continue;
+      std::vector<double> st(unknown.size() * S_);
+      for (size_t i = 0; i < unknown.size(); i++) std::copy(states_.begin() + unknown[i] * S_, states_.begin() + (unknown[i] + 1) * S_, st.begin() + i * S_);
+      const std::vector<bool> ok = vc_.isValidBatch(st, unknown.size());
+      for (size_t i = 0; i < unknown.size(); i++) { known[unknown[i]] = ok[i] ? 1 : 2; if (ok[i]) near.push_back(unknown[i]); }
+    }
+    if (near.empty()) return std::nullopt;
+    std::stable_sort(near.begin(), near.end(), [&](size_t a, size_t b) { return tip_dist2(&tips_[3 * a]) < tip_dist2(&tips_[3 * b]); });
+    const size_t m = near.size();
+    std::vector<double> starts(m * S_);
+    for (size_t i = 0; i < m; i++) std::copy(states_.begin() + near[i] * S_, states_.begin() + (near[i] + 1) * S_, starts.begin() + i * S_);
+    // 3. IK from all of them in one batch
+    const std::vector<tip_control::IKResult> ik =
+        tip_control::inverse_kinematics_batch(rb, starts, m, {request}, 100, 0.1, 1e-9, 1e-4, tolerance, 1e-6);
+    // 4. one validity batch
+    std::vector<double> sol(m * S_);
+    for (size_t i = 0; i < m; i++) std::copy(ik[i].state.begin(), ik[i].state.end(), sol.begin() + i * S_);
+    const std::vector<bool> valid = vc_.isValidBatch(sol, m);
+    auto result = [&](size_t i, const std::vector<double> &x, const std::array<double, 3> &tip, double err) {
+      IKResult r;
+      r.controls = x; r.tip_position = tip; r.error = err; r.neighbor_vertex = near[i];
+      r.neighbor.assign(starts.begin() + i * S_, starts.begin() + (i + 1) * S_);
+      return r;
+    };
+    // 5. the first valid one within tolerance, else the valid one with the least error
+    for (size_t i = 0; i < m; i++) if (valid[i] && ik[i].error <= tolerance) return result(i, ik[i].state, ik[i].tip, ik[i].error);
+    size_t best = m;
+    for (size_t i = 0; i < m; i++) if (valid[i] && (best == m || ik[i].error < ik[best].error)) best = i;
+    if (best < m) return result(best, ik[best].state, ik[best].tip, ik[best].error);
+    // 6. none valid: the last valid state towards each solution, the one whose tip is nearest the request
+    need_validators("roadmapIk");
+    std::vector<double> t;
+    mv_->checkMotionBatch(starts, sol, m, nullptr, &t);
+    std::vector<double> lv(m * S_), tips(3 * m);
+    for (size_t i = 0; i < m; i++) {
+      const std::vector<double> a(starts.begin() + i * S_, starts.begin() + (i + 1) * S_), b(sol.begin() + i * S_, sol.begin() + (i + 1) * S_);
+      const std::vector<double> x = mv_->interpolate(a, b, t[i]);
+      std::copy(x.begin(), x.end(), lv.begin() + i * S_);
+    }
+    check(vc_.context(), tr_fk_tips(vc_.context(), lv.data(), (int64_t)m, tips.data(), nullptr));
+    best = 0;
+    for (size_t i = 1; i < m; i++) if (tip_dist2(&tips[3 * i]) < tip_dist2(&tips[3 * best])) best = i;
+    const std::vector<double> x(lv.begin() + best * S_, lv.begin() + (best + 1) * S_);
+    return result(best, x, {tips[3 * best], tips[3 * best + 1], tips[3 * best + 2]}, std::sqrt(tip_dist2(&tips[3 * best])));
+  }
+
   int64_t releaseSearchState() { int64_t b = 0; if (rm_) rcheck(tr_roadmap_release_search_state(rm_, &b)); return b; }
   /// CompoundStateSpace::distance with the weights of Problem.cpp:112-152 (the edge cost connectVertices stores, :2857-2861)
   double distance(const double *a, const double *b) const {

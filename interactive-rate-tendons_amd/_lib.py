@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "tr_set_debug", "tr_edge_schedule_last",
     "tr_candidate_states", "tr_candidate_states_dev", "tr_validate_candidates_dev", "tr_compact_rows_dev",
     "tr_sample_valid_vertices", "tr_sample_valid_vertices_dev", "tr_sample_valid_vertices_sig_dev",
+    "tr_fk_tips", "tr_fk_tips_dev", "tr_tip_jacobian", "tr_tip_jacobian_dev", "tr_ik_batch", "tr_ik_batch_dev",
 )
 
 
@@ -56,6 +57,11 @@ class TrRobotDesc(C.Structure):
 class TrSpaceParams(C.Structure):
     _fields_ = [("min_tension_change", C.c_double), ("min_rotation_change", C.c_double),
                 ("min_retraction_change", C.c_double)]
+
+
+class TrIkParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("mu_init", C.c_double), ("stop_threshold_JT_err_inf", C.c_double),
+                ("stop_threshold_Dp", C.c_double), ("stop_threshold_err", C.c_double), ("finite_difference_delta", C.c_double)]
 
 
 class TrRoadmapStats(C.Structure):
@@ -309,6 +315,13 @@ def lib():
     L.tr_sample_valid_vertices.argtypes = [vp, u64, u64, dp, dp, i64, i64, dp, dp, P(i64), P(i64), P(i64)]
     L.tr_sample_valid_vertices_dev.argtypes = [vp, u64, u64, dp, dp, i64, i64, vp, vp, vp, P(i64), P(i64), vp]
     L.tr_sample_valid_vertices_sig_dev.argtypes = [vp, u64, u64, dp, dp, i64, i64, vp, vp, vp, vp, P(i64), P(i64), vp]
+    i32p = P(C.c_int32)
+    L.tr_fk_tips.argtypes = [vp, dp, i64, dp, P(C.c_uint8)]
+    L.tr_fk_tips_dev.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.tr_tip_jacobian.argtypes = [vp, dp, i64, C.c_double, dp, dp]
+    L.tr_tip_jacobian_dev.argtypes = [vp, vp, i64, C.c_double, vp, vp, vp]
+    L.tr_ik_batch.argtypes = [vp, P(TrIkParams), dp, i64, dp, i64, dp, dp, dp, dp, dp, i32p, i32p, P(i64)]
+    L.tr_ik_batch_dev.argtypes = [vp, P(TrIkParams), vp, i64, vp, i64, dp, dp, vp, vp, vp, vp, vp, P(i64), vp]
     L.tr_profile_begin.argtypes = [vp]
     L.tr_profile_read.argtypes = [vp, P(i64), dp]
     L.tr_profile_end.argtypes = [vp]

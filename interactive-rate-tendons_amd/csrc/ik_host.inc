@@ -1,0 +1,306 @@
+// ik_host.inc -- tip positions, the tip Jacobian and batched tip IK behind the C ABI (tr_fk_tips*, tr_tip_jacobian*, tr_ik_batch*).
+// The FK of every form is one K1 launch with only the tips stored (launch_fk, the instantiation tr_fk_batch runs); the Jacobian and
+// the LM iteration are ik_kernel.hpp.  The IK loop keeps every problem's state on the device: per round one expansion, one K1
+// launch of m (2S + 1) lanes and one LM-step launch, and the host reads the 4-byte active count from pinned memory.
+// Included at the end of tendon_hip.hip (needs tr_ctx).
+namespace {
+
+// lanes of one K1 launch of the Jacobian / IK paths, at most: problems are solved in chunks of kIkLanes / (2S + 1), each chunk to
+// the end (a problem's iterates do not depend on the others, so the chunking changes no result)
+constexpr int64_t kIkLanes = 1 << 19;
+
+int64_t ik_chunk(const tr_ctx *c) { return kIkLanes / (2 * c->K.state_size + 1); }
+
+void ik_release(tr_ctx *c) {
+  tr_ctx::IkDev &k = c->ik;
+  void *p[] = {k.xs, k.tips, k.p, k.pn, k.f, k.J, k.des, k.err2, k.mu, k.nu, k.iters, k.calls, k.list[0], k.list[1], k.d_count,
+               k.io_s, k.io_3, k.io_e, k.io_i, k.io_c};
+  for (void *q : p) if (q) (void)hipFree(q);
+  if (k.h_count) (void)hipHostFree(k.h_count);
+  k = tr_ctx::IkDev{};
+}
+
+// the workspace for chunks of up to `n` problems (grow-only, released with the context)
+int ik_reserve(tr_ctx *c, int64_t n) {
+  tr_ctx::IkDev &k = c->ik;
+  const int64_t S = c->K.state_size, Q = 2 * S + 1;
+  const int64_t probs = round_up(std::max<int64_t>(1, std::min(n, ik_chunk(c))), 64), lanes = round_up(probs * Q, 64);
+  int rc;
+  if (!k.d_count) {
+    if ((rc = dev_alloc(c, &k.d_count, 2))) return rc;
+    HIP_TRY(c, hipHostMalloc((void **)&k.h_count, sizeof(uint32_t), hipHostMallocDefault));
+  }
+  if (k.probs >= probs) return TR_OK;
+  HIP_TRY(c, hipDeviceSynchronize());
+  if ((rc = dev_alloc(c, &k.xs, (size_t)(lanes * S)))) return rc;
+  if ((rc = dev_alloc(c, &k.tips, (size_t)(lanes * 3)))) return rc;
+  if ((rc = dev_alloc(c, &k.p, (size_t)(probs * S)))) return rc;
+  if ((rc = dev_alloc(c, &k.pn, (size_t)(probs * S)))) return rc;
+  if ((rc = dev_alloc(c, &k.f, (size_t)(probs * 3)))) return rc;
+  if ((rc = dev_alloc(c, &k.J, (size_t)(probs * 3 * S)))) return rc;
+  if ((rc = dev_alloc(c, &k.des, (size_t)(probs * 3)))) return rc;
+  if ((rc = dev_alloc(c, &k.err2, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.mu, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.nu, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.iters, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.calls, (size_t)probs))) return rc;
+  for (int q = 0; q < 2; q++) if ((rc = dev_alloc(c, &k.list[q], (size_t)probs))) return rc;
+  // staging of the host-array forms
+  if ((rc = dev_alloc(c, &k.io_s, (size_t)(probs * S)))) return rc;
+  if ((rc = dev_alloc(c, &k.io_3, (size_t)(probs * 3)))) return rc;
+  if ((rc = dev_alloc(c, &k.io_e, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.io_i, (size_t)probs))) return rc;
+  if ((rc = dev_alloc(c, &k.io_c, (size_t)probs))) return rc;
+  k.probs = probs;
+  k.lanes = lanes;
+  return TR_OK;
+}
+
+trk::IkState ik_state(tr_ctx *c) {
+  tr_ctx::IkDev &k = c->ik;
+  return trk::IkState{k.p, k.pn, k.f, k.J, k.des, k.err2, k.mu, k.nu, k.iters, k.calls};
+}
+
+unsigned ik_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+// K1 over `lanes` expanded states: tips only
+int ik_fk(tr_ctx *c, int64_t lanes, hipStream_t s) {
+  const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->ik.tips, nullptr, nullptr, nullptr};
+  return launch_fk(c, c->ik.xs, lanes, round_up(lanes, 64), out, s);
+}
+
+// f and J of m <= ik_chunk states (device rows)
+int jacobian_chunk(tr_ctx *c, const double *d_states, int64_t m, double delta, double *d_tips, double *d_J, hipStream_t s) {
+  const int S = c->K.state_size;
+  const int64_t lanes = m * (2 * S + 1);
+  hipLaunchKernelGGL(trk::ik_expand, dim3(ik_grid(lanes, 256)), dim3(256), 0, s, d_states, (const int32_t *)nullptr, m, S, delta, c->ik.xs);
+  HIP_TRY(c, hipGetLastError());
+  int rc;
+  if ((rc = ik_fk(c, lanes, s))) return rc;
+  hipLaunchKernelGGL(trk::ik_jacobian, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_states, (const double *)c->ik.tips, m, S, delta,
+                     (int)c->K.enable_retraction, c->K.L, d_tips, d_J);
+  HIP_TRY(c, hipGetLastError());
+  return TR_OK;
+}
+
+int ik_params(tr_ctx *c, const tr_ik_params *ip, const double *lo, const double *hi, trk::IkParams &prm) {
+  const int N = c->K.n_tendons, S = c->K.state_size;
+  if (S > TRK_IK_MAX_S) return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
+  const tr_ik_params def{100, 0.1, 1e-9, 1e-4, 1e-4, 1e-6};                           // tip_control.h:88-100
+  const tr_ik_params &q = ip ? *ip : def;
+  if (q.max_iters < 0) return fail(c, TR_ERR_INVALID_ARG, "max_iters must be >= 0");
+  prm = trk::IkParams{};
+  prm.S = S; prm.max_iters = q.max_iters;
+  prm.rot_index = c->K.enable_rotation ? N : -1;
+  prm.retraction = c->K.enable_retraction;
+  prm.L = c->K.L;
+  prm.delta = q.finite_difference_delta;
+  prm.mu_init = q.mu_init;
+  prm.eps1 = q.stop_threshold_JT_err_inf;
+  prm.eps2_sq = q.stop_threshold_Dp * q.stop_threshold_Dp;
+  prm.eps3_sq = q.stop_threshold_err * q.stop_threshold_err;
+  for (int d = 0; d < S; d++) {                      // Bounds::from_robot (tip_control.cpp:160-185)
+    double a = 0.0, b = 0.0;
+    if (d < N) b = c->max_tension[(size_t)d];
+    else if (c->K.enable_rotation && d == N) { a = -std::numeric_limits<double>::max(); b = std::numeric_limits<double>::max(); }
+    else b = c->K.L;
+    prm.lo[d] = lo ? lo[d] : a;
+    prm.hi[d] = hi ? hi[d] : b;
+  }
+  return TR_OK;
+}
+
+// one chunk of m problems to the end: d_init m x S, goals d_des (row stride des_ld, 0 = one row); outputs may be null
+int ik_chunk_solve(tr_ctx *c, const trk::IkParams &prm, const double *d_init, int64_t m, const double *d_des, int64_t des_ld,
+                   double *d_states, double *d_tips, double *d_err, int32_t *d_iters, int32_t *d_calls, hipStream_t s, int64_t &rounds) {
+  tr_ctx::IkDev &k = c->ik;
+  const int S = prm.S, Q = 2 * S + 1;
+  const trk::IkState st = ik_state(c);
+  hipLaunchKernelGGL(trk::ik_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st);
+  HIP_TRY(c, hipGetLastError());
+  int64_t active = m;
+  int cur = 0;
+  for (bool init = true; active > 0; init = false) {
+    const int nxt = cur ^ 1;
+    const int32_t *list = init ? nullptr : k.list[cur];
+    HIP_TRY(c, hipMemsetAsync(k.d_count + nxt, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(trk::ik_expand, dim3(ik_grid(active * Q, 256)), dim3(256), 0, s, (const double *)k.pn, list, active, S, prm.delta, k.xs);
+    HIP_TRY(c, hipGetLastError());
+    int rc;
+    if ((rc = ik_fk(c, active * Q, s))) return rc;
+    switch (S) {
+#define TRK_CASE(SS) case SS: hipLaunchKernelGGL((trk::ik_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, st, list, active, \
+                                                 (const double *)k.tips, (int)init, k.list[nxt], k.d_count + nxt); break;
+      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8) TRK_CASE(9) TRK_CASE(10)
+#undef TRK_CASE
+      default: return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(k.h_count, k.d_count + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    active = (int64_t)*k.h_count;
+    cur = nxt;
+    rounds++;
+  }
+  hipLaunchKernelGGL(trk::ik_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_states, d_tips, d_err, d_iters, d_calls);
+  HIP_TRY(c, hipGetLastError());
+  return TR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tr_fk_tips_dev(tr_ctx *c, const double *d_states, int64_t n, double *d_tips, uint8_t *d_converged, void *stream) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (n < 0) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return TR_OK;
+  if (!d_states || !d_tips) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = begin_dev_work(c, s))) return rc;
+  const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tips, d_converged, nullptr, nullptr};
+  if ((rc = launch_fk(c, d_states, n, round_up(n, 64), out, s))) return rc;
+  return note_dev_work(c, s);
+}
+
+int tr_fk_tips(tr_ctx *c, const double *states, int64_t n, double *tips, uint8_t *converged) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (n < 0 || (n > 0 && (!states || !tips))) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return TR_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());          // the staging is shared with *_dev calls that may still run on other streams
+  const int S = c->K.state_size;
+  const int64_t chunk_max = std::min<int64_t>(c->max_chunk, 1 << 16);      // tr_fk_batch's chunk
+  int rc;
+  if ((rc = ensure_staging(c, std::min(n, chunk_max)))) return rc;
+  Workspace &w = c->ws;
+  for (int64_t off = 0; off < n; off += chunk_max) {
+    const int64_t m = std::min(chunk_max, n - off);
+    HIP_TRY(c, hipMemcpy(w.states, states + off * S, (size_t)m * S * sizeof(double), hipMemcpyHostToDevice));
+    const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w.tips, converged ? w.flags : nullptr, nullptr, nullptr};
+    if ((rc = launch_fk(c, w.states, m, round_up(m, 64), out, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(tips + off * 3, w.tips, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (converged) HIP_TRY(c, hipMemcpy(converged + off, w.flags, (size_t)m, hipMemcpyDeviceToHost));
+  }
+  return TR_OK;
+}
+
+int tr_tip_jacobian_dev(tr_ctx *c, const double *d_states, int64_t n, double delta, double *d_tips, double *d_J, void *stream) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (n < 0) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return TR_OK;
+  if (!d_states || !d_J) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const hipStream_t s = (hipStream_t)stream;
+  const int S = c->K.state_size;
+  int rc;
+  if ((rc = begin_dev_work(c, s))) return rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  const int64_t chunk = ik_chunk(c);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    if ((rc = jacobian_chunk(c, d_states + off * S, m, delta, d_tips ? d_tips + off * 3 : nullptr, d_J + off * 3 * S, s))) return rc;
+  }
+  return note_dev_work(c, s);
+}
+
+int tr_tip_jacobian(tr_ctx *c, const double *states, int64_t n, double delta, double *tips, double *J) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (n < 0 || (n > 0 && (!states || !J))) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return TR_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());
+  const int S = c->K.state_size;
+  int rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  tr_ctx::IkDev &k = c->ik;
+  const int64_t chunk = ik_chunk(c);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    HIP_TRY(c, hipMemcpy(k.io_s, states + off * S, (size_t)(m * S) * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = jacobian_chunk(c, k.io_s, m, delta, tips ? k.io_3 : nullptr, k.J, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpy(J + off * 3 * S, k.J, (size_t)(m * 3 * S) * sizeof(double), hipMemcpyDeviceToHost));
+    if (tips) HIP_TRY(c, hipMemcpy(tips + off * 3, k.io_3, (size_t)(m * 3) * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return TR_OK;
+}
+
+int tr_ik_batch_dev(tr_ctx *c, const tr_ik_params *params, const double *d_initial_states, int64_t n, const double *d_des, int64_t des_ld,
+                    const double *lo, const double *hi, double *d_states_out, double *d_tips_out, double *d_error_out,
+                    int32_t *d_iters_out, int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (rounds_out) *rounds_out = 0;
+  if (n < 0 || (des_ld != 0 && des_ld < 3)) return fail(c, TR_ERR_INVALID_ARG, "bad argument (des_ld: 0 or >= 3)");
+  if (n == 0) return TR_OK;
+  if (!d_initial_states || !d_des) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const hipStream_t s = (hipStream_t)stream;
+  const int S = c->K.state_size;
+  trk::IkParams prm;
+  int rc;
+  if ((rc = ik_params(c, params, lo, hi, prm))) return rc;
+  if ((rc = begin_dev_work(c, s))) return rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  const int64_t chunk = ik_chunk(c);
+  int64_t rounds = 0;
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    if ((rc = ik_chunk_solve(c, prm, d_initial_states + off * S, m, d_des + off * des_ld, des_ld,
+                             d_states_out ? d_states_out + off * S : nullptr, d_tips_out ? d_tips_out + off * 3 : nullptr,
+                             d_error_out ? d_error_out + off : nullptr, d_iters_out ? d_iters_out + off : nullptr,
+                             d_fk_calls_out ? d_fk_calls_out + off : nullptr, s, rounds))) return rc;
+  }
+  if (rounds_out) *rounds_out = rounds;
+  return note_dev_work(c, s);
+}
+
+int tr_ik_batch(tr_ctx *c, const tr_ik_params *params, const double *initial_states, int64_t n, const double *des, int64_t des_ld,
+                const double *lo, const double *hi, double *states_out, double *tips_out, double *error_out, int32_t *iters_out,
+                int32_t *fk_calls_out, int64_t *rounds_out) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (rounds_out) *rounds_out = 0;
+  if (n < 0 || (des_ld != 0 && des_ld < 3)) return fail(c, TR_ERR_INVALID_ARG, "bad argument (des_ld: 0 or >= 3)");
+  if (n == 0) return TR_OK;
+  if (!initial_states || !des) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());
+  const int S = c->K.state_size;
+  trk::IkParams prm;
+  int rc;
+  if ((rc = ik_params(c, params, lo, hi, prm))) return rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  tr_ctx::IkDev &k = c->ik;
+  const int64_t chunk = ik_chunk(c);
+  std::vector<double> dbuf;
+  int64_t rounds = 0;
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    HIP_TRY(c, hipMemcpy(k.io_s, initial_states + off * S, (size_t)(m * S) * sizeof(double), hipMemcpyHostToDevice));
+    if (des_ld == 0) {
+      HIP_TRY(c, hipMemcpy(k.io_3, des, 3 * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      dbuf.resize((size_t)(m * 3));
+      for (int64_t i = 0; i < m; i++) for (int q = 0; q < 3; q++) dbuf[(size_t)(i * 3 + q)] = des[(off + i) * des_ld + q];
+      HIP_TRY(c, hipMemcpy(k.io_3, dbuf.data(), (size_t)(m * 3) * sizeof(double), hipMemcpyHostToDevice));
+    }
+    // (io_s / io_3 are read by ik_init before ik_finish overwrites them with the results)
+    if ((rc = ik_chunk_solve(c, prm, k.io_s, m, k.io_3, des_ld ? 3 : 0, k.io_s, k.io_3, k.io_e, k.io_i, k.io_c, nullptr, rounds))) return rc;
+    if (states_out) HIP_TRY(c, hipMemcpy(states_out + off * S, k.io_s, (size_t)(m * S) * sizeof(double), hipMemcpyDeviceToHost));
+    if (tips_out) HIP_TRY(c, hipMemcpy(tips_out + off * 3, k.io_3, (size_t)(m * 3) * sizeof(double), hipMemcpyDeviceToHost));
+    if (error_out) HIP_TRY(c, hipMemcpy(error_out + off, k.io_e, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    if (iters_out) HIP_TRY(c, hipMemcpy(iters_out + off, k.io_i, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (fk_calls_out) HIP_TRY(c, hipMemcpy(fk_calls_out + off, k.io_c, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  if (rounds_out) *rounds_out = rounds;
+  return TR_OK;
+}
+
+}  // extern "C"

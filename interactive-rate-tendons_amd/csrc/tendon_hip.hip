@@ -38,8 +38,11 @@
 #include "cache_merge.hpp"
 #include "env_kernel.hpp"
 #include "sample.hpp"
+#include "ik_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
+struct tr_ctx;
+namespace { void ik_release(tr_ctx *c); }   // ik_host.inc
 
 namespace {
 
@@ -231,6 +234,17 @@ struct tr_ctx {
   } samp;
   // pinned staging for host arrays that are uploaded by a synchronous call (upload_staged)
   void *h_stage = nullptr; size_t h_stage_cap = 0;
+  // tip Jacobian / IK (ik_host.inc): the expansion's K1 lanes and the per-problem state of one chunk of problems, grow-only
+  struct IkDev {
+    int64_t probs = 0, lanes = 0;
+    double *xs = nullptr, *tips = nullptr;                          // [lanes][S], [lanes][3]
+    double *p = nullptr, *pn = nullptr, *f = nullptr, *J = nullptr, *des = nullptr;   // [probs][S | 3 | 3 S | 3]
+    double *err2 = nullptr, *mu = nullptr, *nu = nullptr;
+    int32_t *iters = nullptr, *calls = nullptr, *list[2] = {nullptr, nullptr};
+    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    double *io_s = nullptr, *io_3 = nullptr, *io_e = nullptr;       // staging of the host-array forms
+    int32_t *io_i = nullptr, *io_c = nullptr;
+  } ik;
   // instrumentation
   bool profiling = false;
   std::vector<EventPair> events[TR_PROFILE_SLOTS];
@@ -1083,6 +1097,7 @@ void tr_destroy(tr_ctx *c) {
     trk::merge_free(ro.ms);
   }
   if (c->d_fb_count) (void)hipFree(c->d_fb_count);
+  ik_release(c);
   delete c;
 }
 
@@ -2191,3 +2206,4 @@ int tr_profile_end(tr_ctx *c) {
 
 #include "edge_host.inc"
 #include "sample_host.inc"
+#include "ik_host.inc"

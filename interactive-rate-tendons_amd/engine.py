@@ -163,6 +163,96 @@ class Engine:
                                                 npts.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(p=p, R=R, L=Lb, L_i=Li, converged=conv.astype(bool), n_points=npts)
 
+    # ---- tip positions, tip Jacobian, tip IK (tr_fk_tips / tr_tip_jacobian / tr_ik_batch, include/tendon_hip.h) ----------------
+    def fk_tips(self, states):
+        """fk_batch's last point of every state, without the backbone: (n, 3) tips and (n,) converged."""
+        st = self._states(states)
+        n = st.shape[0]
+        tips = np.empty((n, 3))
+        conv = np.empty(n, dtype=np.uint8)
+        L.check(self._ctx, self.lib.tr_fk_tips(self._ctx, _dp(st), n, _dp(tips), conv.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return tips, conv.astype(bool)
+
+    def fk_tips_dev(self, d_states, n, d_tips, d_conv=None, stream=None):
+        torch = _torch()
+        ps = self._check_dev(d_states, torch.float64, n * self.state_size, "d_states")
+        pt = self._check_dev(d_tips, torch.float64, 3 * n, "d_tips")
+        pc = self._check_dev(d_conv, torch.uint8, n, "d_conv") if d_conv is not None else None
+        L.check(self._ctx, self.lib.tr_fk_tips_dev(self._ctx, ps, int(n), pt, pc, self._stream_ptr(stream)))
+
+    def tip_jacobian(self, states, delta=1e-6, want_tips=False):
+        """Central-difference tip Jacobians through tip_control's FK wrapper: (n, 3, S) [, f(p) (n, 3)]."""
+        st = self._states(states)
+        n, S = st.shape
+        J = np.empty((n, 3, S))
+        tips = np.empty((n, 3)) if want_tips else None
+        L.check(self._ctx, self.lib.tr_tip_jacobian(self._ctx, _dp(st), n, float(delta), _dp(tips) if want_tips else None, _dp(J)))
+        return (J, tips) if want_tips else J
+
+    def tip_jacobian_dev(self, d_states, n, d_J, delta=1e-6, d_tips=None, stream=None):
+        torch = _torch()
+        S = self.state_size
+        ps = self._check_dev(d_states, torch.float64, n * S, "d_states")
+        pj = self._check_dev(d_J, torch.float64, 3 * S * n, "d_J")
+        pt = self._check_dev(d_tips, torch.float64, 3 * n, "d_tips") if d_tips is not None else None
+        L.check(self._ctx, self.lib.tr_tip_jacobian_dev(self._ctx, ps, int(n), float(delta), pt, pj, self._stream_ptr(stream)))
+
+    @staticmethod
+    def _ik_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta):
+        return L.TrIkParams(int(max_iters), float(mu_init), float(stop_threshold_JT_err_inf), float(stop_threshold_Dp),
+                            float(stop_threshold_err), float(finite_difference_delta))
+
+    def _ik_bounds(self, bounds):
+        if bounds is None:
+            return None, None, None
+        lo, hi = _f64(bounds[0]), _f64(bounds[1])
+        if lo.shape != (self.state_size,) or hi.shape != (self.state_size,):
+            raise L.InvalidArgument("State is not the right size")
+        return (lo, hi), _dp(lo), _dp(hi)
+
+    def ik_batch(self, initial_states, des, bounds=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9,
+                 stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6):
+        """Batched tip IK on the device (tr_ik_batch): des is (3,) or (n, 3); bounds (lo, hi) or None = Bounds::from_robot.
+        Returns dict(state, tip, error, iters, num_fk_calls, rounds)."""
+        st = self._states(initial_states)
+        n, S = st.shape
+        d = _f64(des)
+        if d.shape == (3,):
+            d_ld = 0
+        elif d.shape == (n, 3):
+            d_ld = 3
+        else:
+            raise L.InvalidArgument("des must be (3,) or (n, 3)")
+        keep, plo, phi = self._ik_bounds(bounds)
+        prm = self._ik_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta)
+        state, tip, err = np.empty((n, S)), np.empty((n, 3)), np.empty(n)
+        iters, calls = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        rounds = C.c_int64(0)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        L.check(self._ctx, self.lib.tr_ik_batch(self._ctx, C.byref(prm), _dp(st), n, _dp(d), d_ld, plo, phi, _dp(state), _dp(tip),
+                                                _dp(err), i32(iters), i32(calls), C.byref(rounds)))
+        return dict(state=state, tip=tip, error=err, iters=iters, num_fk_calls=calls, rounds=int(rounds.value))
+
+    def ik_batch_dev(self, d_initial_states, n, d_des, d_states_out, d_tips_out=None, d_error_out=None, d_iters_out=None,
+                     d_fk_calls_out=None, des_ld=3, bounds=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9,
+                     stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6, stream=None):
+        """tr_ik_batch_dev: device tensors in and out (des_ld = 0: one goal row for all); returns the number of rounds."""
+        torch = _torch()
+        S = self.state_size
+        ps = self._check_dev(d_initial_states, torch.float64, n * S, "d_initial_states")
+        pd = self._check_dev(d_des, torch.float64, 3 if des_ld == 0 else (n - 1) * des_ld + 3, "d_des")
+        po = self._check_dev(d_states_out, torch.float64, n * S, "d_states_out")
+        pt = self._check_dev(d_tips_out, torch.float64, 3 * n, "d_tips_out") if d_tips_out is not None else None
+        pe = self._check_dev(d_error_out, torch.float64, n, "d_error_out") if d_error_out is not None else None
+        pi = self._check_dev(d_iters_out, torch.int32, n, "d_iters_out") if d_iters_out is not None else None
+        pc = self._check_dev(d_fk_calls_out, torch.int32, n, "d_fk_calls_out") if d_fk_calls_out is not None else None
+        keep, plo, phi = self._ik_bounds(bounds)
+        prm = self._ik_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta)
+        rounds = C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_ik_batch_dev(self._ctx, C.byref(prm), ps, int(n), pd, int(des_ld), plo, phi, po, pt, pe, pi, pc,
+                                                    C.byref(rounds), self._stream_ptr(stream)))
+        return int(rounds.value)
+
     def validate_batch(self, states, want_tips=True, want_flags=True):
         st = self._states(states)
         n = st.shape[0]

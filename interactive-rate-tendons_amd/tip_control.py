@@ -170,6 +170,33 @@ def inverse_kinematics(robot, initial_state, des, max_iters=100, mu_init=0.1, st
     return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
 
 
+def inverse_kinematics_batch_device(robot, initial_states, des, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9,
+                                    stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6, device=0):
+    """inverse_kinematics_batch with the whole iteration on the device (tr_ik_batch): the same scheme, arguments and result
+    fields; `launches` is the number of rounds (one K1 launch and one LM-step launch each)."""
+    p = np.asarray(initial_states, dtype=np.float64)
+    if p.ndim == 1:
+        p = p.reshape(1, -1)
+    if p.shape[1] != robot.state_size():
+        raise L.InvalidArgument("State is not the right size")
+    des = np.asarray(des, dtype=np.float64)
+    if des.ndim == 2 and des.shape[0] == 1 and p.shape[0] != 1:
+        des = des[0]
+    r = robot.engine(device).ik_batch(p, des, max_iters=max_iters, mu_init=mu_init, stop_threshold_JT_err_inf=stop_threshold_JT_err_inf,
+                                      stop_threshold_Dp=stop_threshold_Dp, stop_threshold_err=stop_threshold_err,
+                                      finite_difference_delta=finite_difference_delta)
+    return dict(state=r["state"], tip=r["tip"], error=r["error"], iters=r["iters"].astype(int),
+                num_fk_calls=r["num_fk_calls"].astype(int), launches=r["rounds"])
+
+
+def inverse_kinematics_device(robot, initial_state, des, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9,
+                              stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6, device=0):
+    """tip_control::inverse_kinematics for one start state, on the device."""
+    r = inverse_kinematics_batch_device(robot, np.asarray(initial_state, float).reshape(1, -1), des, max_iters, mu_init,
+                                        stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta, device)
+    return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
+
+
 def roadmap_ik(robot, goal_tip, vertex_states, vertex_tips, k=10, tolerance=1e-4, **lm):
     """The IK leg of VoxelCachedLazyPRM::roadmapIk (:3164-3205): start from the k roadmap vertices whose tips are
     nearest to the goal, all k solves in the same launches; returns the batch result sorted by error plus the
