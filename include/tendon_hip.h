@@ -639,8 +639,8 @@ int tr_edge_schedule_last(const tr_ctx *ctx, uint32_t stats[4]);
  *   TENDON_HIP_FB_CAP=n             columns of the fallback pass's point workspace (default: one resident round of waves)
  *   TENDON_HIP_RETRACT_SORT=n       retraction robots: batches of at least n configurations are ordered by backbone length
  *                                   (0 = never); TENDON_HIP_RETRACT_KBEGIN_OFF: no per-wave loop start in that order
- *   TENDON_HIP_CH_SCALE=x           milestone spacing of the self-collision proof in robot radii (default 2)
- * Read per call (the tests switch between two paths inside one process):
+ * Read per call (the tests switch between two paths inside one process; the switches of tr_roadmap_*: once, at the start of the call
+ * that uses them -- csrc/roadmap.hip: read_switches):
  *   TENDON_HIP_KNN=lanes            neighbour search by the lane-per-query kernel for every k (default: wave per query up to k = 64);
  *                                   TENDON_HIP_KNN_CELL=x scales its cell width (tuning)
  *   TENDON_HIP_MERGE=sort           edge voxel sets merged by the segmented sort (default: the per-edge LDS table);

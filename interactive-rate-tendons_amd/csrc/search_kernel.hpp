@@ -3,7 +3,7 @@
 // QUERY, thousands of queries in flight.  It is roadmap.hip's host `astar` -- the same heuristic (state-space distance, sharpened by the
 // landmark bounds), the same relaxation rule (a vertex whose cost improves is opened again), the same stopping rule (the goal leaves
 // the open list as its minimum) -- shaped for a wave:
-//   * a step takes up to SR_K = 6 vertices off the open list at once (the minimum, and the smallest of the other lanes' minima) -- as
+//   * a step takes up to SR_K = 12 vertices off the open list at once (the minimum, and the smallest of the other lanes' minima) -- as
 //     many as their arcs fill the wave's 64 lanes, one arc per lane: an open-list entry carries its vertex's arc count next to the
 //     vertex (5 bits of the word), so the lanes are dealt out before anything is loaded (~5 vertices of a 10-nearest roadmap).  Arcs
 //     live in ADJACENCY ROWS at a fixed stride of SR_D = 16 per vertex (a vertex with more chains further rows through its last slot,
@@ -106,11 +106,10 @@ struct SearchArgs {
 // Values that are the same in every lane are told so to the compiler (readfirstlane): counters, thresholds and the popped vertices
 // live in scalar registers and the loops around them branch on the scalar unit instead of being predicated lane by lane.
 __device__ __forceinline__ int sr_u(int x) { return __builtin_amdgcn_readfirstlane(x); }
-// The lane index as the loops below see it: re-read through an empty asm once per iteration, so that the optimiser cannot prove the
-// `lane == 0` tests of consecutive iterations equal.  Without this it threads the back edge of the query loop for the 63 lanes that
-// do not draw the ticket straight into the loop body -- a second, inner loop that lane 0 is not part of -- and the cross-lane
-// operations (readfirstlane, ballot, shuffles) of the body then run without lane 0, who alone writes the list heads (hipcc 7.2:
-// faults on garbage indices; found in the listing as a Depth-2 copy of the query loop with the ticket's register set to zero).
+// A value re-read through an empty asm, so that the optimiser cannot prove two tests of it equal.  It was the first answer to the
+// duplicated ticket site of the query loop (hipcc 7.2 threaded the loop's back edge through `if (lane == 0) ticket = atomicAdd(..)`:
+// an inner copy of the loop without lane 0, faults on garbage indices) and is NOT what prevents it now: the ticket is drawn by an
+// atomic every lane executes (the header comment; the loop head in roadmap_astar), and nothing below calls this any more.
 __device__ __forceinline__ int sr_opaque(int x) { asm volatile("" : "+v"(x)); return x; }
 __device__ __forceinline__ double sr_u(double x) {
   const long long b = __double_as_longlong(x);

@@ -205,12 +205,13 @@ def test_windowed_search_with_rotation_and_retraction_metrics(irt, orc, helpers,
         want = np.argsort(d, kind="stable")[:k]
         assert np.array_equal(idx[q], want), (q, idx[q], want)
         assert np.abs(dist[q] - d[want]).max() <= 1e-12
-    os.environ["TENDON_HIP_KNN_HW_DIV"] = "4"
-    try:
-        idx2, dist2 = eng.knn(st, k)
-    finally:
-        os.environ.pop("TENDON_HIP_KNN_HW_DIV")
-    assert np.array_equal(idx, idx2) and np.array_equal(dist, dist2)
+    for cell in ("0.25", "4"):                                 # the same neighbours and distances whatever the cell width
+        os.environ["TENDON_HIP_KNN_CELL"] = cell
+        try:
+            idx2, dist2 = eng.knn(st, k)
+        finally:
+            os.environ.pop("TENDON_HIP_KNN_CELL")
+        assert np.array_equal(idx, idx2) and np.array_equal(dist, dist2), cell
     md = float(np.median(dist[:, 5]))
     idx3, _ = eng.knn(st, k, max_distance=md)
     assert np.array_equal(idx3 >= 0, dist <= md) and np.array_equal(idx3[idx3 >= 0], idx[dist <= md])

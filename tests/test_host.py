@@ -40,6 +40,32 @@ def test_shared_library_exports_every_symbol(irt):
         assert hasattr(lib, s)
 
 
+def test_environment_switches_are_documented_and_alive():
+    """The switch surface stays honest: what csrc/ reads is what the table in include/tendon_hip.h documents, and every switch a
+    test or a benchmark sets is still read by the library or the package (a dead one makes an A/B compare a call with itself)."""
+    name = re.compile(r"TENDON_HIP_[A-Z0-9_]*[A-Z0-9]")
+    pkg = os.path.join(ROOT, "interactive-rate-tendons_amd")
+    csrc = os.path.join(pkg, "csrc")
+    read_c = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".hpp", ".inc")):
+            read_c |= set(re.findall(r'getenv\(\s*"(TENDON_HIP_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    header = open(os.path.join(ROOT, "include", "tendon_hip.h")).read()
+    table = header[header.index("/* Environment switches"):]
+    documented = set(name.findall(table[:table.index("*/")]))
+    assert read_c == documented, (sorted(read_c - documented), sorted(documented - read_c))
+    read_py = set()
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            read_py |= set(name.findall(open(os.path.join(pkg, f)).read()))
+    tests = os.path.join(ROOT, "tests")
+    users = [os.path.join(tests, f) for f in sorted(os.listdir(tests)) if f.endswith(".py")] + \
+            [os.path.join(ROOT, f) for f in sorted(os.listdir(ROOT)) if f.startswith("bench") and f.endswith(".py")]
+    for f in users:
+        dead = set(name.findall(open(f).read())) - read_c - read_py
+        assert not dead, (f, sorted(dead))
+
+
 def test_library_contains_gfx950_code_object(irt):
     data = open(irt.LIB_PATH, "rb").read()
     assert b"gfx950" in data and b"fk_rk4_batch_uniform" in data and b"backbone_voxel_sweep" in data and b"fk_sweep_fused" in data
