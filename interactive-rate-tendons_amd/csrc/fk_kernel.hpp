@@ -18,7 +18,10 @@
 //    A_i is symmetric, G = B^T, H is symmetric, K_se/K_bt are diagonal, and the 6x6 solve
 //    [v';u'] = M^-1 [d;c] with M = [[K_se+A, B^T],[B, K_bt+H]] is an unrolled symmetric L D L^T
 //    factorisation (round 4; before: block elimination with adjugate 3x3 inverses);
-//  * (p, L, L_i) are pure quadratures (nothing depends on them), so they keep no stage copy.
+//  * (p, L, L_i) are pure quadratures (nothing depends on them), so they keep no stage copy;
+//  * what the diagonal stiffnesses make redundant is not computed: the moment balance keeps the two factors of its cross
+//    products that survive K_bt = diag(kb0, kb0, kb2), K_se = diag(ks0, ks0, ks2); the stiffnesses and the rhat^2 terms are
+//    folded into the accumulators of A and H; the position and frame sums of a step are FMA chains scaled once;
 //  * __launch_bounds__(64, 2): two waves per SIMD (<= 256 registers) measured 16 % faster than the
 //    365-register single-wave allocation the compiler picks when unconstrained.
 // fp64 throughout.  Contraction to FMA is enabled here (parity with the oracle is by tolerance:
@@ -73,10 +76,13 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
   //   A = sum q pd^T - (sum c|pd|^2) I
   //   B = sum rhat A_i   = sum g pd^T - sum c|pd|^2 rhat
   //   H = -sum B_i rhat  = sum g e^T  + sum c|pd|^2 rhat^2
-  //   a = sum q (pd.w) - c|pd|^2 w,   b = sum r x a_i,   w = u x (pd + r') + r''
-  double Axx = 0, Axy = 0, Axz = 0, Ayy = 0, Ayz = 0, Azz = 0, Z = 0;
+  //   a = sum q pd^T w - c|pd|^2 w,   b = sum r x a_i,   w = u x (pd + r') + r''
+  // The diagonals start at the stiffnesses (the first FMA of each chain takes the constant as its addend), and the rhat^2
+  // terms, rhat^2 = [[-ry^2, rx ry, 0],[rx ry, -rx^2, 0],[0,0,-(rx^2+ry^2)]], go into H tendon by tendon: the tail below
+  // adds nothing to K_se + A or K_bt + H but -Z on the first.
+  double Axx = K.ks0, Axy = 0, Axz = 0, Ayy = K.ks0, Ayz = 0, Azz = K.ks2, Z = 0;
   double B00 = 0, B01 = 0, B02 = 0, B10 = 0, B11 = 0, B12 = 0, B20 = 0, B21 = 0, B22 = 0, Q1 = 0, Q2 = 0;
-  double Hxx = 0, Hxy = 0, Hxz = 0, Hyy = 0, Hyz = 0, Hzz = 0, P1 = 0, P2 = 0, P3 = 0;
+  double Hxx = K.kb0, Hxy = 0, Hxz = 0, Hyy = K.kb0, Hyz = 0, Hzz = K.kb2;
   double ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
 #pragma unroll
   for (int j = 0; j < N; j++) {
@@ -89,7 +95,7 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double pdx = (v[0] + rdx) - u[2] * ry;
     const double pdy = (v[1] + rdy) + u[2] * rx;
     const double pdz = __builtin_fma(u[0], ry, __builtin_fma(-u[1], rx, v[2]));
-    const double s2 = pdx * pdx + pdy * pdy + pdz * pdz;
+    const double sxy = pdx * pdx + pdy * pdy, s2 = sxy + pdz * pdz;
     const double rs = fast_rsqrt(s2);
     sdot[j] = s2 * rs;
     // c = -tau / |pd|^3 and c |pd|^2 = -tau / |pd| from the same reciprocal root (one multiply fewer than c * s2)
@@ -98,16 +104,21 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double qx = c * pdx, qy = c * pdy, qz = c * pdz;
     Axx += qx * pdx; Axy += qx * pdy; Axz += qx * pdz; Ayy += qy * pdy; Ayz += qy * pdz; Azz += qz * pdz;
     Z += cs2;
-    // e = r x pd, g = c e  (r_z = 0)
-    const double ex = ry * pdz, ey = -rx * pdz, ez = rx * pdy - ry * pdx;
-    const double gx = c * ex, gy = c * ey, gz = c * ez;
+    // e = r x pd = (ry pdz, -rx pdz, ez), g = c e  (r_z = 0)
+    const double ez = rx * pdy - ry * pdx;
+    const double gx = ry * qz, gy = -rx * qz, gz = c * ez;
     B00 += gx * pdx; B01 += gx * pdy; B02 += gx * pdz;
     B10 += gy * pdx; B11 += gy * pdy; B12 += gy * pdz;
     B20 += gz * pdx; B21 += gz * pdy; B22 += gz * pdz;
-    Hxx += gx * ex; Hxy += gx * ey; Hxz += gx * ez; Hyy += gy * ey; Hyz += gy * ez; Hzz += gz * ez;
+    Hxz += gx * ez; Hyz += gy * ez; Hzz += gz * ez;
+    // The x-y block of g e^T is c pdz^2 (ry^2, -rx ry, rx^2) and that of c|pd|^2 rhat^2 is c|pd|^2 (-ry^2, rx ry, -rx^2): together
+    // -c (pdx^2 + pdy^2) (ry^2, -rx ry, rx^2), from the partial sum of |pd|^2 -- no e_x, e_y, and no difference of two nearly
+    // equal terms (pdz is close to 1, pdx and pdy are small).
+    const double mxy = c * sxy, mx = mxy * rx, my = mxy * ry;
+    Hxx -= my * ry; Hxy += mx * ry; Hyy -= mx * rx;
     const double t1 = cs2 * rx, t2 = cs2 * ry;
     Q1 += t1; Q2 += t2;
-    P1 += t1 * rx; P2 += t1 * ry; P3 += t2 * ry;
+    Hzz -= t1 * rx; Hzz -= t2 * ry;
     // w = u x (pd + r') + r''
     const double hx = pdx + rdx, hy = pdy + rdy, hz = pdz;
     const double wx = __builtin_fma(u[1], hz, __builtin_fma(-u[2], hy, rddx));
@@ -123,20 +134,19 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
 #define TRK_FMA __builtin_fma
   // - sum c|pd|^2 rhat, rhat = [[0,0,ry],[0,0,-rx],[-ry,rx,0]]
   B02 -= Q2; B12 += Q1; B20 += Q2; B21 -= Q1;
-  // + sum c|pd|^2 rhat^2, rhat^2 = [[-ry^2, rx ry, 0],[rx ry, -rx^2, 0],[0,0,-(rx^2+ry^2)]]
-  Hxy += P2;
-  // c = -u x (K_bt u) - v x (K_se (v - e3)) - b ;  d = -u x (K_se (v - e3)) - a
-  const double kux = K.kb0 * u[0], kuy = K.kb0 * u[1], kuz = K.kb2 * u[2];
+  // c = -u x (K_bt u) - v x (K_se (v - e3)) - b ;  d = -u x (K_se (v - e3)) - a.  With K_bt = diag(kb0, kb0, kb2) and
+  // K_se = diag(ks0, ks0, ks2) -- all RobotK can hold -- the two cross products of c lose their z component and share a factor:
+  //   u x (K_bt u) = (kb2 - kb0) u2 (u1, -u0, 0),   v x (K_se (v - e3)) = w (v1, -v0, 0),   w = ks2 (v2 - 1) - ks0 v2
   const double svx = K.ks0 * v[0], svy = K.ks0 * v[1], svz = K.ks2 * (v[2] - 1.0);
-  const double cx = TRK_FMA(u[2], kuy, TRK_FMA(-u[1], kuz, TRK_FMA(v[2], svy, TRK_FMA(-v[1], svz, -bx))));
-  const double cy = TRK_FMA(u[0], kuz, TRK_FMA(-u[2], kux, TRK_FMA(v[0], svz, TRK_FMA(-v[2], svx, -by))));
-  const double cz = TRK_FMA(u[1], kux, TRK_FMA(-u[0], kuy, TRK_FMA(v[1], svx, TRK_FMA(-v[0], svy, -bz))));
+  const double dku = K.dkb * u[2], w = TRK_FMA(-K.ks0, v[2], svz);
+  const double cx = TRK_FMA(-u[1], dku, TRK_FMA(-v[1], w, -bx));
+  const double cy = TRK_FMA(u[0], dku, TRK_FMA(v[0], w, -by));
+  const double cz = -bz;
   const double dx = TRK_FMA(u[2], svy, TRK_FMA(-u[1], svz, -ax));
   const double dy = TRK_FMA(u[0], svz, TRK_FMA(-u[2], svx, -ay));
   const double dz = TRK_FMA(u[1], svx, TRK_FMA(-u[0], svy, -az));
   // M11 = K_se + A - Z I (symmetric): the leading block of the 6 x 6 system solved below
-  const double ksz0 = K.ks0 - Z, ksz2 = K.ks2 - Z;
-  const double m00 = ksz0 + Axx, m01 = Axy, m02 = Axz, m11 = ksz0 + Ayy, m12 = Ayz, m22 = ksz2 + Azz;
+  const double m00 = Axx - Z, m01 = Axy, m02 = Axz, m11 = Ayy - Z, m12 = Ayz, m22 = Azz - Z;
 #ifndef TRK_SOLVE_SCHUR
   // The symmetric 6 x 6 system [[M11, B^T], [B, K_bt + H]] [v'; u'] = [d; c] by an unrolled L D L^T factorisation without pivoting:
   // 35 FMAs, 15 products and six reciprocals to factor, 36 operations for the two triangular solves (181 flops, ~105 instructions).
@@ -147,7 +157,7 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
   {
     // (no contraction beyond the FMAs written out: every kernel that holds this body then forms the same bits)
 #pragma clang fp contract(off)
-    const double n00 = (K.kb0 - P3) + Hxx, n01 = Hxy, n02 = Hxz, n11 = (K.kb0 - P1) + Hyy, n12 = Hyz, n22 = ((K.kb2 - P1) - P3) + Hzz;
+    const double n00 = Hxx, n01 = Hxy, n02 = Hxz, n11 = Hyy, n12 = Hyz, n22 = Hzz;     // K_bt + H
     const double p0 = m00;
     const double r0 = fast_rcp(p0);
     const double w10 = m01, l10 = w10 * r0;
@@ -205,13 +215,13 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
                T12 = TRK_FMA(B10, i02, TRK_FMA(B11, i12, B12 * i22));
   const double T20 = TRK_FMA(B20, i00, TRK_FMA(B21, i01, B22 * i02)), T21 = TRK_FMA(B20, i01, TRK_FMA(B21, i11, B22 * i12)),
                T22 = TRK_FMA(B20, i02, TRK_FMA(B21, i12, B22 * i22));
-  // Schur complement S = (K_bt + H) - T B^T (symmetric), with H's rhat^2 terms folded into the first operand
-  const double s00 = TRK_FMA(-T02, B02, TRK_FMA(-T01, B01, TRK_FMA(-T00, B00, (K.kb0 - P3) + Hxx)));
+  // Schur complement S = (K_bt + H) - T B^T (symmetric); Hxx ... Hzz hold K_bt + H
+  const double s00 = TRK_FMA(-T02, B02, TRK_FMA(-T01, B01, TRK_FMA(-T00, B00, Hxx)));
   const double s01 = TRK_FMA(-T02, B12, TRK_FMA(-T01, B11, TRK_FMA(-T00, B10, Hxy)));
   const double s02 = TRK_FMA(-T02, B22, TRK_FMA(-T01, B21, TRK_FMA(-T00, B20, Hxz)));
-  const double s11 = TRK_FMA(-T12, B12, TRK_FMA(-T11, B11, TRK_FMA(-T10, B10, (K.kb0 - P1) + Hyy)));
+  const double s11 = TRK_FMA(-T12, B12, TRK_FMA(-T11, B11, TRK_FMA(-T10, B10, Hyy)));
   const double s12 = TRK_FMA(-T12, B22, TRK_FMA(-T11, B21, TRK_FMA(-T10, B20, Hyz)));
-  const double s22 = TRK_FMA(-T22, B22, TRK_FMA(-T21, B21, TRK_FMA(-T20, B20, ((K.kb2 - P1) - P3) + Hzz)));
+  const double s22 = TRK_FMA(-T22, B22, TRK_FMA(-T21, B21, TRK_FMA(-T20, B20, Hzz)));
   // rhs = c - B y
   const double ex = TRK_FMA(-B02, yz, TRK_FMA(-B01, yy_, TRK_FMA(-B00, yx, cx)));
   const double ey = TRK_FMA(-B12, yz, TRK_FMA(-B11, yy_, TRK_FMA(-B10, yx, cy)));
@@ -308,6 +318,49 @@ __device__ __forceinline__ void initial_bending(const double (&tau)[N], const do
   }
 }
 
+// The position quadrature of one RK4 step, p += h/6 (k1 + 2 (k2 + k3) + k4) with k = R v at the stage state: the weighted
+// sum is gathered as FMA chains (qm = k2 + k3, qs = k1 + 2 qm + k4) and scaled once, 14 instructions per coordinate and
+// step where weighting every stage on its own (p += b_st k_st) takes 16.  Called once per stage, st = 0 .. 3.
+__device__ __forceinline__ void position_quadrature(int st, const double (&sR)[9], const double (&sv)[3], double b1,
+                                                    double (&qs)[3], double (&qm)[3], double (&p)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const double r0 = sR[c], r1 = sR[3 + c], r2 = sR[6 + c];
+    if (st == 0) qs[c] = __builtin_fma(r2, sv[2], __builtin_fma(r1, sv[1], r0 * sv[0]));
+    else if (st == 1) qm[c] = __builtin_fma(r2, sv[2], __builtin_fma(r1, sv[1], r0 * sv[0]));
+    else if (st == 2) {
+      qm[c] = __builtin_fma(r2, sv[2], __builtin_fma(r1, sv[1], __builtin_fma(r0, sv[0], qm[c])));
+      qs[c] = __builtin_fma(2.0, qm[c], qs[c]);
+    } else {
+      qs[c] = __builtin_fma(r2, sv[2], __builtin_fma(r1, sv[1], __builtin_fma(r0, sv[0], qs[c])));
+      p[c] = __builtin_fma(b1, qs[c], p[c]);
+    }
+  }
+}
+
+// The frame's rate R' = R uhat (col0 = R1 uz - R2 uy, col1 = R2 ux - R0 uz, col2 = R0 uy - R1 ux) at the stage state, and its
+// weighted sum over the step, aR = k1 + 2 k2 + 2 k3 + k4 (the step ends with R += h/6 aR).  Stages 0 .. 2 need their rate
+// itself (dR: the next stage state is built from it); the last stage's is only ever summed, so its two products go straight
+// into aR's FMA chain: 11 instructions per entry and step where R + sum b_st k_st took 12.
+__device__ __forceinline__ void frame_rate(int st, const double (&sR)[9], const double (&su)[3], double (&dR)[9], double (&aR)[9]) {
+#pragma clang fp contract(fast)
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const double r0 = sR[0 + r], r1 = sR[3 + r], r2 = sR[6 + r];
+    if (st < 3) {
+      dR[0 + r] = r1 * su[2] - r2 * su[1];
+      dR[3 + r] = r2 * su[0] - r0 * su[2];
+      dR[6 + r] = r0 * su[1] - r1 * su[0];
+#pragma unroll
+      for (int c = 0; c < 9; c += 3) aR[c + r] = (st == 0) ? dR[c + r] : __builtin_fma(2.0, dR[c + r], aR[c + r]);
+    } else {
+      aR[0 + r] = __builtin_fma(r1, su[2], __builtin_fma(-r2, su[1], aR[0 + r]));
+      aR[3 + r] = __builtin_fma(r2, su[0], __builtin_fma(-r0, su[2], aR[3 + r]));
+      aR[6 + r] = __builtin_fma(r0, su[1], __builtin_fma(-r1, su[0], aR[6 + r]));
+    }
+  }
+}
+
 // One classical RK4 step of size h (Boost.odeint runge_kutta4 tableau: a = {1/2},{0,1/2},{0,0,1};
 // b = {1/6,1/3,1/3,1/6}; c = {0,1/2,1/2,1}) of the state (R, v, u | p, L, L_i), with the routing
 // produced on demand, tendon by tendon, by `route(t, j, r6)` at t, t + h/2 (stages 2 and 3) and t + h.
@@ -322,10 +375,8 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
   const double b1 = h * (1.0 / 6.0), b2 = h * (1.0 / 3.0);
   double aR[9], av[3], au[3];
 #pragma unroll
-  for (int q = 0; q < 9; q++) aR[q] = R[q];
-#pragma unroll
   for (int q = 0; q < 3; q++) { av[q] = v[q]; au[q] = u[q]; }
-  double sR[9], sv[3], su[3];
+  double sR[9], sv[3], su[3], qs[3], qm[3];
 #pragma unroll
   for (int q = 0; q < 9; q++) sR[q] = R[q];
 #pragma unroll
@@ -341,9 +392,7 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
     const double aw = (st == 2) ? h : hh;
     double dv[3], du[3], sd[N];
     strain_rates_routed<N>(sv, su, tau, [&](int j, double (&r6)[6]) { route(ts, j, r6); }, K, dv, du, sd);
-    p[0] += bw * (sR[0] * sv[0] + sR[3] * sv[1] + sR[6] * sv[2]);
-    p[1] += bw * (sR[1] * sv[0] + sR[4] * sv[1] + sR[7] * sv[2]);
-    p[2] += bw * (sR[2] * sv[0] + sR[5] * sv[1] + sR[8] * sv[2]);
+    position_quadrature(st, sR, sv, b1, qs, qm, p);
     {
       const double v2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
       Lb += bw * (v2 * fast_rsqrt(v2));
@@ -351,15 +400,7 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
 #pragma unroll
     for (int j = 0; j < N; j++) Li[j] += bw * sd[j];
     double dR[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const double r0 = sR[0 + r], r1 = sR[3 + r], r2 = sR[6 + r];
-      dR[0 + r] = r1 * su[2] - r2 * su[1];
-      dR[3 + r] = r2 * su[0] - r0 * su[2];
-      dR[6 + r] = r0 * su[1] - r1 * su[0];
-    }
-#pragma unroll
-    for (int q = 0; q < 9; q++) aR[q] += bw * dR[q];
+    frame_rate(st, sR, su, dR, aR);
 #pragma unroll
     for (int q = 0; q < 3; q++) { av[q] += bw * dv[q]; au[q] += bw * du[q]; }
     if (st < 3) {
@@ -370,7 +411,7 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
     }
   }
 #pragma unroll
-  for (int q = 0; q < 9; q++) R[q] = aR[q];
+  for (int q = 0; q < 9; q++) R[q] = __builtin_fma(b1, aR[q], R[q]);
 #pragma unroll
   for (int q = 0; q < 3; q++) { v[q] = av[q]; u[q] = au[q]; }
 }
@@ -477,13 +518,12 @@ __device__ __forceinline__ void fk_uniform_body(
     const double *__restrict__ rt = tab + (size_t)(1 + 3 * k) * (N * 6);
     const double hh = h * 0.5;
     const double b1 = h * (1.0 / 6.0), b2 = h * (1.0 / 3.0);
-    // accumulators start at the current state
+    // v and u accumulate from the current state; the frame's rates are summed on their own (frame_rate)
     double aR[9], av[3], au[3];
-#pragma unroll
-    for (int q = 0; q < 9; q++) aR[q] = R[q];
 #pragma unroll
     for (int q = 0; q < 3; q++) { av[q] = v[q]; au[q] = u[q]; }
     double sR[9], sv[3], su[3];                // stage state
+    double qs[3], qm[3];                       // position quadrature (position_quadrature)
 #pragma unroll
     for (int q = 0; q < 9; q++) sR[q] = R[q];
 #pragma unroll
@@ -497,9 +537,7 @@ __device__ __forceinline__ void fk_uniform_body(
       double dv[3], du[3], sd[N];
       strain_rates<N>(sv, su, tau, ri, K, dv, du, sd);
       // quadratures: p' = R v, L' = |v|, L_i' = |pd_i|
-      p[0] += bw * (sR[0] * sv[0] + sR[3] * sv[1] + sR[6] * sv[2]);
-      p[1] += bw * (sR[1] * sv[0] + sR[4] * sv[1] + sR[7] * sv[2]);
-      p[2] += bw * (sR[2] * sv[0] + sR[5] * sv[1] + sR[8] * sv[2]);
+      position_quadrature(st, sR, sv, b1, qs, qm, p);
       if (WANT_L && out.L) {                               // wave-uniform
         const double v2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
         Lb += bw * (v2 * fast_rsqrt(v2));
@@ -511,17 +549,8 @@ __device__ __forceinline__ void fk_uniform_body(
 #pragma unroll
         for (int j = 0; j < N; j++) Li[j] += bw * sd[j];
       }
-      // R' = R uhat : col0 = R1*uz - R2*uy ; col1 = R2*ux - R0*uz ; col2 = R0*uy - R1*ux
       double dR[9];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        const double r0 = sR[0 + r], r1 = sR[3 + r], r2 = sR[6 + r];
-        dR[0 + r] = r1 * su[2] - r2 * su[1];
-        dR[3 + r] = r2 * su[0] - r0 * su[2];
-        dR[6 + r] = r0 * su[1] - r1 * su[0];
-      }
-#pragma unroll
-      for (int q = 0; q < 9; q++) aR[q] += bw * dR[q];
+      frame_rate(st, sR, su, dR, aR);
 #pragma unroll
       for (int q = 0; q < 3; q++) { av[q] += bw * dv[q]; au[q] += bw * du[q]; }
       if (st < 3) {
@@ -532,7 +561,7 @@ __device__ __forceinline__ void fk_uniform_body(
       }
     }
 #pragma unroll
-    for (int q = 0; q < 9; q++) R[q] = aR[q];
+    for (int q = 0; q < 9; q++) R[q] = __builtin_fma(b1, aR[q], R[q]);
 #pragma unroll
     for (int q = 0; q < 3; q++) { v[q] = av[q]; u[q] = au[q]; }
     if (obs >= 0) store_point(obs);

@@ -309,10 +309,8 @@ __device__ __forceinline__ void fk_retract_body(
       const double b1 = h * (1.0 / 6.0), b2 = h * (1.0 / 3.0);
       double aR[9], av[3], au[3];
 #pragma unroll
-      for (int q = 0; q < 9; q++) aR[q] = R[q];
-#pragma unroll
       for (int q = 0; q < 3; q++) { av[q] = v[q]; au[q] = u[q]; }
-      double sR[9], sv[3], su[3];
+      double sR[9], sv[3], su[3], qs[3], qm[3];
 #pragma unroll
       for (int q = 0; q < 9; q++) sR[q] = R[q];
 #pragma unroll
@@ -324,9 +322,7 @@ __device__ __forceinline__ void fk_retract_body(
         const double aw = (st == 2) ? h : hh;
         double dv[3], du[3], sd[N];
         strain_rates<N>(sv, su, tau, ri, K, dv, du, sd);
-        p[0] += bw * (sR[0] * sv[0] + sR[3] * sv[1] + sR[6] * sv[2]);
-        p[1] += bw * (sR[1] * sv[0] + sR[4] * sv[1] + sR[7] * sv[2]);
-        p[2] += bw * (sR[2] * sv[0] + sR[5] * sv[1] + sR[8] * sv[2]);
+        position_quadrature(st, sR, sv, b1, qs, qm, p);
         if (out.L) {                                       // wave-uniform: the validity paths do not ask for the backbone length
           const double v2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
           Lb += bw * (v2 * fast_rsqrt(v2));
@@ -334,15 +330,7 @@ __device__ __forceinline__ void fk_retract_body(
 #pragma unroll
         for (int j = 0; j < N; j++) Li[j] += bw * sd[j];
         double dR[9];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-          const double r0 = sR[0 + r], r1 = sR[3 + r], r2 = sR[6 + r];
-          dR[0 + r] = r1 * su[2] - r2 * su[1];
-          dR[3 + r] = r2 * su[0] - r0 * su[2];
-          dR[6 + r] = r0 * su[1] - r1 * su[0];
-        }
-#pragma unroll
-        for (int q = 0; q < 9; q++) aR[q] += bw * dR[q];
+        frame_rate(st, sR, su, dR, aR);
 #pragma unroll
         for (int q = 0; q < 3; q++) { av[q] += bw * dv[q]; au[q] += bw * du[q]; }
         if (st < 3) {
@@ -353,7 +341,7 @@ __device__ __forceinline__ void fk_retract_body(
         }
       }
 #pragma unroll
-      for (int q = 0; q < 9; q++) R[q] = aR[q];
+      for (int q = 0; q < 9; q++) R[q] = __builtin_fma(b1, aR[q], R[q]);
 #pragma unroll
       for (int q = 0; q < 3; q++) { v[q] = av[q]; u[q] = au[q]; }
     }

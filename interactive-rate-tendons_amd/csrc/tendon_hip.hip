@@ -969,7 +969,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
     const double Ar = M_PI * (ro2 - ri2);
     const double J = 2 * I;
     const double Gmod = rb->E / (2 * (1 + rb->nu));
-    K.kb0 = rb->E * I; K.kb2 = J * Gmod;
+    K.kb0 = rb->E * I; K.kb2 = J * Gmod; K.dkb = K.kb2 - K.kb0;
     K.ikb0 = 1 / (rb->E * I); K.ikb2 = 1 / (J * Gmod);
     K.ks0 = Gmod * Ar; K.ks2 = rb->E * Ar;
     K.iks0 = 1 / (Gmod * Ar); K.iks2 = 1 / (rb->E * Ar);

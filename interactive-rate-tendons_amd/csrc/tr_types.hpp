@@ -10,6 +10,7 @@
 struct RobotK {
   double ks0, ks2;            // K_se = diag(G*Ar, G*Ar, E*Ar)
   double kb0, kb2;            // K_bt = diag(E*I, E*I, J*G)
+  double dkb;                 // kb2 - kb0: all that u x (K_bt u) needs (fk_kernel.hpp: strain_rates_routed)
   double iks0, iks2;          // K_se_inv diagonal (computed as 1/x on the host, as the reference does)
   double ikb0, ikb2;          // K_bt_inv diagonal
   double residual_threshold;

@@ -75,7 +75,7 @@ int main() {
   RobotK K{};
   {
     const double ro2 = ro * ro, ri2 = ri * ri, I = 0.25 * M_PI * (ro2 * ro2 - ri2 * ri2), Ar = M_PI * (ro2 - ri2), J = 2 * I, G = E / (2 * (1 + nu));
-    K.kb0 = E * I; K.kb2 = J * G; K.ikb0 = 1 / K.kb0; K.ikb2 = 1 / K.kb2; K.ks0 = G * Ar; K.ks2 = E * Ar; K.iks0 = 1 / K.ks0; K.iks2 = 1 / K.ks2;
+    K.kb0 = E * I; K.kb2 = J * G; K.dkb = K.kb2 - K.kb0; K.ikb0 = 1 / K.kb0; K.ikb2 = 1 / K.kb2; K.ks0 = G * Ar; K.ks2 = E * Ar; K.iks0 = 1 / K.ks0; K.iks2 = 1 / K.ks2;
   }
   K.residual_threshold = 5e-6; K.radius = 0.015; K.L = L; K.dL = dL; K.n_tendons = N; K.n_a = 3; K.n_m = 3; K.state_size = N; K.n_points = 129;
   std::vector<StepK> steps;
