@@ -518,6 +518,60 @@ int tr_roadmap_reserve_search_state(tr_roadmap *rm, int64_t n_queries);
 int tr_roadmap_search_sweeps(tr_roadmap *rm, int64_t *n);
 int tr_roadmap_search_state_bytes(tr_roadmap *rm, int64_t *bytes);
 
+/* ---- tip-goal queries on a cached roadmap: roadmapIk + solveWithRoadmap for a batch ----------------------
+ * The reference's interactive loop (apps/roadmap_chained_plan.cpp:535-679) asks, per waypoint, roadmapIk(goal_tip, tol, k, opts)
+ * (motion-planning/VoxelCachedLazyPRM.cpp:3095-3577) and then solveWithRoadmap.  Here n requests go through both in one call, with
+ * the roadmap's tips, states and validity bytes resident in HBM.  For request q (tip r_q, start vertex s_q):
+ *   1. N_q = the first k vertices in the order (d2, vertex index) among the vertices that have a tip and are valid in the current
+ *      grid (exactly what tr_roadmap_revalidate reports; a vertex without a cache is invalid), d2 = ((tx-rx)^2 + (ty-ry)^2) +
+ *      (tz-rz)^2 in fp64 without contraction; a row with fewer than k is padded with -1; none: TR_TIPQ_NO_NEIGHBOR.  Vertex
+ *      validity learned on the way is kept in the roadmap, as tr_roadmap_solve keeps it.
+ *   2. IK from states[N_q[i]] to r_q for every i: ALL n k problems in one tr_ik_batch_dev (x_i, tip_i, err_i: tr_ik_batch's bits).
+ *   3. (ok_i, t_i) = checkMotion(states[N_q[i]], x_i, last_valid): tr_validate_edges_last_valid's bits.
+ *   4. TR_TIPQ_REACHED: the first i in neighbour order with err_i < tolerance and ok_i (:3214-3287) -> controls x_i, tip_i, err_i,
+ *      connection vertex N_q[i], t = 1.
+ *   5. TR_TIPQ_CLOSEST: otherwise g_i = interpolate(states[N_q[i]], x_i, t_i), its tip from tr_fk_tips, e_i = |tip(g_i) - r_q|;
+ *      the smallest e_i, the first winning a tie (:3445-3521) -> controls g_i, its tip, e_i, N_q[i], t_i.
+ *   6. (tr_roadmap_solve_tips) tr_roadmap_solve(s_q, connection vertex): status codes as there; the path is the vertex path
+ *      followed by the goal state (`controls`); cost = roadmap cost + state-space distance from the connection vertex to it.
+ * The result joins the roadmap through that ONE validated edge, as an RMAP_IK_AUTO_ADD result without ACCURATE does in the reference
+ * (:3242-3244, :3276-3287).  Deliberate difference: in the CLOSEST case the reference also connects the new vertex lazily to its
+ * connection-strategy neighbours (:3534), so its cost may be smaller.  RMAP_IK_ACCURATE, RMAP_IK_LAZY_ADD and persistent insertion
+ * into the graph are not offered; the graph is never edited. */
+/* Replaces vertexTipPositionProperty_ (filled by voxelizeVertex :2803-2837 or read from the file): tips n_vertices x 3 (NULL: computed
+ * once with tr_fk_tips_dev from the roadmap's states); present_bits (optional): a 0 bit = the vertex has no tip and is never a
+ * neighbour.  Uploads the tips and a copy of the states. */
+int tr_roadmap_set_tips(tr_roadmap *rm, const double *tips, const uint64_t *present_bits);
+/* Rule 1 alone -- replaces the nearest-neighbour structure over tips of roadmapIk (:3120-3160; the shim's full stable_sort per request):
+ * vertices n x k (-1 padded), dist2 (optional) n x k (+inf where padded).  Exact, brute force over the tip array (tip_knn). */
+int tr_roadmap_nearest_tips(tr_roadmap *rm, const double *requests, int64_t n, int32_t k, int32_t *vertices, double *dist2);
+int tr_roadmap_nearest_tips_dev(tr_roadmap *rm, const double *d_requests, int64_t n, int32_t k, int32_t *d_vertices, double *d_dist2);
+/* k <= 64; ik: the arguments roadmapIk hands to inverse_kinematics (the shim passes 100, 0.1, 1e-9, 1e-4, tolerance, 1e-6).
+ * A NULL tr_tip_query_params* means k = 5, tolerance = 1e-4 and those; a NULL tr_space_params* the defaults of Problem.h:59-62. */
+typedef struct {
+  int32_t k;
+  double tolerance;
+  tr_ik_params ik;
+} tr_tip_query_params;
+#define TR_TIPQ_REACHED     0
+#define TR_TIPQ_CLOSEST     1
+#define TR_TIPQ_NO_NEIGHBOR 2   /* no vertex to start from (roadmapIk returns nothing); outputs NaN, vertex -1 */
+/* Rules 1 - 5 -- replaces roadmapIk called once per request (:3095-3577).  Outputs (each may be NULL): controls n x S, tips n x 3,
+ * error n, neighbor_vertex n, outcome n (TR_TIPQ_*), last_valid_t n. */
+int tr_roadmap_ik_batch(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const double *requests, int64_t n,
+                        double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t);
+/* Rules 1 - 6 -- replaces the app's roadmapIk + solveWithRoadmap per waypoint (apps/roadmap_chained_plan.cpp:535-679).  status / cost /
+ * path_offsets / stats as tr_roadmap_solve; a request without a neighbour ends TR_QUERY_INVALID_GOAL.  The vertex paths come through
+ * tr_roadmap_fetch_paths as after tr_roadmap_solve; the goal state that follows the last vertex is in `controls`. */
+int tr_roadmap_solve_tips(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const int32_t *starts,
+                          const double *requests, int64_t n, int32_t n_threads, double *controls, double *tips, double *error,
+                          int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t, int32_t *status, double *cost,
+                          int64_t *path_offsets, tr_roadmap_stats *stats);
+/* Host wall time of the phases of the last tr_roadmap_ik_batch / tr_roadmap_solve_tips in milliseconds (instrumentation): out[0] nearest
+ * (validity + tip_knn + gather), out[1] IK, out[2] edges, out[3] select (interpolation, FK, choice, results), out[4] solve;
+ * out[5] = rounds of the IK batch. */
+int tr_roadmap_tip_query_profile(tr_roadmap *rm, double out[6]);
+
 /* The connection loop itself (motion-planning/VoxelCachedLazyPRM.cpp:1491-1502: for every vertex v and every neighbour n
  * of connectionStrategy_(v), `if (!getEdge(v, n)) connectVertices(v, n)`): the undirected edge set of the k-nearest
  * table -- pairs (lo, hi), lo < hi, each once, ordered by (lo, hi) -- built on the device (sort + unique of the pair

@@ -1005,6 +1005,54 @@ class VoxelCachedLazyPRM {
     return result(best, x, {tips[3 * best], tips[3 * best + 1], tips[3 * best + 2]}, std::sqrt(tip_dist2(&tips[3 * best])));
   }
 
+  // ---- roadmapIk + solveWithRoadmap for a batch of tip requests (tr_roadmap_ik_batch / tr_roadmap_solve_tips) ----
+  enum TipOutcome { TIP_REACHED = TR_TIPQ_REACHED, TIP_CLOSEST = TR_TIPQ_CLOSEST, TIP_NO_NEIGHBOR = TR_TIPQ_NO_NEIGHBOR };
+  struct TipResults {
+    std::vector<double> controls;          // n x state size: the goal states (NaN where the outcome is TIP_NO_NEIGHBOR)
+    std::vector<double> tip_positions;     // n x 3
+    std::vector<double> error;             // |tip_position - request|
+    std::vector<int32_t> neighbor_vertex;  // the vertex IK started from = where the goal state joins the roadmap (-1: none)
+    std::vector<int32_t> outcome;          // TipOutcome
+    std::vector<double> last_valid_t;      // 1 when reached, else where checkMotion(neighbor, solution) stopped
+  };
+  struct TipSolution { TipResults ik; Solution roadmap; };   // roadmap.paths[q]: start ... connection vertex; ik.controls follows it
+  /// roadmapIk for every request in ONE call (the rule in include/tendon_hip.h: what RMAP_IK_AUTO_ADD without ACCURATE finds, with
+  /// nothing added to the graph): IK from the k vertices with the nearest tips, all n k problems in one device batch; per request the
+  /// first solution in neighbour order within tolerance whose edge from its neighbour is valid, else the last valid state towards the
+  /// solutions whose tip is nearest the request.
+  TipResults roadmapIkBatch(const std::vector<std::array<double, 3>> &requests, double tolerance = 1e-4, size_t k = 5) {
+    need_validators("roadmapIkBatch");
+    sync_tips();
+    const size_t n = requests.size();
+    TipResults r = tip_results(n);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    rcheck(tr_roadmap_ik_batch(rm_, &mv_->space, &prm, n ? requests[0].data() : nullptr, (int64_t)n, r.controls.data(), r.tip_positions.data(),
+                               r.error.data(), r.neighbor_vertex.data(), r.outcome.data(), r.last_valid_t.data()));
+    return r;
+  }
+  /// ... followed by solveWithRoadmap from starts[q] to request q's connection vertex; cost = roadmap cost + distance(connection
+  /// vertex, goal state).  A request without a neighbour ends TR_QUERY_INVALID_GOAL.
+  TipSolution solveToTips(const std::vector<int32_t> &starts, const std::vector<std::array<double, 3>> &requests, double tolerance = 1e-4,
+                          size_t k = 5, int n_threads = 0) {
+    if (starts.size() != requests.size()) throw std::invalid_argument("starts and requests differ in length");
+    need_validators("solveToTips");
+    sync_tips();
+    const size_t n = requests.size();
+    TipSolution s;
+    s.ik = tip_results(n);
+    s.roadmap.status.resize(n); s.roadmap.cost.resize(n);
+    std::vector<int64_t> off(n + 1, 0);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    rcheck(tr_roadmap_solve_tips(rm_, &mv_->space, &prm, starts.data(), n ? requests[0].data() : nullptr, (int64_t)n, n_threads, s.ik.controls.data(),
+                                 s.ik.tip_positions.data(), s.ik.error.data(), s.ik.neighbor_vertex.data(), s.ik.outcome.data(),
+                                 s.ik.last_valid_t.data(), s.roadmap.status.data(), s.roadmap.cost.data(), off.data(), &s.roadmap.stats));
+    std::vector<int32_t> pv((size_t)off[n]);
+    rcheck(tr_roadmap_fetch_paths(rm_, pv.data(), (int64_t)pv.size()));
+    s.roadmap.paths.resize(n);
+    for (size_t q = 0; q < n; q++) s.roadmap.paths[q].assign(pv.begin() + off[q], pv.begin() + off[q + 1]);
+    return s;
+  }
+
   int64_t releaseSearchState() { int64_t b = 0; if (rm_) rcheck(tr_roadmap_release_search_state(rm_, &b)); return b; }
   /// CompoundStateSpace::distance with the weights of Problem.cpp:112-152 (the edge cost connectVertices stores, :2857-2861)
   double distance(const double *a, const double *b) const {
@@ -1031,6 +1079,28 @@ class VoxelCachedLazyPRM {
   void need_validators(const char *what) const {
     if (!mv_) throw std::runtime_error(std::string(what) + ": missing voxel motion validator");      // the reference's setup_ == false (:1286-1298)
   }
+  TipResults tip_results(size_t n) const {
+    TipResults r;
+    r.controls.resize(n * S_); r.tip_positions.resize(n * 3); r.error.resize(n); r.neighbor_vertex.resize(n); r.outcome.resize(n); r.last_valid_t.resize(n);
+    return r;
+  }
+  static tr_tip_query_params tip_params(double tolerance, size_t k) {
+    return tr_tip_query_params{(int32_t)k, tolerance, tr_ik_params{100, 0.1, 1e-9, 1e-4, tolerance, 1e-6}};   // what roadmapIk hands to IK
+  }
+  /// the device image and, once per image, the vertices' tips (tipPositionProperty_; a vertex without one is no neighbour)
+  void sync_tips() {
+    sync();
+    if (tips_synced_) return;
+    std::vector<bool> has(milestoneCount());
+    std::vector<double> t(tips_);
+    for (size_t v = 0; v < milestoneCount(); v++) {
+      has[v] = has_tip_[v] != 0;
+      if (!has[v]) t[3 * v] = t[3 * v + 1] = t[3 * v + 2] = 0.0;
+    }
+    const auto bits = detail::pack(has);
+    rcheck(tr_roadmap_set_tips(rm_, t.data(), bits.data()));
+    tips_synced_ = true;
+  }
   void create_device_graph() {
     tr_roadmap_destroy(rm_); rm_ = nullptr;
     const int st = tr_roadmap_create(vc_.context(), states_.data(), (int64_t)milestoneCount(), edges_.data(),
@@ -1038,6 +1108,7 @@ class VoxelCachedLazyPRM {
     if (st == TR_ERR_OUT_OF_RANGE) throw std::out_of_range("edge refers to a state outside the roadmap");
     if (st != TR_OK) throw std::invalid_argument("tr_roadmap_create failed");
     dirty_ = false;
+    tips_synced_ = false;
   }
   /// validity the query loop discovered since the last edit comes back into this object
   void absorb() {
@@ -1158,6 +1229,7 @@ class VoxelCachedLazyPRM {
   BuildReport report_;
   tr_roadmap *rm_ = nullptr;
   bool dirty_ = true;
+  bool tips_synced_ = false;
 };
 
 }  // namespace motion_planning

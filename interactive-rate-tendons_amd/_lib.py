@@ -37,6 +37,8 @@ ABI_SYMBOLS = (
     "tr_candidate_states", "tr_candidate_states_dev", "tr_validate_candidates_dev", "tr_compact_rows_dev",
     "tr_sample_valid_vertices", "tr_sample_valid_vertices_dev", "tr_sample_valid_vertices_sig_dev",
     "tr_fk_tips", "tr_fk_tips_dev", "tr_tip_jacobian", "tr_tip_jacobian_dev", "tr_ik_batch", "tr_ik_batch_dev",
+    "tr_roadmap_set_tips", "tr_roadmap_nearest_tips", "tr_roadmap_nearest_tips_dev", "tr_roadmap_ik_batch", "tr_roadmap_solve_tips",
+    "tr_roadmap_tip_query_profile",
 )
 
 
@@ -64,11 +66,16 @@ class TrIkParams(C.Structure):
                 ("stop_threshold_Dp", C.c_double), ("stop_threshold_err", C.c_double), ("finite_difference_delta", C.c_double)]
 
 
+class TrTipQueryParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("tolerance", C.c_double), ("ik", TrIkParams)]
+
+
 class TrRoadmapStats(C.Structure):
     _fields_ = [("rounds", C.c_int64), ("items_checked", C.c_int64), ("astar_runs", C.c_int64), ("expanded", C.c_int64)]
 
 
 TR_QUERY_SOLVED, TR_QUERY_NO_PATH, TR_QUERY_INVALID_START, TR_QUERY_INVALID_GOAL = range(4)
+TR_TIPQ_REACHED, TR_TIPQ_CLOSEST, TR_TIPQ_NO_NEIGHBOR = range(3)
 
 
 class TendonHipError(RuntimeError):
@@ -118,7 +125,7 @@ def _units():
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
-                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc"]
+                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp"]
     fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
     u = [("tendon_hip.o", "tendon_hip.hip", [], main_deps + [HEADER]),
@@ -325,6 +332,14 @@ def lib():
     L.tr_tip_jacobian_dev.argtypes = [vp, vp, i64, C.c_double, vp, vp, vp]
     L.tr_ik_batch.argtypes = [vp, P(TrIkParams), dp, i64, dp, i64, dp, dp, dp, dp, dp, i32p, i32p, P(i64)]
     L.tr_ik_batch_dev.argtypes = [vp, P(TrIkParams), vp, i64, vp, i64, dp, dp, vp, vp, vp, vp, vp, P(i64), vp]
+    tqp = P(TrTipQueryParams)
+    L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
+    L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]
+    L.tr_roadmap_nearest_tips_dev.argtypes = [vp, vp, i64, C.c_int32, vp, vp]
+    L.tr_roadmap_ik_batch.argtypes = [vp, P(TrSpaceParams), tqp, dp, i64, dp, dp, dp, i32p, i32p, dp]
+    L.tr_roadmap_solve_tips.argtypes = [vp, P(TrSpaceParams), tqp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, dp, i32p, dp, P(i64),
+                                        P(TrRoadmapStats)]
+    L.tr_roadmap_tip_query_profile.argtypes = [vp, dp]
     L.tr_profile_begin.argtypes = [vp]
     L.tr_profile_read.argtypes = [vp, P(i64), dp]
     L.tr_profile_end.argtypes = [vp]

@@ -51,6 +51,7 @@
 
 #include "../../include/tendon_hip.h"
 #include "roadmap_kernel.hpp"
+#include "tipq_kernel.hpp"
 #include "handback_feed.hpp"
 
 namespace {
@@ -199,6 +200,20 @@ struct tr_roadmap {
     std::vector<int32_t> label;          // per vertex: the smallest vertex of its component
     int64_t st_cut = 0;                  // searches of the last solve answered by the labels alone
   } dc;
+  // tip-goal queries (tr_roadmap_set_tips .. tr_roadmap_solve_tips; roadmap_tips_host.inc): the tips, a copy of the states and the
+  // validity bytes in HBM for the life of the roadmap, and one grow-only arena for the arrays of a call
+  struct DevTips {
+    bool set = false;
+    double *d_tips = nullptr, *d_states = nullptr;
+    uint8_t *d_vstat = nullptr;          // the image of `vstat` the kernel filters by; sent again only when `vstat` differs from `vstat_sent`
+    uint64_t *d_present = nullptr;       // bit v: vertex v has a tip
+    std::vector<uint8_t> vstat_sent;
+    std::vector<uint64_t> present;
+    char *arena = nullptr;
+    size_t arena_bytes = 0;
+    double phase_ms[5] = {0, 0, 0, 0, 0};   // of the last call: nearest, IK, edges, select, solve
+    int64_t st_ik_rounds = 0;
+  } dt;
 };
 
 namespace {
@@ -240,6 +255,7 @@ void free_dev(tr_roadmap *r) {
 #include "roadmap_components_host.inc"
 #include "roadmap_search_host.inc"
 #include "roadmap_solve_host.inc"
+#include "roadmap_tips_host.inc"
 
 extern "C" {
 
@@ -328,6 +344,7 @@ void tr_roadmap_destroy(tr_roadmap *r) {
   free_dev(r);
   free_search(r);
   free_comp(r);
+  free_tips(r);
   delete r;
 }
 
@@ -437,21 +454,7 @@ int tr_roadmap_solve(tr_roadmap *r, const int32_t *starts, const int32_t *goals,
                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats) {
   if (!r) return TR_ERR_INVALID_ARG;
   RmLock lock_(r);
-  if (n_queries < 0 || (n_queries > 0 && (!starts || !goals || !status || !path_offsets))) return rfail(r, TR_ERR_INVALID_ARG, "bad argument");
-  reset_last_solve(r, n_queries);
-  if (path_offsets) path_offsets[0] = 0;
-  if (n_queries == 0) { if (stats) *stats = tr_roadmap_stats{0, 0, 0, 0}; return TR_OK; }
-  for (int64_t q = 0; q < n_queries; q++)
-    if (starts[q] < 0 || starts[q] >= r->V || goals[q] < 0 || goals[q] >= r->V) return rfail(r, TR_ERR_OUT_OF_RANGE, "query vertex outside the roadmap");
-  RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
-  const RoadmapSwitches sw = read_switches();
-  Laps laps(sw, "tr_roadmap_solve");
-  const int T = host_threads(n_threads);
-  if ((int)r->scratch.size() < T) r->scratch.resize((size_t)T);
-  for (Scratch &sc : r->scratch) sc.trace = sw.hist_path != nullptr;
-  if (r->lm_n < 0 && n_queries >= 64) build_landmarks(r, 16, T, sw);         // a handful of queries does not repay 16 graph sweeps
-  Solve solve(r, starts, goals, n_queries, status, cost, sw, T);
-  return solve.run(laps, path_offsets, stats);
+  return solve_locked(r, starts, goals, n_queries, n_threads, status, cost, path_offsets, stats);
 }
 
 int tr_roadmap_search_stats(tr_roadmap *r, int64_t out[8]) {

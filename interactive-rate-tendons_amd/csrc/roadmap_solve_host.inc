@@ -514,4 +514,24 @@ void reset_last_solve(tr_roadmap *r, int64_t n_queries) {
   r->dc.st_cut = 0;
 }
 
+// tr_roadmap_solve behind the lock (tr_roadmap_solve_tips runs the same call on the connection vertices its IK step chose)
+int solve_locked(tr_roadmap *r, const int32_t *starts, const int32_t *goals, int64_t n_queries, int32_t n_threads,
+                 int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats) {
+  if (n_queries < 0 || (n_queries > 0 && (!starts || !goals || !status || !path_offsets))) return rfail(r, TR_ERR_INVALID_ARG, "bad argument");
+  reset_last_solve(r, n_queries);
+  if (path_offsets) path_offsets[0] = 0;
+  if (n_queries == 0) { if (stats) *stats = tr_roadmap_stats{0, 0, 0, 0}; return TR_OK; }
+  for (int64_t q = 0; q < n_queries; q++)
+    if (starts[q] < 0 || starts[q] >= r->V || goals[q] < 0 || goals[q] >= r->V) return rfail(r, TR_ERR_OUT_OF_RANGE, "query vertex outside the roadmap");
+  RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
+  const RoadmapSwitches sw = read_switches();
+  Laps laps(sw, "tr_roadmap_solve");
+  const int T = host_threads(n_threads);
+  if ((int)r->scratch.size() < T) r->scratch.resize((size_t)T);
+  for (Scratch &sc : r->scratch) sc.trace = sw.hist_path != nullptr;
+  if (r->lm_n < 0 && n_queries >= 64) build_landmarks(r, 16, T, sw);         // a handful of queries does not repay 16 graph sweeps
+  Solve solve(r, starts, goals, n_queries, status, cost, sw, T);
+  return solve.run(laps, path_offsets, stats);
+}
+
 }  // namespace

@@ -1,0 +1,361 @@
+// roadmap_tips_host.inc -- part of roadmap.hip: batched tip-goal queries.  The reference's interactive loop
+// (apps/roadmap_chained_plan.cpp:535-679) asks per waypoint roadmapIk(goal_tip, tol, k, opts)
+// (motion-planning/VoxelCachedLazyPRM.cpp:3095-3577) and then solveWithRoadmap; here a batch of requests goes through
+//   tip_knn (the k nearest tips among the valid vertices) -> tipq_gather -> ONE tr_ik_batch_dev of Q k problems ->
+//   checkMotion(states[N], x, last_valid) on all of them -> tipq_interp + tr_fk_tips_dev -> tipq_select -> tr_roadmap_solve
+// with the roadmap's tips, states and validity bytes resident in HBM: nothing V-sized moves per call (the validity bytes are
+// sent again only after they changed on the host).  A result joins the roadmap through exactly one edge, to the neighbour IK
+// started from (:3242-3244, :3276-3287); the graph itself is not edited.
+namespace {
+
+void free_tips(tr_roadmap *r) {
+  auto &d = r->dt;
+  void *p[] = {d.d_tips, d.d_states, d.d_vstat, d.d_present, d.arena};
+  for (void *q : p) if (q) dev_cache().release(q);
+  d = tr_roadmap::DevTips{};
+}
+
+// Vertex validity the nearest-tips filter needs: while a vertex is still unknown, every vertex's cached set is tested against the
+// current grid in one K4 launch (the vertex part of tr_roadmap_revalidate: same kernel, same rule -- a hit or a missing cache is
+// invalid) and the unknown ones become known; known ones keep what they have.  Then the device image follows `vstat`.
+int tips_validity(tr_roadmap *r) {
+  auto &d = r->dt;
+  const int64_t V = r->V;
+  bool unknown = false;
+  for (int64_t v = 0; v < V && !unknown; v++) unknown = r->vstat[(size_t)v] == V_UNKNOWN;
+  if (unknown) {
+    if (!r->has_caches) return rfail(r, TR_ERR_INVALID_ARG, "vertices of unknown validity and no voxel caches attached (tr_roadmap_set_caches)");
+    const int rc = tr_check_cached_dev(r->ctx, r->d_ids, r->d_masks, r->d_off, V, r->d_bits, nullptr);
+    if (rc) return rfail(r, rc, tr_last_error(r->ctx));
+    const size_t nw = (size_t)(V + 63) / 64;
+    RM_HIP(r, hipMemcpyAsync(r->h_bits, r->d_bits, nw * sizeof(uint64_t), hipMemcpyDeviceToHost, nullptr));
+    RM_HIP(r, hipStreamSynchronize(nullptr));
+    for (int64_t v = 0; v < V; v++) {
+      if (r->vstat[(size_t)v] != V_UNKNOWN) continue;
+      const bool bad = ((r->h_bits[(size_t)v >> 6] | r->absent[(size_t)v >> 6]) >> (v & 63)) & 1;
+      r->vstat[(size_t)v] = bad ? V_INVALID : V_VALID;
+    }
+  }
+  if (d.vstat_sent != r->vstat) {
+    RM_HIP(r, hipMemcpy(d.d_vstat, r->vstat.data(), (size_t)V, hipMemcpyHostToDevice));
+    d.vstat_sent = r->vstat;
+  }
+  return TR_OK;
+}
+
+// the arena of one call, carved in order
+struct TipArena {
+  char *base = nullptr;
+  size_t used = 0;
+  template <class T> T *take(size_t n) { T *p = (T *)(base ? base + used : nullptr); used += up(std::max<size_t>(n, 1) * sizeof(T)); return p; }
+};
+
+struct TipBuffers {
+  double *req, *d2, *part_d2, *starts, *goals, *x, *xtip, *err, *t, *g, *gtip, *o_controls, *o_tip, *o_err, *o_t;
+  int32_t *nbr, *part_idx, *o_nbr, *o_outcome;
+  uint8_t *ok;
+  void carve(TipArena &a, int64_t n, int k, int S, int slices, bool full) {
+    const size_t m = (size_t)n * (size_t)k;
+    req = a.take<double>((size_t)n * 3); nbr = a.take<int32_t>(m); d2 = a.take<double>(m);
+    part_idx = a.take<int32_t>(slices > 1 ? m * (size_t)slices : 1); part_d2 = a.take<double>(slices > 1 ? m * (size_t)slices : 1);
+    if (!full) return;
+    starts = a.take<double>(m * S); goals = a.take<double>(m * 3); x = a.take<double>(m * S); xtip = a.take<double>(m * 3);
+    err = a.take<double>(m); t = a.take<double>(m); ok = a.take<uint8_t>(m); g = a.take<double>(m * S); gtip = a.take<double>(m * 3);
+    o_controls = a.take<double>((size_t)n * S); o_tip = a.take<double>((size_t)n * 3); o_err = a.take<double>((size_t)n);
+    o_t = a.take<double>((size_t)n); o_nbr = a.take<int32_t>((size_t)n); o_outcome = a.take<int32_t>((size_t)n);
+  }
+};
+
+constexpr int kTipQ = 4, kTipG = 4;     // requests per wave, tiles in flight (tip_knn)
+
+// Slices of the tip array: a batch that fills the device with request groups streams it whole; a handful of requests cuts it so
+// that ~1024 waves share the work (one wave alone would take V / 256 dependent rounds of loads).
+int tip_slices(int64_t n, int64_t V) {
+  const int64_t groups = (n + kTipQ - 1) / kTipQ, tiles = (V + 63) / 64;
+  const int64_t by_work = std::max<int64_t>(1, tiles / (2 * kTipG));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, by_work), 1024 / groups));
+}
+
+int tip_buffers(tr_roadmap *r, int64_t n, int k, bool full, TipBuffers &b, int &slices) {
+  auto &d = r->dt;
+  slices = tip_slices(n, r->V);
+  TipArena size;
+  TipBuffers dummy;
+  dummy.carve(size, n, k, r->S, slices, full);
+  if (size.used > d.arena_bytes) {
+    if (d.arena) dev_cache().release(d.arena);
+    d.arena = nullptr; d.arena_bytes = 0;
+    const size_t want = size.used + size.used / 2;
+    RM_HIP(r, dev_cache().alloc(tr_device(r->ctx), (void **)&d.arena, want));
+    d.arena_bytes = want;
+  }
+  TipArena a;
+  a.base = d.arena;
+  b.carve(a, n, k, r->S, slices, full);
+  return TR_OK;
+}
+
+// tip_knn (+ tip_knn_merge) on the null stream: d_req n x 3 -> d_nbr n x k, d_d2 n x k (may be null)
+int launch_nearest(tr_roadmap *r, const double *d_req, int64_t n, int k, int slices, const TipBuffers &b, int32_t *d_nbr, double *d_d2) {
+  auto &d = r->dt;
+  const int64_t groups = (n + kTipQ - 1) / kTipQ;
+  const dim3 grid((unsigned)((groups + 3) / 4), (unsigned)slices);
+  if (slices == 1) {
+    hipLaunchKernelGGL((trk::tip_knn<kTipQ, kTipG>), grid, dim3(256), 0, nullptr, (const double *)d.d_tips, (const uint8_t *)d.d_vstat,
+                       (const uint64_t *)d.d_present, r->V, d_req, n, k, d_nbr, d_d2);
+    RM_HIP(r, hipGetLastError());
+    return TR_OK;
+  }
+  hipLaunchKernelGGL((trk::tip_knn<kTipQ, kTipG>), grid, dim3(256), 0, nullptr, (const double *)d.d_tips, (const uint8_t *)d.d_vstat,
+                     (const uint64_t *)d.d_present, r->V, d_req, n, k, b.part_idx, b.part_d2);
+  RM_HIP(r, hipGetLastError());
+  hipLaunchKernelGGL(trk::tip_knn_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, nullptr, (const int32_t *)b.part_idx,
+                     (const double *)b.part_d2, n, slices, k, d_nbr, d_d2);
+  RM_HIP(r, hipGetLastError());
+  return TR_OK;
+}
+
+int tips_ready(tr_roadmap *r, int64_t n, int32_t k) {
+  if (!r->dt.set) return rfail(r, TR_ERR_INVALID_ARG, "the roadmap has no tips (tr_roadmap_set_tips)");
+  if (n < 0 || k < 1 || k > TRK_TIPQ_MAX_K) return rfail(r, TR_ERR_INVALID_ARG, "bad argument (k: 1 .. 64)");
+  if (n * (int64_t)k > ((int64_t)1 << 28)) return rfail(r, TR_ERR_INVALID_ARG, "too many candidates in one call (n k <= 2^28)");
+  RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
+  return TR_OK;
+}
+
+static_assert(TRK_TIPQ_REACHED == TR_TIPQ_REACHED && TRK_TIPQ_CLOSEST == TR_TIPQ_CLOSEST && TRK_TIPQ_NO_NEIGHBOR == TR_TIPQ_NO_NEIGHBOR, "outcome codes");
+
+// tr_fk_tips_dev on the null stream, a K1 launch per 2^18 states (a state's tip does not depend on the launch it is in)
+int fk_tips_chunked(tr_roadmap *r, const double *d_states, int64_t n, double *d_tips) {
+  const int64_t chunk = (int64_t)1 << 18;
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int rc = tr_fk_tips_dev(r->ctx, d_states + off * r->S, std::min(chunk, n - off), d_tips + off * 3, nullptr, nullptr);
+    if (rc) return rfail(r, rc, tr_last_error(r->ctx));
+  }
+  return TR_OK;
+}
+
+unsigned tipq_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Rules 1 - 5 behind the lock; every output may be null.
+int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const double *requests, int64_t n,
+                     double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t) {
+  const tr_tip_query_params def{5, 1e-4, tr_ik_params{100, 0.1, 1e-9, 1e-4, 1e-4, 1e-6}};      // roadmapIk's defaults and what it hands to IK
+  const tr_tip_query_params &p = params ? *params : def;
+  const tr_space_params spd{0.02, 0.01, 0.0001};                                                // Problem.h:59-62
+  const tr_space_params &space = sp ? *sp : spd;
+  int rc;
+  if ((rc = tips_ready(r, n, p.k))) return rc;
+  auto &d = r->dt;
+  for (double &x : d.phase_ms) x = 0;
+  d.st_ik_rounds = 0;
+  if (n == 0) return TR_OK;
+  if (!requests) return rfail(r, TR_ERR_INVALID_ARG, "null requests");
+  if (!(p.tolerance >= 0)) return rfail(r, TR_ERR_INVALID_ARG, "tolerance must be >= 0");
+  const int k = p.k, S = r->S;
+  const int64_t m = n * k;
+  auto t0 = Clock::now();
+  auto lap = [&](int phase) { const auto t1 = Clock::now(); d.phase_ms[phase] += ms_between(t0, t1); t0 = t1; };
+  // 1. neighbours
+  if ((rc = tips_validity(r))) return rc;
+  TipBuffers b;
+  int slices = 1;
+  if ((rc = tip_buffers(r, n, k, true, b, slices))) return rc;
+  RM_HIP(r, hipMemcpyAsync(b.req, requests, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, nullptr));
+  if ((rc = launch_nearest(r, b.req, n, k, slices, b, b.nbr, nullptr))) return rc;
+  // 2. IK from every neighbour, one batch
+  hipLaunchKernelGGL(trk::tipq_gather, dim3(tipq_grid(m)), dim3(256), 0, nullptr, (const double *)d.d_states, S, (const int32_t *)b.nbr,
+                     (const double *)b.req, n, k, b.starts, b.goals);
+  RM_HIP(r, hipGetLastError());
+  std::vector<int32_t> nbr((size_t)m);
+  RM_HIP(r, hipMemcpy(nbr.data(), b.nbr, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));     // (synchronises: the nearest phase ends here)
+  lap(0);
+  if ((rc = tr_ik_batch_dev(r->ctx, &p.ik, b.starts, m, b.goals, 3, nullptr, nullptr, b.x, b.xtip, b.err, nullptr, nullptr, &d.st_ik_rounds, nullptr)))
+    return rfail(r, rc, tr_last_error(r->ctx));
+  // 3. partial edges: checkMotion(states[N], x, last_valid) on the slots that hold a neighbour (host-array form: Q k S doubles each way)
+  std::vector<double> x((size_t)m * S);
+  RM_HIP(r, hipMemcpy(x.data(), b.x, x.size() * sizeof(double), hipMemcpyDeviceToHost));
+  lap(1);
+  std::vector<int64_t> live;
+  live.reserve((size_t)m);
+  for (int64_t s = 0; s < m; s++) if (nbr[(size_t)s] >= 0) live.push_back(s);
+  const int64_t ml = (int64_t)live.size();
+  std::vector<uint8_t> ok((size_t)m, 0);
+  std::vector<double> t((size_t)m, 0.0);
+  if (ml > 0) {
+    std::vector<double> ea((size_t)ml * S), eb((size_t)ml * S), et((size_t)ml);
+    std::vector<uint64_t> bits((size_t)(ml + 63) / 64, 0);
+    for (int64_t i = 0; i < ml; i++) {
+      std::memcpy(&ea[(size_t)i * S], &r->states[(size_t)nbr[(size_t)live[(size_t)i]] * S], (size_t)S * sizeof(double));
+      std::memcpy(&eb[(size_t)i * S], &x[(size_t)live[(size_t)i] * S], (size_t)S * sizeof(double));
+    }
+    if ((rc = tr_validate_edges_last_valid(r->ctx, &space, ea.data(), eb.data(), ml, bits.data(), et.data(), nullptr))) return rfail(r, rc, tr_last_error(r->ctx));
+    for (int64_t i = 0; i < ml; i++) {
+      ok[(size_t)live[(size_t)i]] = (uint8_t)((bits[(size_t)i >> 6] >> (i & 63)) & 1);
+      t[(size_t)live[(size_t)i]] = et[(size_t)i];
+    }
+  }
+  RM_HIP(r, hipMemcpyAsync(b.ok, ok.data(), (size_t)m, hipMemcpyHostToDevice, nullptr));
+  RM_HIP(r, hipMemcpyAsync(b.t, t.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, nullptr));
+  lap(2);
+  // 4 - 5. the last valid state of every candidate, its tip, and the choice
+  hipLaunchKernelGGL(trk::tipq_interp, dim3(tipq_grid(m)), dim3(256), 0, nullptr, (const double *)b.starts, (const double *)b.x, (const double *)b.t, m, S,
+                     r->rot ? r->NT : -1, b.g);
+  RM_HIP(r, hipGetLastError());
+  if ((rc = fk_tips_chunked(r, b.g, m, b.gtip))) return rc;
+  hipLaunchKernelGGL(trk::tipq_select, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, S, p.tolerance,
+                     (const double *)b.x, (const double *)b.xtip, (const double *)b.err, (const uint8_t *)b.ok, (const double *)b.t, (const double *)b.g,
+                     (const double *)b.gtip, b.o_controls, b.o_tip, b.o_err, b.o_nbr, b.o_outcome, b.o_t);
+  RM_HIP(r, hipGetLastError());
+  if (controls) RM_HIP(r, hipMemcpyAsync(controls, b.o_controls, (size_t)n * S * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  if (tips) RM_HIP(r, hipMemcpyAsync(tips, b.o_tip, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  if (error) RM_HIP(r, hipMemcpyAsync(error, b.o_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  if (neighbor_vertex) RM_HIP(r, hipMemcpyAsync(neighbor_vertex, b.o_nbr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (outcome) RM_HIP(r, hipMemcpyAsync(outcome, b.o_outcome, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (last_valid_t) RM_HIP(r, hipMemcpyAsync(last_valid_t, b.o_t, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  RM_HIP(r, hipStreamSynchronize(nullptr));
+  lap(3);
+  return TR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *present_bits) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
+  free_tips(r);
+  auto &d = r->dt;
+  const int64_t V = r->V;
+  const int dev = tr_device(r->ctx);
+  const size_t nw = (size_t)V / 64 + 1;
+  RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_tips, std::max<size_t>(1, (size_t)V * 3) * sizeof(double)));
+  RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_states, std::max<size_t>(1, (size_t)V * r->S) * sizeof(double)));
+  RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_vstat, std::max<size_t>(1, (size_t)V)));
+  RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_present, nw * sizeof(uint64_t)));
+  d.present.assign(nw, 0);
+  for (int64_t v = 0; v < V; v++)
+    if (!present_bits || ((present_bits[v >> 6] >> (v & 63)) & 1)) d.present[(size_t)v >> 6] |= (uint64_t)1 << (v & 63);
+  if (V > 0) {
+    RM_HIP(r, hipMemcpy(d.d_states, r->states.data(), (size_t)V * r->S * sizeof(double), hipMemcpyHostToDevice));
+    if (tips) {
+      RM_HIP(r, hipMemcpy(d.d_tips, tips, (size_t)V * 3 * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+      // fk_shape(state).p.back() of every vertex, once (voxelizeVertex stores it: vertexTipPositionProperty_, :2803-2837)
+      if (const int rc = fk_tips_chunked(r, d.d_states, V, d.d_tips)) return rc;
+      RM_HIP(r, hipStreamSynchronize(nullptr));
+    }
+  }
+  RM_HIP(r, hipMemcpy(d.d_present, d.present.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+  d.vstat_sent.clear();                                     // (differs from `vstat` unless the roadmap is empty: the first call sends it)
+  d.set = true;
+  return TR_OK;
+}
+
+int tr_roadmap_nearest_tips_dev(tr_roadmap *r, const double *d_requests, int64_t n, int32_t k, int32_t *d_vertices, double *d_dist2) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  int rc;
+  if ((rc = tips_ready(r, n, k))) return rc;
+  if (n == 0) return TR_OK;
+  if (!d_requests || !d_vertices) return rfail(r, TR_ERR_INVALID_ARG, "null device pointer");
+  RM_HIP(r, hipDeviceSynchronize());                        // (the requests may have been written on any stream)
+  if ((rc = tips_validity(r))) return rc;
+  TipBuffers b;
+  int slices = 1;
+  if ((rc = tip_buffers(r, n, k, false, b, slices))) return rc;
+  if ((rc = launch_nearest(r, d_requests, n, k, slices, b, d_vertices, d_dist2))) return rc;
+  RM_HIP(r, hipStreamSynchronize(nullptr));
+  return TR_OK;
+}
+
+int tr_roadmap_nearest_tips(tr_roadmap *r, const double *requests, int64_t n, int32_t k, int32_t *vertices, double *dist2) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  int rc;
+  if ((rc = tips_ready(r, n, k))) return rc;
+  if (n == 0) return TR_OK;
+  if (!requests || !vertices) return rfail(r, TR_ERR_INVALID_ARG, "null argument");
+  if ((rc = tips_validity(r))) return rc;
+  TipBuffers b;
+  int slices = 1;
+  if ((rc = tip_buffers(r, n, k, false, b, slices))) return rc;
+  RM_HIP(r, hipMemcpyAsync(b.req, requests, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, nullptr));
+  if ((rc = launch_nearest(r, b.req, n, k, slices, b, b.nbr, b.d2))) return rc;
+  RM_HIP(r, hipMemcpyAsync(vertices, b.nbr, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (dist2) RM_HIP(r, hipMemcpyAsync(dist2, b.d2, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  RM_HIP(r, hipStreamSynchronize(nullptr));
+  return TR_OK;
+}
+
+int tr_roadmap_ik_batch(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const double *requests, int64_t n,
+                        double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  return tip_query_locked(r, sp, params, requests, n, controls, tips, error, neighbor_vertex, outcome, last_valid_t);
+}
+
+int tr_roadmap_solve_tips(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const int32_t *starts,
+                          const double *requests, int64_t n, int32_t n_threads, double *controls, double *tips, double *error,
+                          int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t, int32_t *status, double *cost,
+                          int64_t *path_offsets, tr_roadmap_stats *stats) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  if (n < 0 || (n > 0 && (!starts || !requests || !status || !path_offsets))) return rfail(r, TR_ERR_INVALID_ARG, "bad argument");
+  reset_last_solve(r, n);
+  if (path_offsets) path_offsets[0] = 0;
+  if (stats) *stats = tr_roadmap_stats{0, 0, 0, 0};
+  for (int64_t q = 0; q < n; q++)
+    if (starts[q] < 0 || starts[q] >= r->V) return rfail(r, TR_ERR_OUT_OF_RANGE, "query vertex outside the roadmap");
+  // rules 1 - 5 (the solve below needs the connection vertices and the goal states whether or not the caller asked for them)
+  std::vector<double> own_controls;
+  std::vector<int32_t> own_nbr, own_outcome;
+  if (!controls) { own_controls.resize((size_t)n * r->S); controls = own_controls.data(); }
+  if (!neighbor_vertex) { own_nbr.resize((size_t)n); neighbor_vertex = own_nbr.data(); }
+  if (!outcome) { own_outcome.resize((size_t)n); outcome = own_outcome.data(); }
+  int rc;
+  if ((rc = tip_query_locked(r, sp, params, requests, n, controls, tips, error, neighbor_vertex, outcome, last_valid_t))) return rc;
+  if (n == 0) return TR_OK;
+  // rule 6: the roadmap query to the connection vertex; a request without a neighbour has no goal
+  const auto t0 = Clock::now();
+  std::vector<int64_t> live;
+  std::vector<int32_t> s2, g2;
+  for (int64_t q = 0; q < n; q++)
+    if (outcome[q] != TR_TIPQ_NO_NEIGHBOR) { live.push_back(q); s2.push_back(starts[q]); g2.push_back(neighbor_vertex[q]); }
+  const int64_t nl = (int64_t)live.size();
+  std::vector<int32_t> st2((size_t)nl);
+  std::vector<double> c2((size_t)nl);
+  std::vector<int64_t> off2((size_t)nl + 1, 0);
+  if ((rc = solve_locked(r, s2.data(), g2.data(), nl, n_threads, st2.data(), c2.data(), off2.data(), stats))) return rc;
+  // (the stored paths are the live requests' in order: only the offsets change)
+  r->path_off.assign((size_t)n + 1, 0);
+  for (int64_t q = 0; q < n; q++) { status[q] = TR_QUERY_INVALID_GOAL; if (cost) cost[q] = std::numeric_limits<double>::infinity(); }
+  int64_t j = 0;
+  for (int64_t q = 0; q < n; q++) {
+    int64_t len = 0;
+    if (j < nl && live[(size_t)j] == q) {
+      len = off2[(size_t)j + 1] - off2[(size_t)j];
+      status[q] = st2[(size_t)j];
+      // the one edge that joins the goal state to the roadmap: its cost is the state-space distance (connectVertices :2857-2861)
+      if (cost && st2[(size_t)j] == TR_QUERY_SOLVED)
+        cost[q] = c2[(size_t)j] + state_distance(r, &r->states[(size_t)neighbor_vertex[q] * r->S], &controls[(size_t)q * r->S]);
+      j++;
+    }
+    r->path_off[(size_t)q + 1] = r->path_off[(size_t)q] + len;
+    path_offsets[q + 1] = r->path_off[(size_t)q + 1];
+  }
+  r->dt.phase_ms[4] = ms_between(t0, Clock::now());
+  return TR_OK;
+}
+
+int tr_roadmap_tip_query_profile(tr_roadmap *r, double out[6]) {
+  if (!r || !out) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  for (int i = 0; i < 5; i++) out[i] = r->dt.phase_ms[i];
+  out[5] = (double)r->dt.st_ik_rounds;
+  return TR_OK;
+}
+
+}  // extern "C"

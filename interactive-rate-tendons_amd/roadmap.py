@@ -224,6 +224,7 @@ class RoadmapBuilder:
         vc = self.vertex_caches(states, device=device)
         prm = VoxelCachedLazyPRM(self.checker, states, edges)
         prm.set_caches(vc, ec)
+        prm.set_tips(tips)
         if n_landmarks:
             prm.prepare(n_landmarks)
         self.timing["create_roadmap"] = dict(seconds=time.perf_counter() - t0, vertices=len(states), candidate_edges=len(cand), edges=len(edges))
@@ -375,6 +376,9 @@ class VoxelCachedLazyPRM:
             raise ValueError("%s holds no voxel caches" % path)
         prm = cls(checker, d["states"], d["edges"], weights=d["weights"])
         prm.set_caches(d["vertex_caches"], d["edge_caches"])
+        tips = d.get("tips")
+        if tips is not None and len(tips) and np.isfinite(tips).all(axis=1).any():
+            prm.set_tips(tips, present=np.isfinite(tips).all(axis=1))       # (NaN rows: the file has no tip for that vertex)
         if n_landmarks:
             prm.prepare(n_landmarks)
         return prm
@@ -508,6 +512,127 @@ class VoxelCachedLazyPRM:
         self.search_profile = dict(kernel_ms=float(pr[0]), launches=int(pr[1]), expansions=int(pr[2]), bytes_per_expansion=float(pr[3]))
         return dict(status=status, cost=cost, path_offsets=off, path_vertices=pv, paths=_Paths(pv, off))
 
+    # ---- tip-goal queries (tr_roadmap_set_tips .. tr_roadmap_solve_tips, include/tendon_hip.h): roadmapIk + solveWithRoadmap for a batch ----
+    def set_tips(self, tips=None, present=None):
+        """The vertices' tip positions go to the device (vertexTipPositionProperty_): tips (V, 3), or None = computed there once
+        from the roadmap's states; present (bool[V], optional): False = the vertex has no tip and is never a neighbour."""
+        C = self._C
+        from .distributed import pack_bits
+        t = None
+        if tips is not None:
+            t = np.ascontiguousarray(tips, dtype=np.float64)
+            if t.shape != (len(self.states), 3):
+                raise self._L.InvalidArgument("tips must be (n_vertices, 3)")
+            if present is None and not np.isfinite(t).all():
+                raise self._L.InvalidArgument("tips must be finite where a vertex has one (pass `present`)")
+            t = np.where(np.isfinite(t), t, 0.0)
+        pb = None
+        if present is not None:
+            pr = np.asarray(present, dtype=bool)
+            if pr.shape != (len(self.states),):
+                raise self._L.InvalidArgument("present must be (n_vertices,)")
+            pb = np.ascontiguousarray(pack_bits(pr))
+        self._check(self.lib.tr_roadmap_set_tips(self._rm, t.ctypes.data_as(C.POINTER(C.c_double)) if t is not None else None,
+                                                 pb.ctypes.data_as(C.POINTER(C.c_uint64)) if pb is not None else None))
+
+    @staticmethod
+    def _requests(requests):
+        r = np.ascontiguousarray(requests, dtype=np.float64)
+        if r.ndim == 1:
+            r = r.reshape(1, -1)
+        if r.ndim != 2 or r.shape[1] != 3:
+            raise L.InvalidArgument("requests must be (n, 3)")
+        return r
+
+    def nearest_tips(self, requests, k=5):
+        """Per request the k vertices whose tips are nearest, among the vertices that have a tip and are valid in the current
+        grid, in the order (d2, vertex index) -> (vertices (n, k) int32, -1 padded; dist2 (n, k), +inf where padded)."""
+        C = self._C
+        r = self._requests(requests)
+        n = len(r)
+        idx = np.full((n, int(k)), -1, dtype=np.int32)
+        d2 = np.full((n, int(k)), np.inf)
+        self._check(self.lib.tr_roadmap_nearest_tips(self._rm, r.ctypes.data_as(C.POINTER(C.c_double)), n, int(k),
+                                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, d2
+
+    def nearest_tips_dev(self, d_requests, n, k, d_vertices, d_dist2=None):
+        """nearest_tips on device tensors of the checker's GPU (float64 (n, 3) -> int32 (n, k) [, float64 (n, k)])."""
+        import torch
+        eng = self.engine
+        pr = eng._check_dev(d_requests, torch.float64, 3 * n, "d_requests")
+        pv = eng._check_dev(d_vertices, torch.int32, n * k, "d_vertices")
+        pd = eng._check_dev(d_dist2, torch.float64, n * k, "d_dist2") if d_dist2 is not None else None
+        self._check(self.lib.tr_roadmap_nearest_tips_dev(self._rm, pr, int(n), int(k), pv, pd))
+
+    def _tip_params(self, k, tolerance, ik, motion_validator):
+        L_ = self._L
+        ikd = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, stop_threshold_err=tolerance,
+                   finite_difference_delta=1e-6)                     # what roadmapIk hands to inverse_kinematics
+        ikd.update(ik or {})
+        prm = L_.TrTipQueryParams(int(k), float(tolerance), L_.TrIkParams(int(ikd["max_iters"]), float(ikd["mu_init"]),
+                                  float(ikd["stop_threshold_JT_err_inf"]), float(ikd["stop_threshold_Dp"]),
+                                  float(ikd["stop_threshold_err"]), float(ikd["finite_difference_delta"])))
+        mv = motion_validator
+        sp = L_.TrSpaceParams(0.02, 0.01, 0.0001) if mv is None else \
+            L_.TrSpaceParams(mv.min_tension_change, mv.min_rotation_change, mv.min_retraction_change)
+        return prm, sp
+
+    def _tip_outputs(self, n):
+        S = self.states.shape[1] if self.states.ndim == 2 else self.engine.state_size
+        return dict(controls=np.empty((n, S)), tip=np.empty((n, 3)), error=np.empty(n), neighbor_vertex=np.empty(n, dtype=np.int32),
+                    outcome=np.empty(n, dtype=np.int32), last_valid_t=np.empty(n))
+
+    def tip_query_profile(self):
+        """Host wall time (ms) of the phases of the last roadmap_ik_batch / solve_to_tips, and the rounds of its IK batch."""
+        o = (self._C.c_double * 6)()
+        self._check(self.lib.tr_roadmap_tip_query_profile(self._rm, o))
+        return dict(nearest_ms=o[0], ik_ms=o[1], edges_ms=o[2], select_ms=o[3], solve_ms=o[4], ik_rounds=int(o[5]))
+
+    def roadmap_ik_batch(self, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None):
+        """roadmapIk (motion-planning/VoxelCachedLazyPRM.cpp:3095-3577) for a batch of tip requests in one call: per request IK
+        from the k vertices with the nearest tips, all n k problems in one device batch; the first solution in neighbour order
+        within tolerance whose edge from its neighbour is valid is REACHED, otherwise the last valid state towards each solution
+        whose tip is nearest the request is CLOSEST (the rule in include/tendon_hip.h).  -> dict(controls (n, S), tip (n, 3),
+        error, neighbor_vertex, outcome (TR_TIPQ_*), last_valid_t).  motion_validator: its state-space resolutions (None: the
+        defaults of Problem); ik: overrides of the IK arguments."""
+        C = self._C
+        r = self._requests(requests)
+        n = len(r)
+        prm, sp = self._tip_params(k, tolerance, ik, motion_validator)
+        o = self._tip_outputs(n)
+        dp, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(self.lib.tr_roadmap_ik_batch(self._rm, C.byref(sp), C.byref(prm), r.ctypes.data_as(dp), n, o["controls"].ctypes.data_as(dp),
+                                                 o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32),
+                                                 o["outcome"].ctypes.data_as(i32), o["last_valid_t"].ctypes.data_as(dp)))
+        return o
+
+    def solve_to_tips(self, starts, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0):
+        """roadmap_ik_batch, then solveWithRoadmap from starts[q] to request q's connection vertex: the fields of both, with
+        cost = roadmap cost + state-space distance from the connection vertex to the goal state (`controls`), which follows the
+        last vertex of paths[q].  A request without a neighbour ends TR_QUERY_INVALID_GOAL."""
+        C, L_ = self._C, self._L
+        r = self._requests(requests)
+        n = len(r)
+        s = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+        if len(s) != n:
+            raise L_.InvalidArgument("starts and requests differ in length")
+        prm, sp = self._tip_params(k, tolerance, ik, motion_validator)
+        o = self._tip_outputs(n)
+        status, cost, off = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n + 1, dtype=np.int64)
+        st = L_.TrRoadmapStats()
+        dp, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(self.lib.tr_roadmap_solve_tips(
+            self._rm, C.byref(sp), C.byref(prm), s.ctypes.data_as(i32), r.ctypes.data_as(dp), n, int(n_threads), o["controls"].ctypes.data_as(dp),
+            o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32),
+            o["last_valid_t"].ctypes.data_as(dp), status.ctypes.data_as(i32), cost.ctypes.data_as(dp), off.ctypes.data_as(C.POINTER(C.c_int64)),
+            C.byref(st)))
+        pv = np.zeros(int(off[-1]), dtype=np.int32)
+        self._check(self.lib.tr_roadmap_fetch_paths(self._rm, pv.ctypes.data_as(i32), len(pv)))
+        self.stats = dict(rounds=st.rounds, items_checked=st.items_checked, astar_runs=st.astar_runs, expanded=st.expanded)
+        o.update(status=status, cost=cost, path_offsets=off, path_vertices=pv, paths=_Paths(pv, off))
+        return o
+
     def search_state_bytes(self):
         """Device memory the graph searches hold for this roadmap between calls (tr_roadmap_search_state_bytes)."""
         b = self._C.c_int64(0)
@@ -529,3 +654,63 @@ class VoxelCachedLazyPRM:
         b = self._C.c_int64(0)
         self._check(self.lib.tr_roadmap_release_search_state(self._rm, self._C.byref(b)))
         return int(b.value)
+
+
+def interpolate_states(engine, a, b, t):
+    """CompoundStateSpace::interpolate for rows of a and b at t (Problem.cpp:101-163: linear, the shortest arc on the SO2
+    rotation) -- the state checkMotion's last_valid names, in the arithmetic of the device's tipq_interp."""
+    a = np.asarray(a, float).reshape(-1, engine.state_size)
+    b = np.asarray(b, float).reshape(-1, engine.state_size)
+    t = np.asarray(t, float).reshape(-1, 1)
+    out = a + (b - a) * t
+    n, rot, _ = engine.state_layout()
+    if rot:
+        x, y, tt = a[:, n], b[:, n], t[:, 0]
+        diff = y - x
+        far = np.abs(diff) > np.pi
+        diff = np.where(diff > 0.0, 2.0 * np.pi - diff, -2.0 * np.pi - diff)
+        v = x - diff * tt
+        v = np.where(v > np.pi, v - 2.0 * np.pi, np.where(v < -np.pi, v + 2.0 * np.pi, v))
+        out[:, n] = np.where(far, v, out[:, n])
+    return out
+
+
+def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0):
+    """The loop of apps/roadmap_chained_plan.cpp:535-679 for a batch of chains: chain c starts at roadmap vertex
+    start_vertex[c] and visits the tips waypoints[c, 0], waypoints[c, 1], ...; hop h of EVERY chain is one solve_to_tips call.
+    A hop ends at an off-roadmap goal state joined to the roadmap by one edge, so the next hop starts at that state: it is
+    prefixed with the reversed connecting edge (goal state -> its connection vertex) and that edge's distance, then follows the
+    roadmap from the connection vertex.  A chain stops at its first hop that is not solved.
+    -> dict(hops: per hop the solve_to_tips result plus start_state (C, S), prefix_cost (C,), total_cost (C,), active (C,);
+            cost (C,): the sum over the chain's solved hops; solved (C,): every hop solved)."""
+    wp = np.asarray(waypoints, dtype=np.float64)
+    if wp.ndim == 2:
+        wp = wp[None]
+    if wp.ndim != 3 or wp.shape[2] != 3:
+        raise L.InvalidArgument("waypoints must be (chains, hops, 3)")
+    C_, H = wp.shape[0], wp.shape[1]
+    at = np.ascontiguousarray(np.asarray(start_vertex, dtype=np.int32).reshape(-1))
+    if len(at) != C_:
+        raise L.InvalidArgument("one start vertex per chain")
+    state = prm.states[at].copy()
+    on_roadmap = np.ones(C_, dtype=bool)
+    active = np.ones(C_, dtype=bool)
+    total = np.zeros(C_)
+    hops = []
+    for h in range(H):
+        idx = np.flatnonzero(active)
+        res = dict(active=active.copy(), start_state=state.copy(), prefix_cost=np.zeros(C_), total_cost=np.full(C_, np.inf), chains=idx)
+        if len(idx):
+            r = prm.solve_to_tips(at[idx], wp[idx, h], tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, n_threads=n_threads)
+            res.update(r)
+            ok = r["status"] == L.TR_QUERY_SOLVED
+            # the reversed connecting edge of the previous hop
+            res["prefix_cost"][idx] = np.where(on_roadmap[idx], 0.0, prm.engine.state_distance(state[idx], prm.states[at[idx]]))
+            res["total_cost"][idx] = np.where(ok, res["prefix_cost"][idx] + r["cost"], np.inf)
+            total[idx[ok]] += res["total_cost"][idx[ok]]
+            state[idx[ok]] = r["controls"][ok]
+            at[idx[ok]] = r["neighbor_vertex"][ok]
+            on_roadmap[idx[ok]] = False
+            active[idx[~ok]] = False
+        hops.append(res)
+    return dict(hops=hops, cost=np.where(active, total, np.inf), solved=active.copy(), final_state=state, final_vertex=at)
