@@ -2,7 +2,7 @@
 // (VoxelEnvironment::voxelize_valid_backbone_motion, motion-planning/VoxelEnvironment.cpp:304-424,
 // driven by AbstractVoxelMotionValidator::checkMotion, AbstractVoxelMotionValidator.h:143-151).
 //
-// One bisection level of all edges at a time (edge_host.inc explains why that equals the reference's
+// One bisection level of all edges at a time (edge_run_host.inc explains why that equals the reference's
 // depth-first order): `edge_open` turns the frontier intervals that are still undecided into new FK
 // samples (OMPL interpolate), K1 + K2 evaluate them, `edge_fold` folds the verdicts into per-edge
 // state, `edge_filter` runs the reference's `should_subdivide` on both halves of every interval and
@@ -181,7 +181,7 @@ __device__ inline void interpolate_state_dev(const EdgeSpaceK &sk, const double 
 // that folds the LAST outstanding sample of an edge's level runs should_subdivide on that level's signature rows and pushes the
 // edge's next level at the tail.  An edge waits for nothing but its own samples: first_invalid_t is per edge
 // (VoxelEnvironment.cpp:357-398), so the sample set of every edge -- and with it the verdict AND the count of FK calls -- is what
-// the level-synchronous schedule (edge_host.inc) evaluates.
+// the level-synchronous schedule (edge_run_host.inc) evaluates.
 // The queue is the pool in push order: slots [first, tail), the edges' first midpoints seeded before the launch in the order of
 // the edge list (neighbouring edges share end vertices: their rows stay close in memory; ordering the seeds by edge length, longest
 // first, was measured -- it shortens the tail and costs more than that in scattered row reads), then everything the waves push.  EQ_AVAIL counts the published samples nobody has taken yet (a

@@ -34,6 +34,7 @@
 #include "sphere_kernel.hpp"
 #include "verdict_kernel.hpp"
 #include "edge_kernel.hpp"
+#include "edge_plan.hpp"
 #include "knn_kernel.hpp"
 #include "cache_merge.hpp"
 #include "env_kernel.hpp"
@@ -70,7 +71,7 @@ struct EventPair { hipEvent_t a, b; };
 constexpr int64_t kRetractSortMin = 8192;   // below this a launch is a few waves per CU at most: ordering them buys nothing
 constexpr int64_t kSmallBatch = 4096;   // tr_validate_batch: up to here the single-stream path without a device-wide sync
 
-// device state of the edge frontier (edge_kernel.hpp / edge_host.inc)
+// device state of the edge frontier (edge_kernel.hpp / edge_run_host.inc)
 struct EdgeDev {
   int64_t cap = 0;                // pool capacity this was sized for; edges per chunk <= cap / 2
   double *lvl_states = nullptr;   // [cap][S]  states of the level being evaluated
@@ -81,7 +82,6 @@ struct EdgeDev {
   double *A = nullptr, *B = nullptr, *rel = nullptr;  // [cap/2][S] x 2, [cap/2]
   uint32_t *edge_ok = nullptr; int32_t *nfk = nullptr;
   unsigned long long *first_inv = nullptr, *last_t = nullptr;
-  uint32_t *counters = nullptr;
   uint32_t *nd = nullptr; int64_t *cnt = nullptr;      // discrete variant: validSegmentCount, sample offsets [cap/2 + 2]
   uint32_t *sig = nullptr; int64_t sig_stride = 0;     // [cap][sig_stride] cell signatures of the pool samples (sweep_kernel.hpp)
   // [cap] point counts of the pool samples whose signatures fk_verdict_retract wrote (tip-aligned rows).  NOT the
@@ -147,13 +147,25 @@ struct tr_ctx {
   // env TENDON_HIP_FUSED selects; the edge calls, the sphere checker and the voxel caches need the points and use 1 / 0.
   int fuse = 2;
   int64_t fb_cap = 1 << 17;       // columns of the fallback pass's point workspace: one resident round of waves (tr_create), env TENDON_HIP_FB_CAP
-  int32_t *d_fb_list = nullptr; uint32_t *d_fb_count = nullptr; int64_t fb_list_cap = 0;
-  // second lane of the edge bisection (edge_host.inc: EdgeLane): its own fallback list, stream, counters
-  static constexpr int kMaxLanes = 4;             // lanes of an edge bisection (edge_host.inc): streams, counters, fallback lists, ordering buffers
-  int32_t *d_fb_list1[kMaxLanes - 1] = {}; uint32_t *d_fb_count1[kMaxLanes - 1] = {}; int64_t fb_list1_cap[kMaxLanes - 1] = {};   // lanes 1 ..
-  hipStream_t edge_stream[kMaxLanes] = {};
-  uint32_t *edge_hc[kMaxLanes] = {};              // pinned host images of the lanes' counters
-  uint32_t *d_edge_counters1[kMaxLanes - 1] = {}; // lanes 1 .. (lane 0: EdgeDev::counters)
+  // retraction robots: the batch ordered by backbone length for the verdict-only kernel (cache_merge.hpp: retraction_order);
+  // for batches of at least retract_sort_min configurations (TENDON_HIP_RETRACT_SORT=<n>; 0 = never, keep arrival order)
+  struct RetractOrder {
+    uint32_t *keys[2] = {nullptr, nullptr}; int32_t *vals[2] = {nullptr, nullptr}; int64_t cap = 0;
+    int32_t *kbegin = nullptr;          // [cap / 64 + 1] per wave of the ordered batch: the step its tip-aligned loop may start at
+    double *handoff = nullptr; int64_t handoff_cap = 0;   // [19 + N + S][cap]: fk_retract_prologue -> fk_verdict_retract
+    trk::MergeScratch ms;               // radix-sort scratch of lanes 1 .. (lane 0 uses tr_ctx::merge)
+  };
+  // One lane of an edge bisection (edge_run_host.inc: EdgeLane; launch_verdict's `lane`): what the lanes must not share when they run
+  // side by side on their own streams.  Lane 0's fallback list and ordering buffers are also those of tr_validate_batch* and
+  // tr_reserve; its counters are allocated with EdgeDev (the edge queue and the discrete form use them without any lane set up).
+  static constexpr int kMaxLanes = edge_plan::kMaxLanes;
+  struct EdgeLaneDev {
+    hipStream_t stream = nullptr;
+    uint32_t *hc = nullptr;             // pinned host image of the counters
+    uint32_t *counters = nullptr;       // device [EC_COUNT]
+    int32_t *fb_list = nullptr; uint32_t *fb_count = nullptr; int64_t fb_list_cap = 0;   // candidates of the verdict path's fallback pass
+    RetractOrder ro;
+  } lane[kMaxLanes];
   int edge_lanes = kMaxLanes;                     // TENDON_HIP_EDGE_LANES=1 .. 4: exactly that many lanes (1: one lane only); default: by the edge count
   bool edge_lanes_fixed = false;
   bool edge_kernels_loaded = false;               // tr_reserve_edges has launched every kernel of the indexed edge path once
@@ -161,7 +173,7 @@ struct tr_ctx {
   // launches on lanes: the default where it applies (backbone checker, no retraction, verdict-only schedule); TENDON_HIP_EDGE_QUEUE=0
   // keeps the lanes (A/B, tests).  edge_queue_waves: workgroups of that launch (0 = what the device holds at once)
   bool edge_queue = true;
-  bool edge_queue_forced = false;                 // TENDON_HIP_EDGE_QUEUE=1: also for the host-array form (default there: the lanes, see validate_edges_indexed_impl)
+  bool edge_queue_forced = false;                 // TENDON_HIP_EDGE_QUEUE=1: also for the host-array form (default there: the lanes, see ValidateIndexed::try_queue)
   int edge_queue_waves = 0;
   uint32_t edge_queue_last[4] = {0, 0, 0, 0};     // the last queue run: samples, rounds (wave batches), samples through the exact sweep, flags
   double edge_rate_seen = 0.0;                    // own samples per edge of this context's last indexed edge call (0 = none yet): sizes
@@ -169,15 +181,6 @@ struct tr_ctx {
   bool edge_lane_guess_forced = false;            // TENDON_HIP_EDGE_LANE_GUESS was given: it overrides the rate this context has seen
   double edge_lane_guess = 6.0;                   // own samples per edge assumed when a half is given its share of the pool
                                                   // (TENDON_HIP_EDGE_LANE_GUESS: testing, a small value provokes the overflow path)
-  // retraction robots: the batch ordered by backbone length for the verdict-only kernel (cache_merge.hpp: retraction_order);
-  // for batches of at least retract_sort_min configurations (TENDON_HIP_RETRACT_SORT=<n>; 0 = never, keep arrival order)
-  // (one set of buffers per lane of the edge bisection, launch_verdict's `lane`)
-  struct RetractOrder {
-    uint32_t *keys[2] = {nullptr, nullptr}; int32_t *vals[2] = {nullptr, nullptr}; int64_t cap = 0;
-    int32_t *kbegin = nullptr;          // [cap / 64] per wave of the ordered batch: the step its tip-aligned loop may start at
-    double *handoff = nullptr; int64_t handoff_cap = 0;   // [19 + N + S][cap]: fk_retract_prologue -> fk_verdict_retract
-    trk::MergeScratch ms;               // radix-sort scratch of lanes 1 .. (lane 0 uses tr_ctx::merge)
-  } ro[kMaxLanes];
   int64_t retract_sort_min = kRetractSortMin;
   bool rows_one_step = false;           // behind the grid's own first interval every RK4 step ends in the next row
   bool retract_wave_start = true;       // TENDON_HIP_RETRACT_KBEGIN_OFF (A/B switch of profiles/probe_retract.py): +1 - 2 %
@@ -509,6 +512,49 @@ int note_dev_work(tr_ctx *ctx, hipStream_t s) {
   return TR_OK;
 }
 
+// A lane's fallback list (with its counter) and its ordering buffers, grown to hold n entries: the caller says how much room it wants
+// (whole waves; the lanes of an edge bisection ask for their share of the pool up front, since growing mid-run would stall all streams)
+int ensure_lane_fallback(tr_ctx *ctx, int lane, int64_t n) {
+  tr_ctx::EdgeLaneDev &ln = ctx->lane[lane];
+  if (ln.fb_list_cap >= n) return TR_OK;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  int rc;
+  if ((rc = dev_alloc(ctx, &ln.fb_list, (size_t)n))) return rc;
+  if (!ln.fb_count && (rc = dev_alloc(ctx, &ln.fb_count, 1))) return rc;
+  ln.fb_list_cap = n;
+  return TR_OK;
+}
+int ensure_lane_order(tr_ctx *ctx, int lane, int64_t n) {
+  tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
+  if (ro.cap >= n) return TR_OK;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  int rc;
+  for (int q = 0; q < 2; q++) {
+    if ((rc = dev_alloc(ctx, &ro.keys[q], (size_t)n))) return rc;
+    if ((rc = dev_alloc(ctx, &ro.vals[q], (size_t)n))) return rc;
+  }
+  if ((rc = dev_alloc(ctx, &ro.kbegin, (size_t)n / 64 + 1))) return rc;
+  ro.cap = n;
+  return TR_OK;
+}
+
+// radix-sort scratch of a lane's ordering: lane 0 sorts in the context's (cache_merge.hip), lanes 1 .. in their own
+trk::MergeScratch &order_scratch(tr_ctx *ctx, int lane) { return lane == 0 ? ctx->merge : ctx->lane[lane].ro.ms; }
+
+// The point workspace from column `col` on, as K1 writes it and as K2 reads it (stored points, no frames, lengths or tips)
+trk::FkOut ws_fk_out(const tr_ctx *ctx, int64_t col) {
+  const Workspace &w = ctx->ws;
+  const bool ret = ctx->K.enable_retraction;
+  return trk::FkOut{w.px + col, w.py + col, w.pz + col, nullptr, nullptr, w.Li + col, nullptr, w.conv + col, ret ? w.np + col : nullptr,
+                    ret ? w.homeLi + col : nullptr};
+}
+trk::SweepIn ws_sweep_in(const tr_ctx *ctx, int64_t col) {
+  const Workspace &w = ctx->ws;
+  const bool ret = ctx->K.enable_retraction;
+  return trk::SweepIn{w.px + col, w.py + col, w.pz + col, ret ? w.np + col : nullptr, w.Li + col, w.conv + col, ret ? w.homeLi + col : nullptr,
+                      w.acc + col};
+}
+
 // ---- K1 launch (instantiations live in fk_inst.hip objects) ------------------------------------
 int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, hipStream_t s, int lane = 0) {
   if (n <= 0) return TR_OK;
@@ -520,20 +566,10 @@ int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const 
     // A large batch of a retraction robot is integrated in the order of its backbone lengths, as the verdict-only kernels do
     // (a wave runs from its LONGEST backbone's base to the tip, the shorter ones idle: in arrival order half of the lane-steps
     // are masked), and every stored output goes to its configuration's own column: same planes, bit for bit.
-    tr_ctx::RetractOrder &ro = ctx->ro[lane];           // (a lane of the edge bisection: its own buffers and sort scratch, as launch_verdict's)
-    int rc;
-    if (ro.cap < n) {
-      HIP_TRY(ctx, hipDeviceSynchronize());
-      const int64_t want = round_up(n, 64);
-      for (int q = 0; q < 2; q++) {
-        if ((rc = dev_alloc(ctx, &ro.keys[q], (size_t)want))) return rc;
-        if ((rc = dev_alloc(ctx, &ro.vals[q], (size_t)want))) return rc;
-      }
-      if ((rc = dev_alloc(ctx, &ro.kbegin, (size_t)want / 64))) return rc;
-      ro.cap = want;
-    }
+    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;      // (a lane of the edge bisection: its own buffers and sort scratch, as launch_verdict's)
+    if (const int rc = ensure_lane_order(ctx, lane, round_up(n, 64))) return rc;
     const int32_t *perm = nullptr;
-    const hipError_t e = trk::retraction_order(lane ? ro.ms : ctx->merge, d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &perm, s,
+    const hipError_t e = trk::retraction_order(order_scratch(ctx, lane), d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &perm, s,
                                                ctx->K.dL, ctx->k_first, ctx->rows_one_step, ro.kbegin);
     if (e != hipSuccess) return fail(ctx, TR_ERR_HIP, std::string("retraction order: ") + hipGetErrorString(e));
     a.d_perm = perm;
@@ -643,17 +679,11 @@ int launch_verdict(tr_ctx *ctx, const double *d_states, int64_t n, uint64_t *d_b
   // lanes 1 .. (the further lanes of an edge bisection, running concurrently on their own streams): their own list and counter, and
   // the workspace columns [lane fb_cap, (lane + 1) fb_cap) for their fallback pass
   if (lane < 0 || lane >= tr_ctx::kMaxLanes) return fail(ctx, TR_ERR_RUNTIME, "bad lane");
-  int32_t *&fb_list = lane ? ctx->d_fb_list1[lane - 1] : ctx->d_fb_list;
-  uint32_t *&fb_count = lane ? ctx->d_fb_count1[lane - 1] : ctx->d_fb_count;
-  int64_t &fb_list_cap = lane ? ctx->fb_list1_cap[lane - 1] : ctx->fb_list_cap;
-  if (fb_list_cap < n) {
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if ((rc = dev_alloc(ctx, &fb_list, (size_t)round_up(n, 64)))) return rc;
-    if (!fb_count && (rc = dev_alloc(ctx, &fb_count, 1))) return rc;
-    fb_list_cap = round_up(n, 64);
-  }
+  if ((rc = ensure_lane_fallback(ctx, lane, round_up(n, 64)))) return rc;
+  int32_t *const fb_list = ctx->lane[lane].fb_list;
+  uint32_t *const fb_count = ctx->lane[lane].fb_count;
   const int64_t cap = std::min<int64_t>(ctx->fb_cap, round_up(n, 64));
-  if ((rc = ensure_workspace(ctx, lane ? (lane + 1) * ctx->fb_cap : cap))) return rc;
+  if ((rc = ensure_workspace(ctx, lane == 0 ? cap : (lane + 1) * ctx->fb_cap))) return rc;
   const int64_t fcol = lane * ctx->fb_cap;                        // first workspace column of this lane's fallback pass
   tr_ctx::VerdictRing &vr = ctx->vring;
   if (!vr.d_slots) {
@@ -686,18 +716,9 @@ int launch_verdict(tr_ctx *ctx, const double *d_states, int64_t n, uint64_t *d_b
   }
   if (ctx->K.enable_retraction && ctx->retract_sort_min > 0 && n >= ctx->retract_sort_min) {
     // waves of one backbone length: see retraction_order.  The mask is filled by atomic ORs, so it starts from zero.
-    tr_ctx::RetractOrder &ro = ctx->ro[lane];
-    if (ro.cap < n) {
-      HIP_TRY(ctx, hipDeviceSynchronize());
-      const int64_t want = round_up(n, 64);
-      for (int q = 0; q < 2; q++) {
-        if ((rc = dev_alloc(ctx, &ro.keys[q], (size_t)want))) return rc;
-        if ((rc = dev_alloc(ctx, &ro.vals[q], (size_t)want))) return rc;
-      }
-      if ((rc = dev_alloc(ctx, &ro.kbegin, (size_t)want / 64))) return rc;
-      ro.cap = want;
-    }
-    const hipError_t e = trk::retraction_order(lane ? ro.ms : ctx->merge, d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &a.perm, s,
+    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
+    if ((rc = ensure_lane_order(ctx, lane, round_up(n, 64)))) return rc;
+    const hipError_t e = trk::retraction_order(order_scratch(ctx, lane), d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &a.perm, s,
                                                ctx->K.dL, ctx->k_first, ctx->rows_one_step, ro.kbegin);
     a.wave_k_begin = ctx->retract_wave_start ? ro.kbegin : nullptr;
     if (e != hipSuccess) return fail(ctx, TR_ERR_HIP, std::string("retraction order: ") + hipGetErrorString(e));
@@ -708,16 +729,14 @@ int launch_verdict(tr_ctx *ctx, const double *d_states, int64_t n, uint64_t *d_b
   HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(uint32_t), s));
   // the fallback pass sweeps columns of the small point workspace
   const bool ret = ctx->K.enable_retraction;      // K1r's body in both launches, tip-aligned rows in the fallback workspace
-  trk::SweepIn in{w.px + fcol, w.py + fcol, w.pz + fcol, ret ? w.np + fcol : nullptr, w.Li + fcol, w.conv + fcol, ret ? w.homeLi + fcol : nullptr,
-                  w.acc + fcol};
   const trk::FusedSweepArgs *d_fargs; size_t lds_f; int fslot;
-  if ((rc = fused_args_slot(ctx, in, spheres ? 2 : 1, d_bits, d_flags, s, &d_fargs, &lds_f, &fslot))) return rc;
+  if ((rc = fused_args_slot(ctx, ws_sweep_in(ctx, fcol), spheres ? 2 : 1, d_bits, d_flags, s, &d_fargs, &lds_f, &fslot))) return rc;
   const trk::FkOut vout{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tips, nullptr, nullptr, nullptr};
   trk::FkLaunch vl{d_states, n, 0, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
                    (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, vout, s};
   if (ctx->K.enable_retraction) {
     // the prologue kernel's hand-over planes (fk_retract_prologue -> fk_verdict_retract), one set per lane of the edge bisection
-    tr_ctx::RetractOrder &ro = ctx->ro[lane];
+    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
     const int64_t hld = round_up(n, 64);
     if (ro.handoff_cap < hld) {
       HIP_TRY(ctx, hipDeviceSynchronize());
@@ -727,8 +746,7 @@ int launch_verdict(tr_ctx *ctx, const double *d_states, int64_t n, uint64_t *d_b
     }
     vl.d_handoff = ro.handoff; vl.handoff_ld = hld; vl.d_perm = a.perm;
   }
-  const trk::FkOut fout{w.px + fcol, w.py + fcol, w.pz + fcol, nullptr, nullptr, w.Li + fcol, nullptr, w.conv + fcol, ret ? w.np + fcol : nullptr,
-                        ret ? w.homeLi + fcol : nullptr};
+  const trk::FkOut fout = ws_fk_out(ctx, fcol);
   const trk::FkLaunch fl{d_states, cap, w.ld, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
                          (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, fout, s};
   const size_t lds_v = trk::verdict_lds_bytes(a.NM, sig != nullptr);
@@ -795,9 +813,8 @@ int launch_edge_queue(tr_ctx *ctx, hipStream_t s, uint32_t *sig, int64_t sig_str
   a.finish_hot();
   HIP_TRY(ctx, hipMemcpyAsync(vr.d_slots + vslot, &a, sizeof(a), hipMemcpyHostToDevice, s));
   int rc;
-  trk::SweepIn in{w.px, w.py, w.pz, nullptr, w.Li, w.conv, nullptr, w.acc};
   const trk::FusedSweepArgs *d_fargs; size_t lds_f; int fslot;
-  if ((rc = fused_args_slot(ctx, in, 1, nullptr, nullptr, s, &d_fargs, &lds_f, &fslot))) return rc;
+  if ((rc = fused_args_slot(ctx, ws_sweep_in(ctx, 0), 1, nullptr, nullptr, s, &d_fargs, &lds_f, &fslot))) return rc;
   const size_t lds_v = std::max(trk::verdict_lds_bytes(a.NM, true) + (size_t)trk::EQ_STASH_WORDS * 4, lds_f);   // (+ the waves' stash: edge_queue_kernel.hpp)
   const trk::FkOut none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const trk::FkLaunch fl{nullptr, 0, 0, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
@@ -1062,7 +1079,7 @@ void tr_destroy(tr_ctx *c) {
                   c->d_vbits, w.px, w.py, w.pz, w.acc, w.Li, w.conv,
                   w.states, w.bits, w.tips, w.flags, w.L, w.npts,
                   c->edge.lvl_states, c->edge.bits, c->edge.sample_edge, c->edge.sample_t, c->edge.open, c->edge.frontier,
-                  c->edge.A, c->edge.B, c->edge.rel, c->edge.edge_ok, c->edge.nfk, c->edge.first_inv, c->edge.last_t, c->edge.counters, c->edge.nd, c->edge.cnt, c->edge.sig, c->edge.sig_np, c->edge.ix_states, c->edge.ix_idx, c->edge.open2, c->edge.lvl_states2, c->edge.q_remaining, c->edge.q_lvl_base, c->edge.q_lvl_cnt, c->edge.q_ctl, c->edge.q_args, c->d_envw[0], c->d_envw[1], c->d_sph_near, c->d_sph_tmp};
+                  c->edge.A, c->edge.B, c->edge.rel, c->edge.edge_ok, c->edge.nfk, c->edge.first_inv, c->edge.last_t, c->edge.nd, c->edge.cnt, c->edge.sig, c->edge.sig_np, c->edge.ix_states, c->edge.ix_idx, c->edge.open2, c->edge.lvl_states2, c->edge.q_remaining, c->edge.q_lvl_base, c->edge.q_lvl_cnt, c->edge.q_ctl, c->edge.q_args, c->d_envw[0], c->d_envw[1], c->d_sph_near, c->d_sph_tmp};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   trk::merge_free(c->merge);
   if (c->fused.d_slots) { (void)hipFree(c->fused.d_slots); (void)hipHostFree(c->fused.h_slots); for (auto &e : c->fused.ev) (void)hipEventDestroy(e); }
@@ -1079,23 +1096,17 @@ void tr_destroy(tr_ctx *c) {
   for (void *q : c->knn.p) if (q) (void)hipFree(q);
   if (c->vstore.ids) (void)hipFree(c->vstore.ids);
   if (c->vstore.masks) (void)hipFree(c->vstore.masks);
-  if (c->d_fb_list) (void)hipFree(c->d_fb_list);
-  for (int q = 0; q < tr_ctx::kMaxLanes - 1; q++) {
-    if (c->d_fb_list1[q]) (void)hipFree(c->d_fb_list1[q]);
-    if (c->d_fb_count1[q]) (void)hipFree(c->d_fb_count1[q]);
-    if (c->d_edge_counters1[q]) (void)hipFree(c->d_edge_counters1[q]);
-  }
-  for (int q = 0; q < tr_ctx::kMaxLanes; q++) { if (c->edge_stream[q]) (void)hipStreamDestroy(c->edge_stream[q]); if (c->edge_hc[q]) (void)hipHostFree(c->edge_hc[q]); }
   if (c->edge.q_hctl) (void)hipHostFree(c->edge.q_hctl);
   if (c->edge.q_hargs) (void)hipHostFree(c->edge.q_hargs);
   if (c->h_stage) (void)hipHostFree(c->h_stage);
-  for (auto &ro : c->ro) {
-    for (int q = 0; q < 2; q++) { if (ro.keys[q]) (void)hipFree(ro.keys[q]); if (ro.vals[q]) (void)hipFree(ro.vals[q]); }
-    if (ro.kbegin) (void)hipFree(ro.kbegin);
-    if (ro.handoff) (void)hipFree(ro.handoff);
+  for (auto &ln : c->lane) {
+    tr_ctx::RetractOrder &ro = ln.ro;
+    void *lp[] = {ln.counters, ln.fb_list, ln.fb_count, ro.keys[0], ro.keys[1], ro.vals[0], ro.vals[1], ro.kbegin, ro.handoff};
+    for (void *q : lp) if (q) (void)hipFree(q);
+    if (ln.stream) (void)hipStreamDestroy(ln.stream);
+    if (ln.hc) (void)hipHostFree(ln.hc);
     trk::merge_free(ro.ms);
   }
-  if (c->d_fb_count) (void)hipFree(c->d_fb_count);
   ik_release(c);
   delete c;
 }
@@ -1334,12 +1345,7 @@ int tr_reserve(tr_ctx *c, int64_t n) {
   int rc;
   if (c->fuse == 2) {
     // the verdict path keeps no points: a list of fallback candidates and the fallback pass's small workspace
-    if (c->fb_list_cap < n) {
-      HIP_TRY(c, hipDeviceSynchronize());
-      if ((rc = dev_alloc(c, &c->d_fb_list, (size_t)round_up(std::max<int64_t>(n, 64), 64)))) return rc;
-      if (!c->d_fb_count && (rc = dev_alloc(c, &c->d_fb_count, 1))) return rc;
-      c->fb_list_cap = round_up(std::max<int64_t>(n, 64), 64);
-    }
+    if (n > 0 && (rc = ensure_lane_fallback(c, 0, round_up(std::max<int64_t>(n, 64), 64)))) return rc;
     rc = ensure_workspace(c, std::min<int64_t>(c->fb_cap, std::max<int64_t>(n, 64)));
   } else {
     rc = ensure_workspace(c, n);
@@ -2203,6 +2209,8 @@ int tr_profile_end(tr_ctx *c) {
 
 }  // extern "C"
 
-#include "edge_host.inc"
+#include "edge_run_host.inc"
+#include "edge_pairs_host.inc"
+#include "edge_indexed_host.inc"
 #include "sample_host.inc"
 #include "ik_host.inc"

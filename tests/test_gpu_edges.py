@@ -609,3 +609,52 @@ def test_edge_queue_equals_the_level_synchronous_lanes(irt, orc, helpers):
                                                 states[edges[idx, 1]], inv_rot=np.eye(3) if inv_rot is None else inv_rot, nthreads=0, lib=orc.omp_lib())
             assert np.array_equal(want["valid"][idx], ov)
             assert np.array_equal(want["n_fk"][idx][ov], onf[ov])
+
+
+def test_reserve_edges_changes_no_result(irt):
+    """tr_reserve_edges sizes the pool, the lanes' fallback lists and the index buffers ahead of a roadmap's first edge call and launches
+    every kernel of the indexed path once on nothing (the lanes' lists and the queue's arguments through the helpers the real run
+    uses).  A call after it gives the verdicts, FK counts, domain-error count and schedule record of a call on a fresh context: on the
+    host form with two lanes (1 500 vertices of config 3, 7 neighbours each = 10 500 edges, the smallest roadmap the lanes take; through a
+    64-column fallback workspace, since 2 x 2 lanes x the default 2^17 columns exceed the 128 256 slots this roadmap is given -- the
+    arithmetic is in tests/cpp/edge_plan_test.cpp) and on the device-resident form through the edge queue.  Of the queue's record the
+    sample count, the count through the exact sweep and the flags are compared; `rounds` counts the waves' claims of up to 64 published
+    samples and depends on their timing (profiles/r04/edge_queue_phases_v1.txt: 38 634 .. 38 697 over six identical calls)."""
+    import torch
+    W = irt.workloads
+    robot = W.robot_config3()
+    vox, _ = W.reach_environment(seed=7, n_spheres=48)
+    nv = 1500
+    states = W.random_states(robot, nv, seed=91, tau_max=20.0)
+    nt = len(robot.tendons)
+    near = np.argsort(np.linalg.norm(states[:, None, :nt] - states[None, :, :nt], axis=2), axis=1)[:, 1:8]
+    edges = np.ascontiguousarray(np.stack([np.repeat(np.arange(nv), 7), near.reshape(-1)], 1), dtype=np.int32)
+    ne = len(edges)
+    d_states, d_edges = torch.from_numpy(states).cuda(), torch.from_numpy(edges).cuda()
+
+    def host(reserve):
+        chk = irt.VoxelBackboneValidityChecker(robot, irt.VoxelEnvironment(), vox)
+        if reserve:
+            chk.engine.reserve_edges(ne)
+        out = irt.VoxelBackboneMotionValidator(chk).check_motion_indexed(states, edges)
+        return np.asarray(out["valid"]), np.asarray(out["n_fk"]), out["n_domain_errors"], chk.engine.edge_schedule_last()
+
+    def device(reserve):
+        eng = irt.VoxelBackboneValidityChecker(robot, irt.VoxelEnvironment(), vox).engine
+        if reserve:
+            eng.reserve_edges(ne)
+        d_bits = torch.zeros((ne + 63) // 64, dtype=torch.int64, device="cuda")
+        d_nfk = torch.zeros(ne, dtype=torch.int32, device="cuda")
+        nd = eng.validate_edges_indexed_dev(d_states, nv, d_edges, ne, d_bits, d_nfk)
+        return irt.unpack_bits(d_bits.cpu().numpy().view(np.uint64), ne), d_nfk.cpu().numpy(), nd, eng.edge_schedule_last()
+
+    lanes_env = {"TENDON_HIP_EDGE_LANES": "2", "TENDON_HIP_FB_CAP": "64"}
+    plain, reserved = _with_env(irt, lanes_env, lambda: host(False)), _with_env(irt, lanes_env, lambda: host(True))
+    q_plain, q_reserved = device(False), device(True)
+    print("schedules: lanes", plain[3], reserved[3], "queue", q_plain[3], q_reserved[3])
+    for a, b in ((plain, reserved), (q_plain, q_reserved), (plain, q_plain)):
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
+    assert plain[3] == reserved[3] and plain[3]["samples"] == 0                       # the lanes took both calls
+    assert all(q_plain[3][k] == q_reserved[3][k] for k in ("samples", "exact_sweep", "flags")) and q_plain[3]["rounds"] > 0
+    assert q_plain[3]["flags"] == 0 and q_plain[3]["samples"] == int(q_plain[1].sum()) - 2 * ne     # ... and the queue both of these
+    assert 0.2 < plain[0].mean() < 0.995 and plain[1].max() > 4
