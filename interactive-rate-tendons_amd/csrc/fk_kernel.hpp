@@ -28,10 +28,11 @@
 // tip position <= 1e-9 m, see tests/); the bit-exact integer/predicate stage lives in
 // sweep_kernel.hpp and is compiled without contraction.
 // That tolerance guards the interfaces, not this arithmetic.  The integrator's own guard is tests/test_gpu_fk_truth.py:
-// points, tip frame, L and L_i of fk_rk4_batch_uniform / fk_rk4_batch_retract, the tips-only form and (through its length
-// test) fk_verdict against a 40-digit evaluation of the same discrete scheme, within 4 (E_ref + E_design) per state --
-// E_ref the fp64 oracle's own distance from that truth, E_design the shift that 2e-14 in the reciprocals below makes in
-// it (tests/golden/make_fk_truth.py): 3e-16 .. 3e-13 m on the points.  A change to the right-hand side answers to that.
+// points, tip frame, L and L_i of fk_rk4_batch_uniform / fk_rk4_batch_retract, the tips-only form, (through their length
+// tests and their tips) fk_verdict and fk_verdict_retract, and (through its length test) fk_edge_queue against a 40-digit
+// evaluation of the same discrete scheme, within 4 (E_ref + E_design) per state -- E_ref the fp64 oracle's own distance from
+// that truth, E_design the shift that 2e-14 in the reciprocals below makes in it (tests/golden/make_fk_truth.py): 3e-16 ..
+// 3e-13 m on the points.  A change to the right-hand side answers to that.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>

@@ -24,7 +24,9 @@ namespace trk {
 // coefficient loads, wave-uniform degree) plus a rotation of (sin, cos) by dtheta = theta_new - theta_old
 // with an 11th/12th-order Taylor pair -- |dtheta| is ~1e-2 for a half step; beyond 1/8 rad it falls back to
 // sincos.  Re-evaluating at the same abscissa rotates by exactly zero.  (FK parity is a 1e-9 m tolerance:
-// the rotations add ~1e-16 each.)
+// the rotations add ~1e-16 each.  The guard of this arithmetic, tests/test_gpu_fk_truth.py, counts them: its error model
+// puts c * 1e-16 on the c-th routing evaluation of a lane's own first interval, 4 stages x at most 2 steps --
+// tests/golden/make_fk_truth.py, E_trig.)
 template <int N>
 struct RouteCarry { double th[N], sn[N], cs[N]; };
 
@@ -349,7 +351,9 @@ __device__ __forceinline__ void fk_retract_body(
   }
 
   // home-shape tendon lengths: home_shape clamps s_start into [0, L] (TendonRobot.cpp:257-258); composite
-  // Simpson over the lane's points with a trapezoid for a trailing odd interval (see tendon_hip.hip: home_lengths)
+  // Simpson over the lane's points with a trapezoid for a trailing odd interval (see tendon_hip.hip: home_lengths).
+  // Guarded per lane by tests/test_gpu_fk_truth.py: a 40-digit evaluation of the same rule over the lane's abscissae, within
+  // (P_lane + 2) ulp -- a weight, a row of hl[] or the end the trapezoid sits at shows there, not in a comparison of flags.
   bool any_general = false;
 #pragma unroll
   for (int j = 0; j < N; j++) any_general = any_general || (pk->home_kind[j] == 2);

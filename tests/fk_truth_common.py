@@ -15,15 +15,28 @@ Fixture layout (numeric arrays only; 24 states per fixture):
   L_hi (24,), L_lo; Li_hi (24, N), Li_lo
   Eref_p, Eref_R, Eref_L (24,), Eref_Li (24, N)        distance of the oracle's fp64 result from the truth
   Edes_p, Edes_R, Edes_L (24,), Edes_Li (24, N)        largest shift under the one-Newton-step perturbation model
+Retraction fixtures (consts[9] = 1) also hold
+  Etrig_p, Etrig_R, Etrig_L (24,), Etrig_Li (24, N)    largest shift under the carried-(sin, cos) perturbation of the lane's own
+                                                       first interval (route_tendon, fk_retract_kernel.hpp); added to E_design
+  home_hi (24, N) f64, home_lo f32                     truth of home_shape(s_start).L_i: the rule orc_home_shape follows, in mpmath
+  Eref_home (24, N)                                    distance of the oracle's home lengths from it
 """
+import contextlib
 import os
 
 import numpy as np
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-FIXTURES = ("config1", "config2", "config3", "config3_rot", "config3_rot_ret", "config2_dl35", "n1", "n8")
+NEW_RETRACTION = ("config3_ret_edges", "config2_ret_edges", "n1_ret", "n8_ret")       # dL = L / 40, the special s_start values
+FIXTURES = ("config1", "config2", "config3", "config3_rot", "config3_rot_ret", "config2_dl35", "n1", "n8") + NEW_RETRACTION
+RETRACTION = ("config3_rot_ret",) + NEW_RETRACTION
 N_STATES = 24
 NEWTON_REL = 2e-14            # fk_kernel.hpp: one Newton step leaves ~2e-14 relative error in 1/x and 1/sqrt(x)
+TRIG_ABS = 1e-16              # fk_retract_kernel.hpp (route_tendon): every carried rotation of (sin, cos) adds ~1e-16 absolute
+TRIG_CARRIED = 8              # ... and a lane's own first interval carries at most 4 stages x 2 steps of them
+# first-interval classes of a retraction state (first_interval_class)
+ONE_STEP_SHORT, ONE_STEP_DL, TWO_STEPS, NO_INTERVAL, SINGLE = range(5)
+CLASS_NAMES = ("one step < dL", "exactly dL", "two steps", "no interval", "single")
 
 
 def path(name):
@@ -35,8 +48,55 @@ def load(name):
         return {k: d[k] for k in d.files}
 
 
+@contextlib.contextmanager
+def with_env(**values):
+    """Environment variables for the time of a `with` block (the engine reads its switches when a context is created)."""
+    old = {k: os.environ.get(k) for k in values}
+    os.environ.update({k: str(v) for k, v in values.items()})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def special_s_start(L, dL):
+    """The sixteen s_start values of the NEW_RETRACTION fixtures, in row order; the last one (negative retraction) is reported
+    unconverged by the kernels, has no truth and is not a fixture row."""
+    return np.array([0.0, dL / 3, L - 20 * dL, L - 17.5 * dL, 17 * dL, L - 3.2 * dL, L - 2.49 * dL, L - 1.5 * dL, L - 1.25 * dL,
+                     L - 0.75 * dL, L - dL / 2, L - dL / 4, L, L + 0.01, 0.0975, -0.01])
+
+
+def first_interval_class(fx):
+    """(24,) the class of every state's own first interval, from the oracle's step sequence.  `exactly dL` is an aligned grid
+    (s_start = L - k dL): t_range reaches its abscissae by at most P - 1 additions of dL, each rounded at the magnitude of L, so
+    the interval is dL to within (P / 2) ulp(L) -- 1e-13 dL; the kernels' shared grid differs from it by as much."""
+    L, dL = fx["consts"][0], fx["consts"][1]
+    tol = 0.5 * fx["n_points"].max() * np.spacing(L)
+    out = np.empty(N_STATES, np.int64)
+    for i in range(N_STATES):
+        if fx["n_points"][i] == 1:
+            out[i] = SINGLE if fx["states"][i, -1] >= L else NO_INTERVAL
+        elif fx["step_row"][i, 0] < 0:
+            out[i] = TWO_STEPS
+        else:
+            out[i] = ONE_STEP_DL if abs(fx["steps"][i, 0, 1] - dL) <= tol else ONE_STEP_SHORT
+    return out
+
+
+def abscissae(fx, i):
+    """(n_points,) the fp64 arc-length abscissae of state i's backbone points: where its intervals start, and L."""
+    k = int(fx["n_steps"][i])
+    starts = np.r_[True, fx["step_row"][i, :k][:-1] >= 0][:k]
+    return np.r_[fx["steps"][i, :k, 0][starts], fx["consts"][0]]
+
+
 def robot_from_fixture(irt, fx, **limits):
-    """The package robot of a fixture; limits: min_length= / max_length= as (N,) arrays."""
+    """The package robot of a fixture; limits: min_length= / max_length= as (N,) arrays; enable_rotation= overrides the
+    fixture's switch (the states then need a rotation column)."""
     N = fx["C"].shape[0]
     L, dL, ro, ri, E, nu, r, res, rot, ret = fx["consts"]
     lo = limits.get("min_length", np.full(N, -0.015))
@@ -44,7 +104,8 @@ def robot_from_fixture(irt, fx, **limits):
     tendons = [irt.TendonSpecs(C=[float(x) for x in fx["C"][j]], D=[float(x) for x in fx["D"][j]], max_tension=float(fx["max_tension"][j]),
                                min_length=float(lo[j]), max_length=float(hi[j])) for j in range(N)]
     return irt.TendonRobot(tendons=tendons, specs=irt.BackboneSpecs(L=float(L), dL=float(dL), ro=float(ro), ri=float(ri), E=float(E), nu=float(nu)),
-                           r=float(limits.get("r", r)), enable_rotation=bool(rot), enable_retraction=bool(ret), residual_threshold=float(res))
+                           r=float(limits.get("r", r)), enable_rotation=bool(limits.get("enable_rotation", rot)), enable_retraction=bool(ret),
+                           residual_threshold=float(res))
 
 
 def err_vs_truth(x, hi, lo):
@@ -63,11 +124,59 @@ def stored_points(fx, p):
 
 def bounds(fx):
     """bound = 4 (E_ref + E_design), at least 4 ulp of the output's magnitude -- per state (points: the largest
-    coordinate of the state's backbone; R: 1; L and every L_i: themselves)."""
+    coordinate of the state's backbone; R: 1; L and every L_i: themselves).  E_design is the Newton-step shift plus, in
+    retraction fixtures, the carried-(sin, cos) shift.
+
+    Retraction fixtures have a `home` entry, max(4 E_ref_home, floor).  The home length has no Newton-step reciprocal, so its
+    E_design is 0.  The floor is derived, not measured: the quadrature sums a lane's P_lane integrand values (each a correctly
+    rounded sqrt of a sum near 1, so at most 1 ulp of a term that is no larger than the weighted sum) with one rounding per
+    addition, and then multiplies by dL and divides by 3 -- P_lane + 2 roundings, each at most ulp(home) once scaled to the
+    result: floor = (P_lane + 2) ulp(home).  The closed forms (L - s, (L - s) helix_scale) take 2 - 3 roundings and sit under
+    the same expression."""
     pmag = np.nanmax(np.abs(np.where(fx["pt_idx"][:, :, None] >= 0, fx["p_hi"], np.nan)), axis=(1, 2))
     f = lambda e_ref, e_des, mag: np.maximum(4.0 * (e_ref + e_des), 4.0 * np.spacing(np.abs(mag)))
-    return dict(p=f(fx["Eref_p"], fx["Edes_p"], pmag), R=f(fx["Eref_R"], fx["Edes_R"], np.ones(N_STATES)),
-                L=f(fx["Eref_L"], fx["Edes_L"], fx["L_hi"]), L_i=f(fx["Eref_Li"], fx["Edes_Li"], fx["Li_hi"]))
+    des = lambda k: fx["Edes_" + k] + (fx["Etrig_" + k] if "Etrig_" + k in fx else 0.0)
+    out = dict(p=f(fx["Eref_p"], des("p"), pmag), R=f(fx["Eref_R"], des("R"), np.ones(N_STATES)),
+               L=f(fx["Eref_L"], des("L"), fx["L_hi"]), L_i=f(fx["Eref_Li"], des("Li"), fx["Li_hi"]))
+    if "home_hi" in fx:
+        out["home"] = np.maximum(4.0 * fx["Eref_home"], (fx["n_points"][:, None] + 2) * np.spacing(np.abs(fx["home_hi"])))
+    return out
+
+
+def length_change(fx, home=None):
+    """(dl, b), both (24, N): what the truth says about home - L_i, and how far a length limit has to be from it before a
+    kernel must be on the truth's side: bound_Li + bound_home + 2 ulp(home).  Retraction fixtures carry a home truth per state;
+    the others take `home`, the robot's fp64 home lengths (N,), which every kernel reads from the same table: bound_home = 0."""
+    b = bounds(fx)
+    if "home_hi" in fx:
+        dl = (fx["home_hi"] - fx["Li_hi"]) + (fx["home_lo"].astype(np.float64) - fx["Li_lo"].astype(np.float64))
+        return dl, b["L_i"] + b["home"] + 2 * np.spacing(np.abs(fx["home_hi"]))
+    dl = (home[None, :] - fx["Li_hi"]) - fx["Li_lo"].astype(np.float64)
+    return dl, b["L_i"] + 2 * np.spacing(home)[None, :]
+
+
+def exact_zero(fx):
+    """(24, N) bool: home - L_i is 0 - 0 in every kernel, exactly: a one-point backbone (L_i = 0) whose home length is 0 too
+    (s_start >= L, or a quadrature over one point; the closed forms give (L - s_start) * scale even then)."""
+    if "home_hi" not in fx:
+        return np.zeros(fx["Li_hi"].shape, bool)
+    return (fx["n_points"] == 1)[:, None] & (fx["home_hi"] == 0) & (fx["Li_hi"] == 0)
+
+
+def separated(fx, home=None):
+    """None, or (i, k, j): state k's true length change on tendon j lies within its own b of a limit placed b_i beyond or short
+    of state i's.  The verdict probes (tests/test_gpu_fk_truth.py) place such limits.  The exact zeros (exact_zero) are left out
+    on both sides.  As k: the truth decides their flag with no allowance.  As i: their limits sit at 0 +- 1.5e-323, and the
+    zero-tension state of a helix robot is within its bound of 0 by construction (its L_i is its home length to rounding) under
+    every seed; the probe's own rule -- at most one such state, never the probed one -- is what covers it."""
+    dl, bb = length_change(fx, home)
+    ez = exact_zero(fx)
+    for j in range(dl.shape[1]):
+        for i in np.flatnonzero(~ez[:, j]):
+            for k in np.flatnonzero(~ez[:, j]):
+                if k != i and min(abs(dl[k, j] - (dl[i, j] + bb[i, j])), abs(dl[k, j] - (dl[i, j] - bb[i, j]))) <= bb[k, j]:
+                    return i, int(k), j
+    return None
 
 
 def errors(fx, p, R_tip, L, L_i):

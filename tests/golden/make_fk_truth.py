@@ -25,12 +25,25 @@ Per state the fixture stores (layout: tests/fk_truth_common.py)
             1/|p_dot| (so on A_i through its cube and on the length rate |p_dot|^2 / |p_dot|), on every component of the
             6x6 solution and on the |v| of the length quadrature, for s = +1 everywhere, s = -1 everywhere (one Newton step
             errs to one side) and two seeded random sign patterns.  E_design is the largest shift of each output.
+  E_trig    retraction fixtures only: the second documented error source.  A retracted lane evaluates the routing of its own
+            first interval itself (route_tendon, fk_retract_kernel.hpp) and carries (sin, cos) of every tendon's angle from one
+            stage abscissa to the next by a Taylor rotation; the comment there puts ~1e-16 absolute on each rotation.  The
+            interval has at most 2 RK4 steps of 4 stages, so the c-th routing evaluation of the interval (c = 1 .. 8) gets
+            c * 1e-16 added to sin and to cos -- both with +, with opposite signs, and with seeded random signs per tendon and
+            evaluation.  E_trig is the largest shift of each output; it is added to E_design (fk_truth_common.bounds).  Fixed
+            before any GPU run.
+  home      retraction fixtures only: home_shape(s_start).L_i by the rule orc_home_shape follows (L - s, (L - s) sqrt(1 + d0^2
+            c1^2), or composite Simpson over the state's fp64 abscissae with dx = dL and a trapezoid for a trailing odd
+            interval) in mpmath, and Eref_home, the oracle's distance from it.  No reciprocal: E_design = 0.
 The bound of the tests is 4 (E_ref + E_design) with a floor of 4 ulp (fk_truth_common.bounds).  It changes only through a
 change to this model, with the reason written here; it is never tuned on what a kernel returns.
 
 States (24 per fixture, all converged in the oracle -- checked here): 12 of workloads.random_states at the tension cap
 the existing tests use, 8 of _taut_states (tests/test_gpu_rhs_high_torsion.py), the zero state, one state with a single
-taut tendon, two states with every tendon at 95 - 100 % of max_tension.
+taut tendon, two states with every tendon at 95 - 100 % of max_tension.  With retraction s_start is uniform in [0, 0.6 L];
+the fixtures of fk_truth_common.NEW_RETRACTION (dL = L / 40) give rows 0 .. 14 the s_start values of
+fk_truth_common.special_s_start instead: aligned grids, first intervals of two RK4 steps, two- and one-point backbones, s_start
+= L and beyond.
 """
 import importlib
 import importlib.util
@@ -52,6 +65,7 @@ import fk_truth_common as ftc  # noqa: E402
 
 mp.mp.dps = 40
 PERT_PATTERNS = (("const", 1), ("const", -1), ("rand", 1), ("rand", 2))
+TRIG_PATTERNS = (("trig", (1, 1)), ("trig", (1, -1)), ("trigrand", 1))
 ZERO, ONE = mp.mpf(0), mp.mpf(1)
 
 
@@ -76,6 +90,29 @@ def _add(a, b):
     return [x + y for x, y in zip(a, b)]
 
 
+class TrigSigns:
+    """(d sin, d cos) per tendon for the c-th routing evaluation of a lane's own first interval."""
+
+    def __init__(self, pattern):
+        kind, arg = pattern
+        self.const = arg if kind == "trig" else None
+        self.bits = None if kind == "trig" else np.random.default_rng(2000 + arg).integers(0, 2, 1 << 12)
+        self.c = self.k = 0
+
+    def shifts(self, n_tendons):
+        self.c += 1
+        assert self.c <= ftc.TRIG_CARRIED
+        a = mp.mpf(ftc.TRIG_ABS) * self.c
+        if self.const is not None:
+            return [(a * self.const[0], a * self.const[1])] * n_tendons
+        out = []
+        for _ in range(n_tendons):
+            b = self.bits[self.k:self.k + 2]
+            self.k += 2
+            out.append((a * (2 * int(b[0]) - 1), a * (2 * int(b[1]) - 1)))
+        return out
+
+
 class Signs:
     """The sign s of every perturbed site, in the order the model reaches them."""
 
@@ -94,11 +131,12 @@ class Signs:
         return ONE + mp.mpf(ftc.NEWTON_REL) * s
 
 
-def routing(C, D, t):
-    """[(r, r', r'')] per tendon at the fp64 abscissa t: polynomial calculus and sin / cos in mpmath."""
+def routing(C, D, t, dsc=None):
+    """[(r, r', r'')] per tendon at the fp64 abscissa t: polynomial calculus and sin / cos in mpmath.  dsc: per tendon what
+    is added to (sin, cos)."""
     t = mp.mpf(float(t))
     out = []
-    for c, d in zip(C, D):
+    for j, (c, d) in enumerate(zip(C, D)):
         def poly(co, k):          # k-th derivative of sum co[i] t^i
             s = ZERO
             for i in range(k, len(co)):
@@ -110,6 +148,8 @@ def routing(C, D, t):
         th, th1, th2 = poly(c, 0), poly(c, 1), poly(c, 2)
         rh, rh1, rh2 = poly(d, 0), poly(d, 1), poly(d, 2)
         sn, cs = mp.sin(th), mp.cos(th)
+        if dsc is not None:
+            sn, cs = sn + dsc[j][0], cs + dsc[j][1]
         e = [sn, cs, ZERO]
         e1 = [cs * th1, -sn * th1, ZERO]
         e2 = [-sn * th1 ** 2 + cs * th2, -cs * th1 ** 2 - sn * th2, ZERO]
@@ -198,7 +238,8 @@ def model(fx_consts, C, D, state, v0, u0, steps, pattern=None):
     """Truth of one state: dict(p [points][3], R (column-major 9, tip), L, Li) in mpmath.  steps: [(t, h, row)]."""
     Lr, dL, ro, ri, E, nu, r, res, rot, ret = (float(x) for x in fx_consts)
     N = len(C)
-    signs = Signs(pattern) if pattern is not None else None
+    trig = TrigSigns(pattern) if pattern is not None and pattern[0].startswith("trig") else None
+    signs = Signs(pattern) if pattern is not None and trig is None else None
     Kse, Kbt = stiffness(ro, ri, E, nu)
     tau = [mp.mpf(float(s)) for s in state[:N]]
     x = dict(p=[ZERO] * 3, R=[[ONE, ZERO, ZERO], [ZERO, ONE, ZERO], [ZERO, ZERO, ONE]], v=[mp.mpf(float(s)) for s in v0],
@@ -206,16 +247,23 @@ def model(fx_consts, C, D, state, v0, u0, steps, pattern=None):
     pts = [list(x["p"])]
     rcache = {}
 
-    def rt(t):
+    def rt_plain(t):
         if t not in rcache:                               # a step's end abscissa is the next step's start
             if len(rcache) > 4:
                 rcache.clear()
             rcache[t] = routing(C, D, t)
         return rcache[t]
 
+    rt = rt_plain
+    own = trig is not None                                # inside the lane's own first interval
     for (t, h, row) in steps:
         hm = mp.mpf(h)
         tm, te = t + h * 0.5, t + h                      # fp64, as the oracle and the kernels' table form them
+        if own:
+            rt = lambda tt: routing(C, D, tt, trig.shifts(N))        # noqa: E731  (four evaluations a step, in stage order)
+        else:
+            rt = rt_plain
+        own = own and row < 0
         k1 = deriv(rt(t), Kse, Kbt, tau, x, signs)
         k2 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k1), signs)
         k3 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k2), signs)
@@ -231,6 +279,50 @@ def model(fx_consts, C, D, state, v0, u0, steps, pattern=None):
         pts = [_mv(Rz, q) for q in pts]
         Rm = _mm(Rz, Rm)
     return dict(p=pts, R=[Rm[rr][cc] for cc in range(3) for rr in range(3)], L=x["L"], Li=x["Li"])
+
+
+def home_truth(fx_consts, C, D, s_start, t_pts):
+    """home_shape(s_start).L_i by orc_home_shape's rule, in mpmath: [N] mpf.  t_pts: the state's fp64 abscissae."""
+    L, dL = float(fx_consts[0]), float(fx_consts[1])
+    s = min(max(float(s_start), 0.0), L)
+    if s == L:
+        return [ZERO] * len(C)
+    Lh = mp.mpf(L) - mp.mpf(s)
+    degree = lambda co: max([i for i in range(1, len(co)) if abs(float(co[i])) > 0.0] or [0])
+    poly = lambda co, t: sum((mp.mpf(float(a)) * t ** i for i, a in enumerate(co)), ZERO)
+    dot = lambda co: [i * float(co[i]) for i in range(1, len(co))]            # i * c[i] is what the oracle rounds, too
+    out = []
+    for c, d in zip(C, D):
+        rdeg, tdeg = degree(d), degree(c)
+        if rdeg == 0 and tdeg == 0:
+            out.append(Lh)
+        elif rdeg == 0 and tdeg == 1:
+            out.append(Lh * mp.sqrt(1 + mp.mpf(float(d[0])) ** 2 * mp.mpf(float(c[1])) ** 2))
+        else:
+            vals = []
+            for t in t_pts:
+                t = mp.mpf(float(t))
+                dd, dv, cd = poly(dot(d), t), poly(d, t), poly(dot(c), t)
+                vals.append(mp.sqrt(dd * dd + (dv * dv) * (cd * cd) + 1))
+            out.append(simpson_defined(vals, mp.mpf(dL)))
+    return out
+
+
+def simpson_defined(vals, dx):
+    """simpsons_defined (oracle/tendon_oracle.c): composite Simpson, a trapezoid for the LAST interval when their number is odd."""
+    n = len(vals)
+    if n < 2:
+        return ZERO
+    nint, odd = n - 1, ZERO
+    if nint % 2:
+        odd = dx * (vals[n - 2] + vals[n - 1]) / 2
+        nint -= 1
+    if nint == 0:
+        return odd
+    total = vals[0] + vals[nint]
+    for i in range(1, nint):
+        total += (4 if i % 2 else 2) * vals[i]
+    return odd + total * dx / 3
 
 
 def split(x):
@@ -251,12 +343,13 @@ def _taut_module():
     return m
 
 
-def _counted_robot(irt, n_tendons):
-    """The robots of test_fk_other_tendon_counts (tests/test_gpu_parity.py), same seeds."""
+def _counted_robot(irt, n_tendons, retraction=False):
+    """The robots of test_fk_other_tendon_counts (tests/test_gpu_parity.py), same seeds; retraction: dL = L / 40."""
     rng = np.random.default_rng(n_tendons)
     tendons = [irt.TendonSpecs(C=[2 * np.pi * k / n_tendons, float(rng.uniform(-6, 6)), float(rng.uniform(-10, 10))],
                                D=[0.01, float(rng.uniform(-0.01, 0.01))], max_tension=12.0) for k in range(n_tendons)]
-    return irt.TendonRobot(tendons=tendons, specs=irt.BackboneSpecs(dL=0.004), enable_rotation=True)
+    return irt.TendonRobot(tendons=tendons, specs=irt.BackboneSpecs(dL=0.2 / 40 if retraction else 0.004), enable_rotation=True,
+                           enable_retraction=retraction)
 
 
 def fixture_robot(irt, name):
@@ -270,13 +363,19 @@ def fixture_robot(irt, name):
         r = W.robot_config2()
         r.specs.dL = 0.0035
         return r, 15.0, 17
+    if name == "config2_ret_edges":
+        r = W.robot_config2()
+        r.specs.dL, r.enable_retraction = r.specs.L / 40, True
+        return r, 20.0, 143
     if name.startswith("config3"):
         r = W.robot_config3()
         r.enable_rotation = "rot" in name
         r.enable_retraction = "ret" in name
-        return r, (15.0 if r.enable_retraction else None), 44
-    n = int(name[1:])
-    return _counted_robot(irt, n), 12.0 / np.sqrt(n), 7 + n
+        if name in ftc.NEW_RETRACTION:
+            r.specs.dL = r.specs.L / 40
+        return r, (15.0 if r.enable_retraction else None), 44 + 100 * (name in ftc.NEW_RETRACTION)
+    n = int(name[1:].split("_")[0])
+    return _counted_robot(irt, n, name.endswith("_ret")), 12.0 / np.sqrt(n), 7 + n + 100 * name.endswith("_ret")
 
 
 def fixture_states(irt, name, attempt=0):
@@ -297,6 +396,9 @@ def fixture_states(irt, name, attempt=0):
     if robot.enable_retraction:
         st[:12, -1] *= 0.6                               # s_start in [0, 0.6 L] for every state
         st[20:, -1] = rng.uniform(0.0, 0.6 * robot.specs.L, 4)
+    if name in ftc.NEW_RETRACTION:
+        st[:15, -1] = ftc.special_s_start(robot.specs.L, robot.specs.dL)[:15]
+        st[15, -1] = rng.uniform(0.0, 0.6 * robot.specs.L)  # in the place of the negative s_start, which has no truth
     assert st.shape == (ftc.N_STATES, robot.state_size())
     return robot, st
 
@@ -319,7 +421,7 @@ def stored_idx(n_points, p_max):
 
 def state_task(args):
     """One state: the truth, E_ref against the oracle's result, E_design over the perturbation patterns."""
-    consts, C, D, state, v0, u0, steps, idx, orc_p, orc_R, orc_L, orc_Li = args
+    consts, C, D, state, v0, u0, steps, idx, orc_p, orc_R, orc_L, orc_Li, t_pts, orc_home = args
     t0 = time.time()
     base = model(consts, C, D, state, v0, u0, steps)
     out = {}
@@ -340,14 +442,28 @@ def state_task(args):
         des["Li"] = [max(e, abs(x - y)) for e, x, y in zip(des["Li"], m["Li"], base["Li"])]
     out["Edes_p"], out["Edes_R"], out["Edes_L"] = float(des["p"]), float(des["R"]), float(des["L"])
     out["Edes_Li"] = np.array([float(e) for e in des["Li"]])
+    if orc_home is not None:                              # retraction
+        des = dict(p=ZERO, R=ZERO, L=ZERO, Li=[ZERO] * len(C))
+        for pat in TRIG_PATTERNS if steps else ():
+            m = model(consts, C, D, state, v0, u0, steps, pat)
+            des["p"] = max([des["p"]] + [abs(m["p"][i][k] - base["p"][i][k]) for i in idx for k in range(3)])
+            des["R"] = max([des["R"]] + [abs(x - y) for x, y in zip(m["R"], base["R"])])
+            des["L"] = max(des["L"], abs(m["L"] - base["L"]))
+            des["Li"] = [max(e, abs(x - y)) for e, x, y in zip(des["Li"], m["Li"], base["Li"])]
+        out["Etrig_p"], out["Etrig_R"], out["Etrig_L"] = float(des["p"]), float(des["R"]), float(des["L"])
+        out["Etrig_Li"] = np.array([float(e) for e in des["Li"]])
+        hl = [split(x) for x in home_truth(consts, C, D, state[-1], t_pts)]
+        out["home_hi"] = np.array([h for h, _ in hl], np.float64)
+        out["home_lo"] = np.array([l for _, l in hl], np.float32)
+        out["Eref_home"] = ftc.err_vs_truth(orc_home, out["home_hi"], out["home_lo"])
     out["seconds"] = time.time() - t0
     return out
 
 
-def fixture_tasks(name):
-    """(arrays of the fixture that need no mpmath, [state_task arguments])"""
+def fixture_tasks(name, first_attempt=0):
+    """(arrays of the fixture that need no mpmath, [state_task arguments], the robot's home lengths without retraction)"""
     irt = _irt()
-    for attempt in range(20):
+    for attempt in range(first_attempt, first_attempt + 20):
         robot, st = fixture_states(irt, name, attempt)
         orb = oracle_robot(robot)
         shapes = [orb.shape(s) for s in st]
@@ -370,10 +486,11 @@ def fixture_tasks(name):
               v0=np.array([s["v_i"] for s in shapes]), u0=np.array([s["u_i"] for s in shapes]), attempt=np.array(attempt))
     tasks = []
     for i, (s, sl, idx) in enumerate(zip(shapes, steps, idxs)):
-        fx["steps"][i, :len(sl)] = [(t, h) for t, h, _ in sl]
+        fx["steps"][i, :len(sl)] = np.array([(t, h) for t, h, _ in sl]).reshape(-1, 2)      # (no step: a one-point backbone)
         fx["step_row"][i, :len(sl)] = [r for _, _, r in sl]
         fx["pt_idx"][i, :len(idx)] = idx
-        tasks.append((consts, C, D, st[i], s["v_i"], s["u_i"], sl, idx, s["p"], s["R"][-1], s["L"], s["L_i"]))
+        orc_home = orb.home_shape(st[i, -1])["L_i"] if robot.enable_retraction else None
+        tasks.append((consts, C, D, st[i], s["v_i"], s["u_i"], sl, idx, s["p"], s["R"][-1], s["L"], s["L_i"], s["t"], orc_home))
     home = orb.home_shape()["L_i"] if not robot.enable_retraction else None
     return fx, tasks, home
 
@@ -391,6 +508,10 @@ def save_npz(path, arrays):
             z.writestr(info, buf.getvalue())
 
 
+class TooClose(RuntimeError):
+    pass
+
+
 def assemble(name, fx, results, home):
     Q, N = fx["pt_idx"].shape[1], fx["C"].shape[0]
     fx["p_hi"] = np.zeros((ftc.N_STATES, Q, 3)); fx["p_lo"] = np.zeros((ftc.N_STATES, Q, 3), np.float32)
@@ -398,29 +519,33 @@ def assemble(name, fx, results, home):
         q = len(r["p_hi"]) // 3
         fx["p_hi"][i, :q] = r["p_hi"].reshape(q, 3)
         fx["p_lo"][i, :q] = r["p_lo"].reshape(q, 3)
-    for key in ("R_hi", "R_lo", "Li_hi", "Li_lo", "Eref_Li", "Edes_Li"):
+    ret = bool(fx["consts"][9])
+    for key in ("R_hi", "R_lo", "Li_hi", "Li_lo", "Eref_Li", "Edes_Li") + (("Etrig_Li", "home_hi", "home_lo", "Eref_home") if ret else ()):
         fx[key] = np.stack([r[key] for r in results])
     for key in ("L_hi", "L_lo"):
         fx[key] = np.array([r[key][0] for r in results])
-    for key in ("Eref_p", "Eref_R", "Eref_L", "Edes_p", "Edes_R", "Edes_L"):
+    for key in ("Eref_p", "Eref_R", "Eref_L", "Edes_p", "Edes_R", "Edes_L") + (("Etrig_p", "Etrig_R", "Etrig_L") if ret else ()):
         fx[key] = np.array([r[key] for r in results], np.float64)
     b = ftc.bounds(fx)
-    if home is not None:
-        # the verdict probes (tests/test_gpu_fk_truth.py) place a length limit b away from one state's truth: no other state's
-        # truth may lie within its own b of such a limit
-        for j in range(N):
-            dl = home[j] - fx["Li_hi"][:, j]
-            bb = b["L_i"][:, j] + 2 * np.spacing(home[j])
-            for i in range(ftc.N_STATES):
-                for k in range(ftc.N_STATES):
-                    if k != i and min(abs(dl[k] - (dl[i] + bb[i])), abs(dl[k] - (dl[i] - bb[i]))) <= bb[k]:
-                        raise RuntimeError("%s: states %d and %d are within the bound of each other on tendon %d" % (name, i, k, j))
+    # the verdict probes (tests/test_gpu_fk_truth.py) place a length limit b away from one state's truth: no other state's
+    # truth may lie within its own b of such a limit (fk_truth_common.separated; retraction: home truth per state)
+    clash = ftc.separated(fx, home)
+    if clash is not None:
+        raise TooClose("%s: states %d and %d are within the bound of each other on tendon %d" % ((name,) + clash))
+    if name in ftc.NEW_RETRACTION:
+        cls = ftc.first_interval_class(fx)
+        print("%-16s first-interval classes: %s" % (name, ", ".join("%s: %s" % (ftc.CLASS_NAMES[c], np.flatnonzero(cls == c).tolist()) for c in range(5))))
+        if name == "config3_ret_edges":
+            assert all((cls == c).any() for c in range(5)), "a first-interval class does not occur"
     save_npz(ftc.path(name), fx)
     rng =lambda a: "%.2g .. %.2g" % (np.min(a), np.max(a))
     secs = sum(r["seconds"] for r in results)
     print("%-16s E_ref p %s  L_i %s | E_design p %s  L_i %s | bound p %s  R %s  L %s  L_i %s | %.0f s of model runs, %d KB"
           % (name, rng(fx["Eref_p"]), rng(fx["Eref_Li"]), rng(fx["Edes_p"]), rng(fx["Edes_Li"]), rng(b["p"]), rng(b["R"]), rng(b["L"]),
              rng(b["L_i"]), secs, os.path.getsize(ftc.path(name)) // 1024), flush=True)
+    if ret:
+        print("%-16s E_trig p %s  L_i %s | E_ref home %s | bound home %s" % ("", rng(fx["Etrig_p"]), rng(fx["Etrig_Li"]), rng(fx["Eref_home"]),
+                                                                            rng(b["home"])), flush=True)
 
 
 def main(names):
@@ -430,7 +555,14 @@ def main(names):
     with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
         futures = [(n, fx, [pool.submit(state_task, t) for t in tasks], home) for n, fx, tasks, home in prepared]
         for n, fx, fs, home in futures:
-            assemble(n, fx, [f.result() for f in fs], home)
+            while True:
+                try:
+                    assemble(n, fx, [f.result() for f in fs], home)
+                    break
+                except TooClose as e:                    # the next seed of the tensions (and of the ordinary rows' s_start)
+                    print(e, "-- next seed", flush=True)
+                    fx, tasks, home = fixture_tasks(n, int(fx["attempt"]) + 1)
+                    fs = [pool.submit(state_task, t) for t in tasks]
     print("generated %d fixtures in %.0f s" % (len(names), time.time() - t0))
 
 
