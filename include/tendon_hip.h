@@ -221,6 +221,61 @@ int tr_ik_batch_dev(tr_ctx *ctx, const tr_ik_params *params, const double *d_ini
                     int64_t des_ld, const double *lo, const double *hi, double *d_states_out, double *d_tips_out,
                     double *d_error_out, int32_t *d_iters_out, int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
 
+/* ---- loaded forward kinematics: TendonRobot::general_shape --------------------------------- */
+
+/* The arguments of TendonRobot::general_shape after the loads and the guess (tendon/TendonRobot.h:199-203); a NULL
+ * tr_shoot_params* means the defaults written there: 100, 0.1, 1e-9, 1e-4, 1e-6. */
+typedef struct {
+  int32_t max_iters;
+  double  mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta;
+} tr_shoot_params;
+
+/* Batched TendonRobot::general_shape (tendon/TendonRobot.h:155-219 -> general_tension_shape, tendon/TendonRobot.cpp:689-952):
+ * the shape of the rod under a tip force and moment F_e, L_e and a distributed force and moment f_e, l_e per unit length, all
+ * in the robot's base frame BEFORE the state's rotation (general_shape rotates the solved shape).  It is a boundary-value
+ * problem: classical RK4 over t_range(0, L, dL) from p = 0, R = I and base strains (v0, u0) with tendon_deriv's loaded right-hand
+ * side (tendon_deriv.cpp:331-332), solved for the six strains by single shooting until the tip balance
+ * e = (F_e_est - F_e, L_e_est - L_e) of PointForces::calc_point_forces (TendonRobot.cpp:188-217, routing at s = L) vanishes.
+ *   - The distributed load is ONE CONSTANT VECTOR PAIR per problem (gravity).  The reference takes functions of (t, p); a
+ *     position-dependent load is not offered.
+ *   - The optimiser is this library's own Levenberg-Marquardt (tr_ik_batch's, without bounds) with levmar's central-difference
+ *     Jacobian (d_j = max(|1e-4 p_j|, delta)) and gain-ratio damping; it is not levmar's code path.  The damping term is
+ *     mu diag(J^T J) with mu starting at mu_init (Marquardt's scaling: strains, curvatures, forces and moments put nine decades
+ *     into diag(J^T J), and mu_init max diag(J^T J) times the identity freezes the bending directions), and the step that the
+ *     |Dp| test judges small is still evaluated before the problem ends.  Stops: |e| <=
+ *     residual_threshold -> converged (levmar's reason 6, the only one general_tension_shape reports as converged);
+ *     |J^T e|_inf <= stop_threshold_JT_err_inf; |Dp| <= stop_threshold_Dp |p|; max_iters; a non-finite residual.  All but the first
+ *     report not converged; none is an error of the call.
+ *   - Start: guess (n x 6 rows (v, u)), or with guess == NULL the UNLOADED solution of the problem's tensions
+ *     (solve_initial_bending), not the reference's straight rod (v, u) = (e3, 0).  At zero load that start already balances the
+ *     tip, so the call takes zero iterations and returns tr_fk_batch's shape; under load it is a few iterations from the answer.
+ *   - All 13 integrations of an iteration (the trial point and its 12 neighbours) of all still-active problems are one launch;
+ *     one round = expansion, integration, LM step.  Problems are solved in chunks that bound the workspace.
+ *   states    n x S                 wrench   (F_e, L_e) rows with stride wrench_ld >= 6, or one row for all (wrench_ld == 0);
+ *                                            NULL = no tip wrench
+ *   dist      (f_e, l_e) rows with stride dist_ld >= 6, one row for all (dist_ld == 0), NULL = none
+ *   p, R, L, L_i, n_points          tr_fk_batch's outputs, of the integration at the final strains
+ *   converged n                     |e| <= residual_threshold at the final strains
+ *   vu0_out   n x 6 final (v0, u0); vuL_out n x 6: the strains (v, u) at the tip (TendonResult::v_f, u_f);
+ *   residual_out n: |e| at the final strains; iters_out n: LM steps taken;
+ *   fk_calls_out n: integrations of the solve (1 for the start, 13 per round after it; the launch that writes the outputs
+ *   is not counted); rounds_out: rounds run, a host pointer in both forms.
+ * Every output may be NULL.  A problem's result does not depend on the other problems of the call, their order or the chunking.
+ * Robots with retraction: TR_ERR_UNSUPPORTED. */
+int tr_fk_loaded_batch(tr_ctx *ctx, const tr_shoot_params *params, const double *states, int64_t n,
+                       const double *wrench, int64_t wrench_ld, const double *dist, int64_t dist_ld, const double *guess,
+                       double *p, double *R, double *L, double *L_i, uint8_t *converged, int32_t *n_points,
+                       double *vu0_out, double *vuL_out, double *residual_out, int32_t *iters_out, int32_t *fk_calls_out,
+                       int64_t *rounds_out);
+/* Device form: device arrays in tr_fk_batch_dev's layout (d_px[j*ld + i], d_R [9][P][ld], d_Li [N][ld]; ld >= n, a multiple of 64),
+ * host params / rounds_out.  d_px, d_py, d_pz, d_Li, d_converged feed tr_validate_shapes_dev unchanged.  It synchronises `stream`
+ * once per round to read the number of problems still active (4 bytes through pinned memory). */
+int tr_fk_loaded_batch_dev(tr_ctx *ctx, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
+                           const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess,
+                           double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L, double *d_Li, uint8_t *d_converged,
+                           int32_t *d_n_points, double *d_vu0_out, double *d_vuL_out, double *d_residual_out, int32_t *d_iters_out,
+                           int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
+
 /* ---- state validity: StateValidityChecker::isValid -------------------------------------- */
 
 /* Batched AbstractValidityChecker::isValid (motion-planning/AbstractValidityChecker.cpp:124-133)
@@ -691,6 +746,7 @@ int tr_edge_schedule_last(const tr_ctx *ctx, uint32_t stats[4]);
  *                                   provokes the overflow path)
  *   TENDON_HIP_EDGE_POOL=n          upper bound of the FK sample pool (tests: forces chunking / the overflow paths)
  *   TENDON_HIP_FB_CAP=n             columns of the fallback pass's point workspace (default: one resident round of waves)
+ *   TENDON_HIP_SHOOT_CHUNK=n        problems per chunk of tr_fk_loaded_batch* (tests: forces chunking; default: what 2^19 lanes hold)
  *   TENDON_HIP_RETRACT_SORT=n       retraction robots: batches of at least n configurations are ordered by backbone length
  *                                   (0 = never); TENDON_HIP_RETRACT_KBEGIN_OFF: no per-wave loop start in that order
  * Read per call (the tests switch between two paths inside one process; the switches of tr_roadmap_*: once, at the start of the call

@@ -63,6 +63,14 @@ struct TendonResult {               // tendon/TendonResult.h:17-40
   double L = 0.0;
   std::vector<double> L_i;
   bool converged = true;
+  // base and tip strains; filled by general_shape (u_i, v_i: the solved base strains)
+  std::array<double, 3> u_i{}, v_i{}, u_f{}, v_f{};
+};
+
+/// the arguments of TendonRobot::general_shape after the loads and the guess (tendon/TendonRobot.h:199-203)
+struct ShootOptions {
+  int max_iters = 100;
+  double mu_init = 0.1, stop_threshold_JT_err_inf = 1e-9, stop_threshold_Dp = 1e-4, finite_difference_delta = 1e-6;
 };
 
 class TendonRobot {                 // tendon/TendonRobot.h:52-355
@@ -159,6 +167,75 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
       res.converged = conv[i] != 0;
     }
     return out;
+  }
+
+  using V3 = std::array<double, 3>;
+
+  /// general_shape for n states in one call (tr_fk_loaded_batch): `wrench` holds (F_e, L_e) once (6 values) or per state (6 n);
+  /// `dist` holds (f_e, l_e) the same way, or is empty; `guess` holds n rows (v, u) or is empty = start from the unloaded solution.
+  /// Loads are in the base frame before the state's rotation.  iters / fk_calls (optional) receive the per-state counters.
+  std::vector<TendonResult> generalShapeBatch(const std::vector<double> &states, size_t n, const std::vector<double> &wrench,
+                                              const std::vector<double> &dist = {}, const std::vector<double> &guess = {},
+                                              const ShootOptions &opt = ShootOptions(), std::vector<int32_t> *iters = nullptr,
+                                              std::vector<int32_t> *fk_calls = nullptr) const {
+    tr_ctx *c = context();
+    const size_t S = state_size(), P = (size_t)tr_num_points(c), N = tendons.size();
+    if (states.size() != n * S) throw std::invalid_argument("State is not the right size");
+    if (wrench.size() != 6 && wrench.size() != 6 * n) throw std::invalid_argument("wrench: 6 values, or 6 per state");
+    if (!dist.empty() && dist.size() != 6 && dist.size() != 6 * n) throw std::invalid_argument("dist: empty, 6 values, or 6 per state");
+    if (!guess.empty() && guess.size() != 6 * n) throw std::invalid_argument("guess: empty, or 6 per state");
+    const tr_shoot_params prm{opt.max_iters, opt.mu_init, opt.stop_threshold_JT_err_inf, opt.stop_threshold_Dp, opt.finite_difference_delta};
+    std::vector<double> p(n * P * 3), R(n * P * 9), L(n), Li(n * N), vu0(6 * n), vuL(6 * n);
+    std::vector<uint8_t> conv(n);
+    std::vector<int32_t> np(n);
+    if (iters) iters->resize(n);
+    if (fk_calls) fk_calls->resize(n);
+    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error)
+    check(c, tr_fk_loaded_batch(c, &prm, states.data(), (int64_t)n, wrench.data(), wrench.size() == 6 ? 0 : 6,
+                                dist.empty() ? nullptr : dist.data(), dist.size() == 6 ? 0 : 6,
+                                guess.empty() ? nullptr : guess.data(), p.data(), R.data(), L.data(), Li.data(), conv.data(), np.data(),
+                                vu0.data(), vuL.data(), nullptr, iters ? iters->data() : nullptr, fk_calls ? fk_calls->data() : nullptr,
+                                nullptr));
+    const std::vector<double> tg = t_grid();
+    std::vector<TendonResult> out(n);
+    for (size_t i = 0; i < n; i++) {
+      TendonResult &res = out[i];
+      const size_t m = (size_t)np[i];
+      res.t.assign(tg.begin(), tg.begin() + m);
+      res.p.resize(m); res.R.resize(m);
+      for (size_t j = 0; j < m; j++) {
+        for (int k = 0; k < 3; k++) res.p[j][k] = p[(i * P + j) * 3 + k];
+        for (int k = 0; k < 9; k++) res.R[j][k] = R[(i * P + j) * 9 + k];
+      }
+      res.L = L[i];
+      res.L_i.assign(Li.begin() + i * N, Li.begin() + (i + 1) * N);
+      res.converged = conv[i] != 0;
+      for (int k = 0; k < 3; k++) {
+        res.v_i[k] = vu0[6 * i + k]; res.u_i[k] = vu0[6 * i + 3 + k];
+        res.v_f[k] = vuL[6 * i + k]; res.u_f[k] = vuL[6 * i + 3 + k];
+      }
+    }
+    return out;
+  }
+
+  /// TendonRobot::general_shape(state, f_e, l_e, F_e, L_e, u_guess, v_guess, max_iters, ...), TendonRobot.h:155-219, with two
+  /// differences: f_e, l_e are constant vectors (per unit length, base frame), not functions of (t, p); and without a guess the
+  /// shooting starts from the unloaded solution of the tensions, where the reference starts from the straight rod -- pass
+  /// u_guess = {0, 0, 0}, v_guess = {0, 0, 1} for that.  `verbose` is accepted and ignored.
+  TendonResult general_shape(const std::vector<double> &state, const V3 &f_e, const V3 &l_e, const V3 &F_e, const V3 &L_e,
+                             const std::optional<V3> &u_guess = std::nullopt, const std::optional<V3> &v_guess = std::nullopt,
+                             int max_iters = 100, double mu_init = 0.1, double stop_threshold_JT_err_inf = 1e-9,
+                             double stop_threshold_Dp = 1e-4, double finite_difference_delta = 1e-6, bool verbose = false) const {
+    (void)verbose;
+    if (state.size() != state_size()) throw std::invalid_argument("State is not the right size");
+    const std::vector<double> wrench{F_e[0], F_e[1], F_e[2], L_e[0], L_e[1], L_e[2]}, dist{f_e[0], f_e[1], f_e[2], l_e[0], l_e[1], l_e[2]};
+    std::vector<double> guess;
+    if (u_guess || v_guess) {
+      const V3 v = v_guess.value_or(V3{0.0, 0.0, 1.0}), u = u_guess.value_or(V3{0.0, 0.0, 0.0});
+      guess = {v[0], v[1], v[2], u[0], u[1], u[2]};
+    }
+    const ShootOptions opt{max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta};
+    return std::move(generalShapeBatch(state, 1, wrench, dist, guess, opt)[0]);
   }
 
   /// home_shape(0).L_i, TendonRobot.cpp:249-314

@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import (TendonHipError, InvalidArgument, OutOfRange, DomainError, LengthError, HipError, Unsupported,
                    build, LIB_PATH)
 from .engine import Engine, unpack_bits
-from .tendon import BackboneSpecs, TendonSpecs, TendonResult, TendonRobot
+from .tendon import BackboneSpecs, TendonSpecs, TendonResult, TendonRobot, PointForces
 from .collision import VoxelOctree
 from .motion_planning import (VoxelEnvironment, VoxelBackboneValidityChecker, VoxelValidityChecker, VoxelBackboneMotionValidator,
                               VoxelBackboneDiscreteMotionValidator, FunctionTimer, Environment, Problem)
@@ -21,7 +21,7 @@ from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan
 
 __all__ = [
     "TendonHipError", "InvalidArgument", "OutOfRange", "DomainError", "LengthError", "HipError", "Unsupported",
-    "build", "LIB_PATH", "Engine", "unpack_bits", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot",
+    "build", "LIB_PATH", "Engine", "unpack_bits", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot", "PointForces",
     "VoxelOctree", "VoxelEnvironment", "VoxelBackboneValidityChecker", "VoxelValidityChecker", "VoxelBackboneMotionValidator", "VoxelBackboneDiscreteMotionValidator", "Environment", "Problem",
     "FunctionTimer", "workloads", "distributed", "roadmap", "RoadmapBuilder", "VoxelCachedLazyPRM", "chained_plan", "tip_control",
 ]

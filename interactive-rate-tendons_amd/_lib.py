@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "tr_fk_tips", "tr_fk_tips_dev", "tr_tip_jacobian", "tr_tip_jacobian_dev", "tr_ik_batch", "tr_ik_batch_dev",
     "tr_roadmap_set_tips", "tr_roadmap_nearest_tips", "tr_roadmap_nearest_tips_dev", "tr_roadmap_ik_batch", "tr_roadmap_solve_tips",
     "tr_roadmap_tip_query_profile",
+    "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev",
 )
 
 
@@ -64,6 +65,11 @@ class TrSpaceParams(C.Structure):
 class TrIkParams(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("mu_init", C.c_double), ("stop_threshold_JT_err_inf", C.c_double),
                 ("stop_threshold_Dp", C.c_double), ("stop_threshold_err", C.c_double), ("finite_difference_delta", C.c_double)]
+
+
+class TrShootParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("mu_init", C.c_double), ("stop_threshold_JT_err_inf", C.c_double),
+                ("stop_threshold_Dp", C.c_double), ("finite_difference_delta", C.c_double)]
 
 
 class TrTipQueryParams(C.Structure):
@@ -119,8 +125,8 @@ OBJ_DIR = os.path.join(SRC_DIR, "_obj")
 
 def _units():
     """(object name, source, extra flags): the C ABI + K2..K6, the cache merge, and K1 once per
-    (tendon count, kernel: shared grid / retraction / fused with K2 / verdict-only / verdict-only with retraction / edge queue) so its
-    instantiations compile in parallel."""
+    (tendon count, kernel: shared grid / retraction / fused with K2 / verdict-only / verdict-only with retraction / edge queue /
+    loaded) so its instantiations compile in parallel."""
     fk_deps = ["fk_inst.hip", "fk_launch.hpp", "fk_kernel.hpp", "fk_retract_kernel.hpp", "fused_kernel.hpp", "verdict_kernel.hpp",
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
@@ -133,10 +139,11 @@ def _units():
          ("roadmap.o", "roadmap.hip", ["-pthread"], roadmap_deps + [HEADER]),
          ("sample.o", "sample.hip", [], ["sample.hip", "sample.hpp", "tr_types.hpp"])]
     q_deps = fk_deps + ["edge_queue_kernel.hpp", "edge_kernel.hpp"]
+    l_deps = fk_deps + ["fk_loaded_kernel.hpp"]
     for n in range(1, 9):
-        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q")):
+        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l")):
             u.append(("fk_%s%d.o" % (tag, n), "fk_inst.hip", ["-DTRK_INST_N=%d" % n, "-DTRK_INST_KIND=%d" % kind],
-                      q_deps if kind == 5 else fk_deps))
+                      q_deps if kind == 5 else (l_deps if kind == 6 else fk_deps)))
     return u
 
 
@@ -332,6 +339,9 @@ def lib():
     L.tr_tip_jacobian_dev.argtypes = [vp, vp, i64, C.c_double, vp, vp, vp]
     L.tr_ik_batch.argtypes = [vp, P(TrIkParams), dp, i64, dp, i64, dp, dp, dp, dp, dp, i32p, i32p, P(i64)]
     L.tr_ik_batch_dev.argtypes = [vp, P(TrIkParams), vp, i64, vp, i64, dp, dp, vp, vp, vp, vp, vp, P(i64), vp]
+    shp = P(TrShootParams)
+    L.tr_fk_loaded_batch.argtypes = [vp, shp, dp, i64, dp, i64, dp, i64, dp, dp, dp, dp, dp, P(C.c_uint8), i32p, dp, dp, dp, i32p, i32p, P(i64)]
+    L.tr_fk_loaded_batch_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     tqp = P(TrTipQueryParams)
     L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
     L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]

@@ -70,13 +70,20 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
   return y;
 }
 
+// What an external distributed load adds to the right-hand sides c and d of the strain equations.  The default adds nothing:
+// the unloaded kernels compile to the instructions they had before the policy existed (fk_loaded_kernel.hpp holds the other one).
+struct NoLoad {
+  __device__ __forceinline__ void operator()(double &, double &, double &, double &, double &, double &) const {}
+};
+
 // Right-hand side for the strain part of the state: (v', u') and the length rates.
 // route(j, r6) yields tendon j's routing {rx, ry, rdx, rdy, rddx, rddy} when the tendon loop reaches it
 // (a table row for the shared-grid kernel, an on-the-fly evaluation for the retraction kernel).
-template <int N, class Route>
+// load(cx, cy, cz, dx, dy, dz) takes R^T l_e from c and R^T f_e from d (tendon/tendon_deriv.cpp:331-332).
+template <int N, class Route, class Load = NoLoad>
 __device__ __forceinline__ void strain_rates_routed(const double v[3], const double u[3], const double (&tau)[N],
                                                     Route &&route, const RobotK &K,
-                                                    double dv[3], double du[3], double (&sdot)[N]) {
+                                                    double dv[3], double du[3], double (&sdot)[N], const Load &load = Load()) {
 #pragma clang fp contract(fast)
   // Sums over tendons, using A_i = c (pd pd^T - |pd|^2 I), c = -tau/|pd|^3, q = c pd, e = r x pd, g = c e:
   //   A = sum q pd^T - (sum c|pd|^2) I
@@ -145,12 +152,13 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
   //   u x (K_bt u) = (kb2 - kb0) u2 (u1, -u0, 0),   v x (K_se (v - e3)) = w (v1, -v0, 0),   w = ks2 (v2 - 1) - ks0 v2
   const double svx = K.ks0 * v[0], svy = K.ks0 * v[1], svz = K.ks2 * (v[2] - 1.0);
   const double dku = K.dkb * u[2], w = TRK_FMA(-K.ks0, v[2], svz);
-  const double cx = TRK_FMA(-u[1], dku, TRK_FMA(-v[1], w, -bx));
-  const double cy = TRK_FMA(u[0], dku, TRK_FMA(v[0], w, -by));
-  const double cz = -bz;
-  const double dx = TRK_FMA(u[2], svy, TRK_FMA(-u[1], svz, -ax));
-  const double dy = TRK_FMA(u[0], svz, TRK_FMA(-u[2], svx, -ay));
-  const double dz = TRK_FMA(u[1], svx, TRK_FMA(-u[0], svy, -az));
+  double cx = TRK_FMA(-u[1], dku, TRK_FMA(-v[1], w, -bx));
+  double cy = TRK_FMA(u[0], dku, TRK_FMA(v[0], w, -by));
+  double cz = -bz;
+  double dx = TRK_FMA(u[2], svy, TRK_FMA(-u[1], svz, -ax));
+  double dy = TRK_FMA(u[0], svz, TRK_FMA(-u[2], svx, -ay));
+  double dz = TRK_FMA(u[1], svx, TRK_FMA(-u[0], svy, -az));
+  load(cx, cy, cz, dx, dy, dz);
   // M11 = K_se + A - Z I (symmetric): the leading block of the 6 x 6 system solved below
   const double m00 = Axx - Z, m01 = Axy, m02 = Axz, m11 = Ayy - Z, m12 = Ayz, m22 = Azz - Z;
 #ifndef TRK_SOLVE_SCHUR
@@ -248,14 +256,14 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
 }
 
 // ri: wave-uniform pointer to N x 6 doubles {rx, ry, rdx, rdy, rddx, rddy} per tendon.
-template <int N>
+template <int N, class Load = NoLoad>
 __device__ __forceinline__ void strain_rates(const double v[3], const double u[3], const double (&tau)[N],
                                              const double *__restrict__ ri, const RobotK &K,
-                                             double dv[3], double du[3], double (&sdot)[N]) {
+                                             double dv[3], double du[3], double (&sdot)[N], const Load &load = Load()) {
   strain_rates_routed<N>(v, u, tau, [&](int j, double (&r6)[6]) {
 #pragma unroll
     for (int q = 0; q < 6; q++) r6[q] = ri[6 * j + q];
-  }, K, dv, du, sdot);
+  }, K, dv, du, sdot, load);
 }
 
 // solve_initial_bending + base residual.  Written without contraction and with IEEE div/sqrt so

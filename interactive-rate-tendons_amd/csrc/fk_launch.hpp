@@ -22,6 +22,19 @@ struct FkLaunch {
   const int32_t *d_wave_k_begin = nullptr;      // stored-point retraction kernel: per wave of the order d_perm, the first step of its loop
 };
 
+// Inputs of the loaded FK kernel (fk_loaded_kernel.hpp) beyond FkLaunch: lane t of the launch integrates problem
+// list[t / Q] (list null: t / Q) of the chunk from the base strains vu[t]
+struct LoadedIn {
+  const double *wrench; int64_t wrench_ld;     // the tip wrench (F_e, L_e) every problem must meet: row i wrench_ld (0: one row for all)
+  const double *dist; int64_t dist_ld;         // the distributed load (f_e, l_e) per unit length, base frame; null: none
+  const double *vu;                            // [lanes][6] base strains (v0, u0)
+  const int32_t *list;
+  int32_t Q;                                   // lanes per problem: 13 in a round of the shooting, 1 otherwise
+  const double *tip_route;                     // [N][6] routing at s = L
+  double *res; int64_t ldr;                    // [6][ldr] tip residual of every lane (structure of arrays), or null
+  double *vu_tip;                              // [lanes][6] strains (v, u) at the tip, or null
+};
+
 struct FusedSweepArgs;
 struct VerdictArgs;
 struct EdgeQueueArgs;
@@ -47,7 +60,13 @@ template <int N> void launch_fk_edge_queue(const FkLaunch &a, const VerdictArgs 
 // workgroups of that kernel one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0 on error)
 template <int N> int fk_edge_queue_waves_per_cu(bool rotation, size_t lds);
 
+// the loaded FK (fk_loaded_kernel.hpp): a.n lanes, a.d_states the problems' states, a.out the outputs (column = lane)
+template <int N> void launch_fk_loaded(const FkLaunch &a, const LoadedIn &in);
+// start strains of a.n problems: `guess` rows (v, u), or (guess null) the unloaded solution of the problem's tensions
+template <int N> void launch_shoot_start(const FkLaunch &a, const double *guess, double *vu);
+
 #define TRK_DECL_FK(N) template <> void launch_fk_uniform<N>(const FkLaunch &); template <> void launch_fk_retract<N>(const FkLaunch &); \
+  template <> void launch_fk_loaded<N>(const FkLaunch &, const LoadedIn &); template <> void launch_shoot_start<N>(const FkLaunch &, const double *, double *); \
   template <> void launch_fk_sweep_fused<N>(const FkLaunch &, const FusedSweepArgs *, size_t); \
   template <> void launch_fk_sweep_fused_list<N>(const FkLaunch &, const FusedSweepArgs *, size_t, const int32_t *, const uint32_t *); \
   template <> void launch_fk_verdict<N>(const FkLaunch &, const VerdictArgs *, size_t, bool, bool); \

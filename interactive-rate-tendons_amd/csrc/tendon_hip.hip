@@ -40,10 +40,12 @@
 #include "env_kernel.hpp"
 #include "sample.hpp"
 #include "ik_kernel.hpp"
+#include "fk_loaded_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
 struct tr_ctx;
 namespace { void ik_release(tr_ctx *c); }   // ik_host.inc
+namespace { void shoot_release(tr_ctx *c); }   // loaded_host.inc
 
 namespace {
 
@@ -248,6 +250,24 @@ struct tr_ctx {
     double *io_s = nullptr, *io_3 = nullptr, *io_e = nullptr;       // staging of the host-array forms
     int32_t *io_i = nullptr, *io_c = nullptr;
   } ik;
+  // loaded FK (loaded_host.inc): the lanes of one round and the per-problem state of one chunk of problems, grow-only; io_*: the
+  // staging of the host-array form (its own, smaller chunk)
+  struct ShootDev {
+    int64_t probs = 0, lanes = 0;
+    double *xs = nullptr, *res = nullptr;                           // [lanes][6], [6][lanes]
+    double *p = nullptr, *pn = nullptr, *e = nullptr, *J = nullptr; // [probs][6 | 6 | 6 | 36]
+    double *err2 = nullptr, *mu = nullptr, *nu = nullptr;
+    int32_t *iters = nullptr, *calls = nullptr, *list[2] = {nullptr, nullptr};
+    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    double *tip_route = nullptr, *zero6 = nullptr;                  // [N][6] routing at s = L; a zero wrench
+    int64_t io_probs = 0, io_R_probs = 0;
+    double *io_states = nullptr, *io_w = nullptr, *io_d = nullptr, *io_g = nullptr;
+    double *io_px = nullptr, *io_py = nullptr, *io_pz = nullptr, *io_R = nullptr, *io_L = nullptr, *io_Li = nullptr;
+    double *io_vu = nullptr, *io_vuL = nullptr, *io_e = nullptr;
+    int32_t *io_np = nullptr, *io_it = nullptr, *io_fc = nullptr;
+    uint8_t *io_conv = nullptr;
+  } shoot;
+  int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
   bool profiling = false;
   std::vector<EventPair> events[TR_PROFILE_SLOTS];
@@ -959,6 +979,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
     const long long v = std::atoll(e);
     if (v >= 256 && v <= (1ll << 24)) c->edge_pool_max = c->edge_slots_max = (int64_t)round_up(v, 64);
   }
+  if (const char *e = std::getenv("TENDON_HIP_SHOOT_CHUNK")) { const long long v = std::atoll(e); if (v >= 1 && v <= (1ll << 20)) c->shoot_chunk = (int64_t)v; }
   if (hipSetDevice(device) != hipSuccess) { delete c; return fail(nullptr, TR_ERR_HIP, "hipSetDevice failed"); }
   {
     int cus = 0;
@@ -1108,6 +1129,7 @@ void tr_destroy(tr_ctx *c) {
     trk::merge_free(ro.ms);
   }
   ik_release(c);
+  shoot_release(c);
   delete c;
 }
 
@@ -2214,3 +2236,4 @@ int tr_profile_end(tr_ctx *c) {
 #include "edge_indexed_host.inc"
 #include "sample_host.inc"
 #include "ik_host.inc"
+#include "loaded_host.inc"

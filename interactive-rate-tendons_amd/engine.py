@@ -253,6 +253,102 @@ class Engine:
                                                     C.byref(rounds), self._stream_ptr(stream)))
         return int(rounds.value)
 
+    # ---- loaded FK (tr_fk_loaded_batch, include/tendon_hip.h): TendonRobot::general_shape for a batch ------------------------------
+    @staticmethod
+    def _shoot_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta):
+        return L.TrShootParams(int(max_iters), float(mu_init), float(stop_threshold_JT_err_inf), float(stop_threshold_Dp),
+                               float(finite_difference_delta))
+
+    @staticmethod
+    def _load_rows(a, n, name):
+        """(array, ld) of an optional (6,) or (n, 6) load argument."""
+        if a is None:
+            return None, 0
+        a = _f64(a)
+        if a.shape == (6,):
+            return a, 0
+        if a.shape == (n, 6):
+            return a, 6
+        raise L.InvalidArgument("%s must be (6,) or (n, 6)" % name)
+
+    def fk_loaded_batch(self, states, wrench=None, dist=None, guess=None, want_R=False, max_iters=100, mu_init=0.1,
+                        stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6):
+        """Batched general_shape on the device: wrench = (F_e, L_e) and dist = (f_e, l_e) are (6,) for all states or (n, 6), in the
+        robot's base frame before the state's rotation (None: zero); guess (n, 6) rows (v, u) or None = the unloaded solution.
+        Returns dict(p, R, L, L_i, converged, n_points, vu0, vuL (tip strains), residual, iters, num_fk_calls, rounds)."""
+        st = self._states(states)
+        n, P, N = st.shape[0], self.num_points, self.n_tendons
+        w, wld = self._load_rows(wrench, n, "wrench")
+        d, dld = self._load_rows(dist, n, "dist")
+        g = None
+        if guess is not None:
+            g = _f64(guess)
+            if g.shape != (n, 6):
+                raise L.InvalidArgument("guess must be (n, 6)")
+        prm = self._shoot_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta)
+        p = np.empty((n, P, 3))
+        R = np.empty((n, P, 9)) if want_R else None
+        Lb, Li = np.empty(n), np.empty((n, N))
+        conv = np.empty(n, dtype=np.uint8)
+        npts = np.empty(n, dtype=np.int32)
+        vu0, vuL, res = np.empty((n, 6)), np.empty((n, 6)), np.empty(n)
+        iters, calls = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        rounds = C.c_int64(0)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        opt = lambda a: _dp(a) if a is not None else None
+        L.check(self._ctx, self.lib.tr_fk_loaded_batch(self._ctx, C.byref(prm), _dp(st), n, opt(w), wld, opt(d), dld, opt(g), _dp(p), opt(R),
+                                                       _dp(Lb), _dp(Li), conv.ctypes.data_as(C.POINTER(C.c_uint8)), i32(npts), _dp(vu0),
+                                                       _dp(vuL), _dp(res), i32(iters), i32(calls), C.byref(rounds)))
+        return dict(p=p, R=R, L=Lb, L_i=Li, converged=conv.astype(bool), n_points=npts, vu0=vu0, vuL=vuL, residual=res, iters=iters,
+                    num_fk_calls=calls, rounds=int(rounds.value))
+
+    def fk_loaded_batch_dev(self, d_states, n, ld, d_px, d_py, d_pz, d_wrench=None, wrench_ld=6, d_dist=None, dist_ld=6, d_guess=None,
+                            d_L=None, d_Li=None, d_conv=None, d_R=None, d_npts=None, d_vu0=None, d_vuL=None, d_residual=None, d_iters=None,
+                            d_fk_calls=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
+                            finite_difference_delta=1e-6, stream=None):
+        """tr_fk_loaded_batch_dev: device tensors in tr_fk_batch_dev's layout (wrench_ld / dist_ld = 0: one row for all); d_px, d_py,
+        d_pz, d_Li, d_conv feed validate_shapes_dev.  Returns the number of rounds."""
+        torch = _torch()
+        P = self.num_points
+        f64 = torch.float64
+        opt = lambda t, dt, m, nm: self._check_dev(t, dt, m, nm) if t is not None else None
+        rows = lambda rl: 6 if rl == 0 else (n - 1) * rl + 6
+        prm = self._shoot_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta)
+        rounds = C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_fk_loaded_batch_dev(
+            self._ctx, C.byref(prm), self._check_dev(d_states, f64, n * self.state_size, "d_states"), int(n), int(ld),
+            opt(d_wrench, f64, rows(wrench_ld), "d_wrench"), int(wrench_ld), opt(d_dist, f64, rows(dist_ld), "d_dist"), int(dist_ld),
+            opt(d_guess, f64, 6 * n, "d_guess"), opt(d_px, f64, P * ld, "d_px"), opt(d_py, f64, P * ld, "d_py"),
+            opt(d_pz, f64, P * ld, "d_pz"), opt(d_R, f64, 9 * P * ld, "d_R"), opt(d_L, f64, n, "d_L"),
+            opt(d_Li, f64, self.n_tendons * ld, "d_Li"), opt(d_conv, torch.uint8, n, "d_conv"), opt(d_npts, torch.int32, n, "d_npts"),
+            opt(d_vu0, f64, 6 * n, "d_vu0"), opt(d_vuL, f64, 6 * n, "d_vuL"), opt(d_residual, f64, n, "d_residual"), opt(d_iters, torch.int32, n, "d_iters"),
+            opt(d_fk_calls, torch.int32, n, "d_fk_calls"), C.byref(rounds), self._stream_ptr(stream)))
+        return int(rounds.value)
+
+    def validate_loaded(self, states, wrench=None, dist=None, guess=None, check_voxels=True, **shoot):
+        """isValid of the LOADED shapes: fk_loaded_batch_dev into validate_shapes_dev (converged = the shooting's, tendon-length
+        limits, self-collision, the backbone or sphere sweep against the grid).  Returns dict(valid, bits, flags)."""
+        torch = _torch()
+        st = self._states(states)
+        n, P, N = st.shape[0], self.num_points, self.n_tendons
+        w, wld = self._load_rows(wrench, n, "wrench")
+        d, dld = self._load_rows(dist, n, "dist")
+        dev = "cuda:%d" % self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
+        ld = (n + 63) // 64 * 64
+        planes = torch.empty((3, P, ld), dtype=torch.float64, device=dev)
+        Li = torch.empty((N, ld), dtype=torch.float64, device=dev)
+        conv = torch.empty(n, dtype=torch.uint8, device=dev)
+        bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=dev)
+        flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+        g = None if guess is None else _f64(guess).reshape(n, 6)
+        self.fk_loaded_batch_dev(up(st), n, ld, planes[0], planes[1], planes[2], d_wrench=up(w), wrench_ld=wld, d_dist=up(d), dist_ld=dld,
+                                 d_guess=up(g), d_Li=Li, d_conv=conv, **shoot)
+        self.validate_shapes_dev(n, ld, planes[0], planes[1], planes[2], Li, conv, bits, flags, check_voxels=check_voxels)
+        torch.cuda.synchronize(self.device)
+        words = bits.cpu().numpy().view(np.uint64)
+        return dict(valid=unpack_bits(words, n), bits=words, flags=flags.cpu().numpy())
+
     def validate_batch(self, states, want_tips=True, want_flags=True):
         st = self._states(states)
         n = st.shape[0]

@@ -57,6 +57,23 @@ class TendonResult:                        # tendon/TendonResult.h:17-40
     L: float
     L_i: np.ndarray
     converged: bool = True
+    u_i: np.ndarray = None                 # base and tip strains (general_shape fills them; u_i, v_i: the solved (u0, v0))
+    v_i: np.ndarray = None
+    u_f: np.ndarray = None
+    v_f: np.ndarray = None
+
+
+@dataclass
+class PointForces:                         # tendon/TendonRobot.h:27-50
+    F_e: np.ndarray
+    L_e: np.ndarray
+    F_t: np.ndarray
+    L_t: np.ndarray
+    n: np.ndarray
+    m: np.ndarray
+
+    def residual(self, F_e=(0.0, 0.0, 0.0), L_e=(0.0, 0.0, 0.0)):
+        return float(np.sqrt(((self.F_e - np.asarray(F_e)) ** 2).sum() + ((self.L_e - np.asarray(L_e)) ** 2).sum()))
 
 
 class TendonRobot:
@@ -136,6 +153,91 @@ class TendonRobot:
         t = self._t(s_start) if n > 1 else np.array([min(s_start, self.specs.L)])
         return TendonResult(t=t[:n], p=out["p"][0, :n], R=R, L=float(out["L"][0]),
                             L_i=out["L_i"][0], converged=bool(out["converged"][0]))
+
+    def general_shape(self, state, f_e=(0.0, 0.0, 0.0), l_e=(0.0, 0.0, 0.0), F_e=(0.0, 0.0, 0.0), L_e=(0.0, 0.0, 0.0), u_guess=None,
+                      v_guess=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
+                      finite_difference_delta=1e-6, device=0) -> TendonResult:          # TendonRobot.h:155-219
+        """The shape under a tip force / moment F_e, L_e and a distributed force / moment f_e, l_e per unit length, in the base frame
+        before the state's rotation (the reference rotates the solved shape).  f_e, l_e are CONSTANT vectors (gravity); the
+        reference's functions of (t, p) are not offered.  Without u_guess / v_guess the shooting starts from the unloaded solution of the
+        tensions, not from the reference's straight rod (v, u) = (e3, 0): pass u_guess=(0, 0, 0), v_guess=(0, 0, 1) for that."""
+        state = np.asarray(state, dtype=np.float64).reshape(-1)
+        if state.size != self.state_size():
+            raise L.InvalidArgument("State is not the right size")
+        guess = None
+        if u_guess is not None or v_guess is not None:
+            guess = np.concatenate([np.asarray((0.0, 0.0, 1.0) if v_guess is None else v_guess, float).reshape(3),
+                                    np.asarray((0.0, 0.0, 0.0) if u_guess is None else u_guess, float).reshape(3)])[None]
+        out = self.general_shape_batch(state[None], f_e, l_e, F_e, L_e, guess=guess, want_R=True, max_iters=max_iters, mu_init=mu_init,
+                                       stop_threshold_JT_err_inf=stop_threshold_JT_err_inf, stop_threshold_Dp=stop_threshold_Dp,
+                                       finite_difference_delta=finite_difference_delta, device=device)
+        n = int(out["n_points"][0])
+        R = out["R"][0, :n].reshape(n, 3, 3).transpose(0, 2, 1)
+        return TendonResult(t=self._t(0.0)[:n], p=out["p"][0, :n], R=R, L=float(out["L"][0]), L_i=out["L_i"][0],
+                            converged=bool(out["converged"][0]), v_i=out["vu0"][0, :3].copy(), u_i=out["vu0"][0, 3:].copy(),
+                            v_f=out["vuL"][0, :3].copy(), u_f=out["vuL"][0, 3:].copy())
+
+    def general_shape_batch(self, states, f_e=None, l_e=None, F_e=None, L_e=None, guess=None, want_R=False, device=0, **shoot):
+        """general_shape for a batch: every load is (3,) for all states or (n, 3) (None: zero); guess (n, 6) rows (v, u) or None.
+        Returns Engine.fk_loaded_batch's dict."""
+        st = np.atleast_2d(np.asarray(states, dtype=np.float64))
+        n = st.shape[0]
+
+        def pair(a, b):
+            if a is None and b is None:
+                return None
+            z = np.zeros(3)
+            a, b = np.asarray(z if a is None else a, float), np.asarray(z if b is None else b, float)
+            if a.ndim == 1 and b.ndim == 1:
+                return np.concatenate([a, b])
+            return np.concatenate([np.broadcast_to(a, (n, 3)), np.broadcast_to(b, (n, 3))], axis=1)
+
+        return self.engine(device).fk_loaded_batch(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), guess=guess, want_R=want_R, **shoot)
+
+    def _stiffness(self):
+        s = self.specs
+        I = 0.25 * np.pi * (s.ro ** 4 - s.ri ** 4)
+        Ar = np.pi * (s.ro ** 2 - s.ri ** 2)
+        G = s.E / (2 * (1 + s.nu))
+        return np.diag([G * Ar, G * Ar, s.E * Ar]), np.diag([s.E * I, s.E * I, 2 * I * G])
+
+    def _routing(self, t):
+        """r, r' of every tendon at arc length t (get_r_info.cpp:105-144), (N, 3) each."""
+        r, rd = np.zeros((len(self.tendons), 3)), np.zeros((len(self.tendons), 3))
+        for i, td in enumerate(self.tendons):
+            Cp, Dp = np.polynomial.Polynomial(td.C), np.polynomial.Polynomial(td.D)
+            th, thd, rho, rhod = Cp(t), Cp.deriv()(t), Dp(t), Dp.deriv()(t)
+            r[i] = [rho * np.sin(th), rho * np.cos(th), 0.0]
+            rd[i] = [rhod * np.sin(th) + rho * np.cos(th) * thd, rhod * np.cos(th) - rho * np.sin(th) * thd, 0.0]
+        return r, rd
+
+    def _point_forces(self, tau, R, u, v, t):
+        """PointForces::calc_point_forces (TendonRobot.cpp:188-217) on the host."""
+        tau = np.asarray(tau, float).reshape(-1)[:len(self.tendons)]
+        Kse, Kbt = self._stiffness()
+        R, u, v = np.asarray(R, float), np.asarray(u, float), np.asarray(v, float)
+        r, rd = self._routing(t)
+        n = R @ Kse @ (v - np.array([0.0, 0.0, 1.0]))
+        m = R @ Kbt @ u
+        F_t, L_t = np.zeros(3), np.zeros(3)
+        for i in range(len(self.tendons)):
+            pd = R @ (np.cross(u, r[i]) + rd[i] + v)
+            F_ti = -tau[i] * pd / np.linalg.norm(pd)
+            F_t += F_ti
+            L_t += np.cross(R @ r[i], F_ti)
+        return PointForces(F_e=n - F_t, L_e=m - L_t, F_t=F_t, L_t=L_t, n=n, m=m)
+
+    def tip_forces(self, tau, result):                          # TendonRobot.h:298-299
+        """Forces at the tip of a general_shape result (its v_f, u_f are the strains there), in the frame of result.R."""
+        if result.u_f is None or result.v_f is None:
+            raise L.InvalidArgument("the result carries no tip strains (general_shape fills them)")
+        return self._point_forces(tau, result.R[-1], result.u_f, result.v_f, result.t[-1])
+
+    def base_forces(self, tau, result):                         # TendonRobot.h:305-306
+        """Forces at the base of a general_shape result (its v_i, u_i are the solved base strains)."""
+        if result.u_i is None or result.v_i is None:
+            raise L.InvalidArgument("the result carries no base strains (general_shape fills them)")
+        return self._point_forces(tau, result.R[0], result.u_i, result.v_i, result.t[0])
 
     def forward_kinematics(self, state, device=0):              # TendonRobot.h:68-72
         return self.shape(state, device).p
