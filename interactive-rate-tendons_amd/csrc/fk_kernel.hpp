@@ -89,12 +89,12 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
   //   A = sum q pd^T - (sum c|pd|^2) I
   //   B = sum rhat A_i   = sum g pd^T - sum c|pd|^2 rhat
   //   H = -sum B_i rhat  = sum g e^T  + sum c|pd|^2 rhat^2
-  //   a = sum q pd^T w - c|pd|^2 w,   b = sum r x a_i,   w = u x (pd + r') + r''
+  //   a = sum A_i w,   b = sum r x a_i,   w = u x (pd + r') + r''
   // The diagonals start at the stiffnesses (the first FMA of each chain takes the constant as its addend), and the rhat^2
-  // terms, rhat^2 = [[-ry^2, rx ry, 0],[rx ry, -rx^2, 0],[0,0,-(rx^2+ry^2)]], go into H tendon by tendon: the tail below
-  // adds nothing to K_se + A or K_bt + H but -Z on the first.
+  // and rhat terms go into H and B tendon by tendon, rhat^2 = [[-ry^2, rx ry, 0],[rx ry, -rx^2, 0],[0,0,-(rx^2+ry^2)]],
+  // rhat = [[0,0,ry],[0,0,-rx],[-ry,rx,0]]: the tail below adds nothing to K_se + A, B or K_bt + H but -Z on two diagonal entries.
   double Axx = K.ks0, Axy = 0, Axz = 0, Ayy = K.ks0, Ayz = 0, Azz = K.ks2, Z = 0;
-  double B00 = 0, B01 = 0, B02 = 0, B10 = 0, B11 = 0, B12 = 0, B20 = 0, B21 = 0, B22 = 0, Q1 = 0, Q2 = 0;
+  double B00 = 0, B01 = 0, B02 = 0, B10 = 0, B11 = 0, B12 = 0, B20 = 0, B21 = 0, B22 = 0;
   double Hxx = K.kb0, Hxy = 0, Hxz = 0, Hyy = K.kb0, Hyz = 0, Hzz = K.kb2;
   double ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
 #pragma unroll
@@ -108,20 +108,22 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double pdx = (v[0] + rdx) - u[2] * ry;
     const double pdy = (v[1] + rdy) + u[2] * rx;
     const double pdz = __builtin_fma(u[0], ry, __builtin_fma(-u[1], rx, v[2]));
-    const double sxy = pdx * pdx + pdy * pdy, s2 = sxy + pdz * pdz;
+    // (sums of products are FMA chains written out, here and below: left to contraction, the compiler picks per kernel which
+    // product goes inside the FMA, and the kernels that hold this body differ in the last bit)
+    const double sxy = __builtin_fma(pdy, pdy, pdx * pdx), s2 = __builtin_fma(pdz, pdz, sxy);
     const double rs = fast_rsqrt(s2);
     sdot[j] = s2 * rs;
     // c = -tau / |pd|^3 and c |pd|^2 = -tau / |pd| from the same reciprocal root (one multiply fewer than c * s2)
     const double cs2 = -tau[j] * rs;
-    const double c = cs2 * (rs * rs);
+    const double rs2 = rs * rs, c = cs2 * rs2;
     const double qx = c * pdx, qy = c * pdy, qz = c * pdz;
-    Axx += qx * pdx; Axy += qx * pdy; Axz += qx * pdz; Ayy += qy * pdy; Ayz += qy * pdz; Azz += qz * pdz;
+    Axx += qx * pdx; Axy += qx * pdy; Axz += qx * pdz; Ayy += qy * pdy; Ayz += qy * pdz;
     Z += cs2;
     // e = r x pd = (ry pdz, -rx pdz, ez), g = c e  (r_z = 0)
-    const double ez = rx * pdy - ry * pdx;
+    const double ez = __builtin_fma(rx, pdy, -(ry * pdx));
     const double gx = ry * qz, gy = -rx * qz, gz = c * ez;
-    B00 += gx * pdx; B01 += gx * pdy; B02 += gx * pdz;
-    B10 += gy * pdx; B11 += gy * pdy; B12 += gy * pdz;
+    B00 += gx * pdx; B01 += gx * pdy;
+    B10 += gy * pdx; B11 += gy * pdy;
     B20 += gz * pdx; B21 += gz * pdy; B22 += gz * pdz;
     Hxz += gx * ez; Hyz += gy * ez; Hzz += gz * ez;
     // The x-y block of g e^T is c pdz^2 (ry^2, -rx ry, rx^2) and that of c|pd|^2 rhat^2 is c|pd|^2 (-ry^2, rx ry, -rx^2): together
@@ -130,23 +132,33 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double mxy = c * sxy, mx = mxy * rx, my = mxy * ry;
     Hxx -= my * ry; Hxy += mx * ry; Hyy -= mx * rx;
     const double t1 = cs2 * rx, t2 = cs2 * ry;
-    Q1 += t1; Q2 += t2;
     Hzz -= t1 * rx; Hzz -= t2 * ry;
+    // The same difference, c pdz^2 - c|pd|^2 = -mxy, is all of the z-z entry of A_i, and times (ry, -rx) all of the third column
+    // of the first two rows of B_i (g pd^T gives (ry, -rx) c pdz^2, the rhat term (ry, -rx) (-c|pd|^2)); the third row of B_i takes
+    // its rhat term (t2, -t1, 0) here too.  These five are sums of products that exist already: plain adds (contracted, each
+    // would form its product a second time inside an FMA), where three FMAs and the two sums of t1 and t2 were, and five adds
+    // in the tail of every stage.
+    {
+#pragma clang fp contract(off)
+      Azz -= mxy; B02 -= my; B12 += mx; B20 += t2; B21 -= t1;
+    }
     // w = u x (pd + r') + r''
     const double hx = pdx + rdx, hy = pdy + rdy, hz = pdz;
     const double wx = __builtin_fma(u[1], hz, __builtin_fma(-u[2], hy, rddx));
     const double wy = __builtin_fma(u[2], hx, __builtin_fma(-u[0], hz, rddy));
-    const double wz = u[0] * hy - u[1] * hx;
-    const double pw = pdx * wx + pdy * wy + pdz * wz;
-    const double aix = qx * pw - cs2 * wx, aiy = qy * pw - cs2 * wy, aiz = qz * pw - cs2 * wz;
-    ax += aix; ay += aiy; az += aiz;
-    bx += ry * aiz; by -= rx * aiz; bz += rx * aiy - ry * aix;
+    const double wz = __builtin_fma(u[0], hy, -(u[1] * hx));
+    const double pw = __builtin_fma(pdz, wz, __builtin_fma(pdy, wy, pdx * wx));
+    // a_i = A_i w = c (pd (pd.w) - |pd|^2 w) = cs2 p,  p = pd kappa - w,  kappa = (pd.w) / |pd|^2: minus the part of w orthogonal
+    // to pd, scaled once.  p is formed per tendon, a_i never: a takes cs2 p, and b = sum r x a_i takes (t1, t2, 0) x p with the
+    // t1 = cs2 rx, t2 = cs2 ry of the rhat terms above -- 11 instructions where q (pd.w) - cs2 w, its sum and its cross product took 13.
+    const double kp = pw * rs2;
+    const double px = __builtin_fma(pdx, kp, -wx), py = __builtin_fma(pdy, kp, -wy), pz = __builtin_fma(pdz, kp, -wz);
+    ax = __builtin_fma(cs2, px, ax); ay = __builtin_fma(cs2, py, ay); az = __builtin_fma(cs2, pz, az);
+    bx = __builtin_fma(t2, pz, bx); by = __builtin_fma(-t1, pz, by); bz = __builtin_fma(t1, py, __builtin_fma(-t2, px, bz));
   }
   // The tail below is written as explicit FMA chains: without re-association the compiler keeps the a - (b*c + d*e)
   // shapes as written and spends an extra add / negate on each (~90 instructions per RK4 step).
 #define TRK_FMA __builtin_fma
-  // - sum c|pd|^2 rhat, rhat = [[0,0,ry],[0,0,-rx],[-ry,rx,0]]
-  B02 -= Q2; B12 += Q1; B20 += Q2; B21 -= Q1;
   // c = -u x (K_bt u) - v x (K_se (v - e3)) - b ;  d = -u x (K_se (v - e3)) - a.  With K_bt = diag(kb0, kb0, kb2) and
   // K_se = diag(ks0, ks0, ks2) -- all RobotK can hold -- the two cross products of c lose their z component and share a factor:
   //   u x (K_bt u) = (kb2 - kb0) u2 (u1, -u0, 0),   v x (K_se (v - e3)) = w (v1, -v0, 0),   w = ks2 (v2 - 1) - ks0 v2
@@ -159,8 +171,8 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
   double dy = TRK_FMA(u[0], svz, TRK_FMA(-u[2], svx, -ay));
   double dz = TRK_FMA(u[1], svx, TRK_FMA(-u[0], svy, -az));
   load(cx, cy, cz, dx, dy, dz);
-  // M11 = K_se + A - Z I (symmetric): the leading block of the 6 x 6 system solved below
-  const double m00 = Axx - Z, m01 = Axy, m02 = Axz, m11 = Ayy - Z, m12 = Ayz, m22 = Azz - Z;
+  // M11 = K_se + A - Z I (symmetric): the leading block of the 6 x 6 system solved below (its z-z entry is complete: -mxy above)
+  const double m00 = Axx - Z, m01 = Axy, m02 = Axz, m11 = Ayy - Z, m12 = Ayz, m22 = Azz;
 #ifndef TRK_SOLVE_SCHUR
   // The symmetric 6 x 6 system [[M11, B^T], [B, K_bt + H]] [v'; u'] = [d; c] by an unrolled L D L^T factorisation without pivoting:
   // 35 FMAs, 15 products and six reciprocals to factor, 36 operations for the two triangular solves (181 flops, ~105 instructions).
@@ -362,9 +374,9 @@ __device__ __forceinline__ void frame_rate(int st, const double (&sR)[9], const 
   for (int r = 0; r < 3; r++) {
     const double r0 = sR[0 + r], r1 = sR[3 + r], r2 = sR[6 + r];
     if (st < 3) {
-      dR[0 + r] = r1 * su[2] - r2 * su[1];
-      dR[3 + r] = r2 * su[0] - r0 * su[2];
-      dR[6 + r] = r0 * su[1] - r1 * su[0];
+      dR[0 + r] = __builtin_fma(r1, su[2], -(r2 * su[1]));
+      dR[3 + r] = __builtin_fma(r2, su[0], -(r0 * su[2]));
+      dR[6 + r] = __builtin_fma(r0, su[1], -(r1 * su[0]));
 #pragma unroll
       for (int c = 0; c < 9; c += 3) aR[c + r] = (st == 0) ? dR[c + r] : __builtin_fma(2.0, dR[c + r], aR[c + r]);
     } else {
@@ -408,7 +420,7 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
     strain_rates_routed<N>(sv, su, tau, [&](int j, double (&r6)[6]) { route(ts, j, r6); }, K, dv, du, sd);
     position_quadrature(st, sR, sv, b1, qs, qm, p);
     {
-      const double v2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
+      const double v2 = __builtin_fma(sv[2], sv[2], __builtin_fma(sv[1], sv[1], sv[0] * sv[0]));
       Lb += bw * (v2 * fast_rsqrt(v2));
     }
 #pragma unroll
@@ -553,7 +565,7 @@ __device__ __forceinline__ void fk_uniform_body(
       // quadratures: p' = R v, L' = |v|, L_i' = |pd_i|
       position_quadrature(st, sR, sv, b1, qs, qm, p);
       if (WANT_L && out.L) {                               // wave-uniform
-        const double v2 = sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2];
+        const double v2 = __builtin_fma(sv[2], sv[2], __builtin_fma(sv[1], sv[1], sv[0] * sv[0]));
         Lb += bw * (v2 * fast_rsqrt(v2));
       }
       if constexpr (kLiLds) {

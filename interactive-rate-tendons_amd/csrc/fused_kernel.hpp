@@ -26,6 +26,24 @@ namespace trk {
 #define TRK_FUSED_TWO_WAVE_MAXN 5
 #endif
 
+// The kernel-argument block of the two kernels below, as the launch lays it out (every argument at its natural alignment;
+// fk_sweep_fused_list's two further pointers follow).  What the sweep behind the RK4 loop needs of it -- the robot's length
+// limits and radius, n, ld -- is re-read from there through a pointer the optimiser cannot trace back to the arguments (as
+// PointSweep::args() re-reads its block), so none of it is kept in SGPRs, or spilled to VGPR lanes, across the loop.
+struct FusedKernargs {
+  const double *states; int64_t n, ld; RobotK K; const double *tab; const StepK *steps; int nsteps; FkOut out;
+  const FusedSweepArgs *sa;
+};
+// (no padding but the four bytes behind nsteps: the launch places the arguments exactly so)
+static_assert(alignof(RobotK) == 8 && alignof(FkOut) == 8 && sizeof(FusedKernargs) == 24 + sizeof(RobotK) + 24 + sizeof(FkOut) + 8,
+              "FusedKernargs must mirror the parameter list of fk_sweep_fused");
+typedef const __attribute__((address_space(4))) FusedKernargs *FusedKernargsPtr;
+__device__ __forceinline__ FusedKernargsPtr fused_kernargs() {
+  FusedKernargsPtr p = (FusedKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 template <int N, bool ROT>
 __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk_sweep_fused(
     const double *__restrict__ states, int64_t n, int64_t ld, RobotK K, const double *__restrict__ tab,
@@ -36,8 +54,9 @@ __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk
   fk_uniform_body<N, ROT, false, false>(states, n, ld, K, tab, steps, nsteps, out, hook);
   hook.finish();
   __syncthreads();
-  const FusedSweepArgs a = *sa;
-  sweep_body<false>(a.in, n, ld, a.P, a.CH, a.NM, K, a.g, a.grid, a.near_grid, a.check_voxels, a.debug, a.valid_bits, a.flags);
+  const FusedKernargsPtr ka = fused_kernargs();
+  const FusedSweepArgs a = *ka->sa;
+  sweep_body<false>(a.in, ka->n, ka->ld, a.P, a.CH, a.NM, ka->K, a.g, a.grid, a.near_grid, a.check_voxels, a.debug, a.valid_bits, a.flags);
 }
 
 // The same on a compacted list of configurations: this is the fallback pass of the verdict-only kernel
@@ -58,8 +77,9 @@ __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk
     if ((int64_t)blockIdx.x * 64 >= m) break;                     // wave-uniform
     fk_uniform_body<N, ROT, false, false>(states, m, ld, K, tab, steps, nsteps, out, NoPointHook(), list + offset);
     __syncthreads();
-    const FusedSweepArgs a = *sa;
-    sweep_body<false>(a.in, m, ld, a.P, a.CH, a.NM, K, a.g, a.grid, a.near_grid, a.check_voxels, a.debug, a.valid_bits, a.flags, list + offset);
+    const FusedKernargsPtr ka = fused_kernargs();
+    const FusedSweepArgs a = *ka->sa;
+    sweep_body<false>(a.in, m, ka->ld, a.P, a.CH, a.NM, ka->K, a.g, a.grid, a.near_grid, a.check_voxels, a.debug, a.valid_bits, a.flags, list + offset);
     __syncthreads();
   }
 }

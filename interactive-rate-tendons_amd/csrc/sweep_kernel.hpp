@@ -489,9 +489,9 @@ __device__ __forceinline__ bool milestones_unresolved(const float *__restrict__ 
 // out_map (optional): see the end of the function.  lane_valid (optional): the lane's verdict is returned there instead of written.
 // TIPROWS (retraction robots, in.n_points set): K1r stores a lane's point j in row j + (P - n_points), i.e. rows
 // are aligned at the tip like K1r's iterations, so that its stores -- and the loads here -- stay coalesced.
-template <bool TIPROWS>
+template <bool TIPROWS, class RobotT>
 __device__ __forceinline__ void sweep_body(
-    const SweepIn &in, int64_t n, int64_t ld, int P, int CH, int NM, const RobotK &K, const GridK &g, const uint64_t *__restrict__ grid,
+    const SweepIn &in, int64_t n, int64_t ld, int P, int CH, int NM, const RobotT &K, const GridK &g, const uint64_t *__restrict__ grid,
     const uint64_t *__restrict__ near_grid, int check_voxels, uint32_t debug, uint64_t *__restrict__ valid_bits,
     uint8_t *__restrict__ flags, const int32_t *__restrict__ out_map = nullptr, bool *lane_valid = nullptr) {
 #pragma clang fp contract(off)
