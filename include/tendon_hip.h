@@ -395,6 +395,53 @@ int tr_validate_edges_last_valid(tr_ctx *ctx, const tr_space_params *sp, const d
 int tr_validate_edges_discrete(tr_ctx *ctx, const tr_space_params *sp, const double *a, const double *b,
                                int64_t n_edges, uint64_t *valid_bits, double *last_valid_t, int32_t *n_fk);
 
+/* ---- loaded edges: checkMotion with every FK sample taken from TendonRobot::general_shape --- */
+
+/* The reference's motion validator takes every sample's shape from _vc->fk(state) (motion-planning/
+ * VoxelBackboneMotionValidator.cpp:25), and AbstractValidityChecker::set_fk_func swaps that FK for general_shape under a
+ * load (apps/profile_chained_plan.cpp:407-451): checkMotion then bisects on loaded shapes.  These calls are that, for a
+ * batch of edges and ONE load set per call. */
+enum { TR_LOAD_FRAME_BASE = 0, TR_LOAD_FRAME_WORLD = 1 };
+typedef struct tr_edge_loads {
+  double wrench[6];    /* F_e, L_e */
+  double dist[6];      /* f_e, l_e per unit length */
+  int32_t frame;       /* BASE: tr_fk_loaded_batch's frame (before the state's rotation), the same 12 numbers for every sample.
+                          WORLD: fixed in the frame after rotate_z; a sample with rotation theta gets Rz(-theta) applied to all
+                          four vectors (robots without rotation: the same as BASE) */
+  int32_t warm_start;  /* 0: every sample starts from the unloaded solution of its tensions (tr_fk_loaded_batch without a guess).
+                          1: a midpoint starts from the accepted base strains of its interval's sample at t_a; the end states
+                          (the indexed form's vertices) start cold */
+} tr_edge_loads;
+
+/* tr_validate_edges (last_valid_t == NULL: checkMotion(s1, s2)) or tr_validate_edges_last_valid (otherwise:
+ * checkMotion(s1, s2, last_valid)) on loaded shapes: the same level-synchronous bisection, sample tests, verdict bits, n_fk and
+ * last_valid_t, every sample solved by the shooting of tr_fk_loaded_batch with `shoot` (NULL: its defaults) and the sample's
+ * loads.  A sample whose shooting does not converge is an INVALID sample (general_tension_shape sets res.converged = false and
+ * is_valid_shape rejects it), never an error of the call.  loads == NULL: no load, cold start.
+ *   n_unconverged   (optional) samples whose shooting did not converge
+ *   n_integrations  (optional) the sum of the samples' fk_calls (tr_fk_loaded_batch's fk_calls_out)
+ * The rotation of WORLD loads uses a fixed sequence of IEEE operations for sine and cosine (csrc/loaded_edge_kernel.hpp), so a
+ * host restatement reproduces the per-sample rows bit for bit.  Robots with retraction: TR_ERR_UNSUPPORTED; no grid or a
+ * non-positive resolution: TR_ERR_INVALID_ARG; n_edges == 0: TR_OK.  The verdicts do not depend on the chunking
+ * (TENDON_HIP_SHOOT_CHUNK, TENDON_HIP_EDGE_POOL), the order of the edges or the other edges of the call. */
+int tr_validate_edges_loaded(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                             const double *a, const double *b, int64_t n_edges, uint64_t *valid_bits, double *last_valid_t,
+                             int32_t *n_fk, int64_t *n_domain_errors, int64_t *n_unconverged, int64_t *n_integrations);
+/* The roadmap form (tr_validate_edges_indexed's arguments and n_fk convention): every vertex is solved and swept once, cold, for
+ * all of its edges; with warm_start its accepted strains start the first midpoints of its edges. */
+int tr_validate_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                                     const double *states, int64_t n_states, const int32_t *edges, int64_t n_edges,
+                                     uint64_t *valid_bits, int32_t *n_fk, int64_t *n_domain_errors, int64_t *n_unconverged,
+                                     int64_t *n_integrations);
+/* The accepted base strains (v0, u0), n_states x 6, of the vertices of the context's last tr_validate_edges_loaded_indexed call:
+ * tr_fk_loaded_batch's vu0_out for the same states and per-state loads.  TR_ERR_INVALID_ARG when none are resident (no indexed
+ * call yet, a pairwise loaded call since, the call took the pairwise form) or n_states is not that call's. */
+int tr_edges_loaded_vertex_strains(tr_ctx *ctx, int64_t n_states, double *vu0_out);
+/* How the context's last loaded edge call ran (tuning, benchmarks): samples evaluated (those of chunks retried after a pool
+ * overflow included), levels (one loads / guess / shooting / K2 sequence each), Levenberg-Marquardt rounds (one host
+ * synchronisation each), chunk attempts. */
+int tr_edges_loaded_last(const tr_ctx *ctx, int64_t stats[4]);
+
 /* ---- cached voxel sets vs obstacles: VoxelOctree::collides on roadmap caches ------------ */
 
 /* Batched `obstacles.collides(*cached_voxels)` for roadmap vertices / edges

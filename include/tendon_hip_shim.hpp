@@ -429,6 +429,25 @@ class VoxelBackboneValidityChecker {
   }
   tr_ctx *context() const { return ctx_; }
 
+  // ---- loads: AbstractValidityChecker::set_fk_func with TendonRobot::general_shape under a load
+  // (apps/profile_chained_plan.cpp:407-451).  Once set, the motion validators on this checker take every FK sample from the
+  // loaded FK (tr_validate_edges_loaded*); clearLoads() restores the unloaded checks. ----
+  /// wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, 6 values each (empty: zero); world: the loads are fixed behind the
+  /// state's rotation (every sample's rows are turned by Rz(-theta)), else before it (tr_fk_loaded_batch's frame)
+  void setLoads(const std::vector<double> &wrench, const std::vector<double> &dist, bool world = false, bool warm_start = false) {
+    if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6))
+      throw std::invalid_argument("wrench and dist hold 6 values each: one load set");
+    loads_ = tr_edge_loads{};
+    for (size_t q = 0; q < wrench.size(); q++) loads_.wrench[q] = wrench[q];
+    for (size_t q = 0; q < dist.size(); q++) loads_.dist[q] = dist[q];
+    loads_.frame = world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
+    loads_.warm_start = warm_start ? 1 : 0;
+    has_loads_ = true;
+  }
+  void clearLoads() { has_loads_ = false; }
+  /// the load set, or nullptr when none is set
+  const tr_edge_loads *loads() const { return has_loads_ ? &loads_ : nullptr; }
+
   // ---- edits of the obstacle set where it lives (collision::VoxelOctree's add_sphere / dilate* /
   // remove_interior, VoxelOctree.cpp:434-469, :533-952, as apps/prepare_voxel_env.cpp:269-315 applies them) ----
   /// VoxelOctree::add_capsule on the resident obstacle set (collision/VoxelOctree.cpp:471-515)
@@ -456,6 +475,8 @@ class VoxelBackboneValidityChecker {
  private:
   const tendon::TendonRobot &robot_;
   tr_ctx *ctx_;
+  tr_edge_loads loads_{};
+  bool has_loads_ = false;
 };
 
 /// VoxelValidityChecker (motion-planning/VoxelValidityChecker.h:18-26): the same interface; the robot is
@@ -556,6 +577,11 @@ class VoxelBackboneMotionValidator {
     const size_t n = edges.size() / 2;
     std::vector<uint64_t> bits((n + 63) / 64);
     if (n_fk) n_fk->resize(n);
+    if (const tr_edge_loads *ld = vc_.loads()) {            // the checker's FK is the loaded one (setLoads)
+      check(vc_.context(), tr_validate_edges_loaded_indexed(vc_.context(), &space, nullptr, ld, states.data(), (int64_t)n_states, edges.data(),
+                                                            (int64_t)n, bits.data(), n_fk ? n_fk->data() : nullptr, nullptr, nullptr, nullptr));
+      return detail::unpack(bits, n);
+    }
     check(vc_.context(), tr_validate_edges_indexed(vc_.context(), &space, states.data(), (int64_t)n_states, edges.data(), (int64_t)n,
                                                    bits.data(), n_fk ? n_fk->data() : nullptr, nullptr));
     return detail::unpack(bits, n);
@@ -612,6 +638,8 @@ class VoxelBackboneMotionValidator {
 
  protected:
   virtual int run(const double *a, const double *b, int64_t n, uint64_t *bits, int32_t *n_fk, double *t) const {
+    if (const tr_edge_loads *ld = vc_.loads())            // the checker's FK is the loaded one (setLoads)
+      return tr_validate_edges_loaded(vc_.context(), &space, nullptr, ld, a, b, n, bits, t, n_fk, nullptr, nullptr, nullptr);
     if (t) return tr_validate_edges_last_valid(vc_.context(), &space, a, b, n, bits, t, n_fk);
     return tr_validate_edges(vc_.context(), &space, a, b, n, bits, n_fk, nullptr);
   }
@@ -626,6 +654,7 @@ class VoxelBackboneDiscreteMotionValidator : public VoxelBackboneMotionValidator
 
  protected:
   int run(const double *a, const double *b, int64_t n, uint64_t *bits, int32_t *n_fk, double *t) const override {
+    if (vc_.loads()) throw std::logic_error("the discrete motion validator is not built for loaded shapes (setLoads)");
     return tr_validate_edges_discrete(vc_.context(), &space, a, b, n, bits, t, n_fk);
   }
 };

@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "tr_roadmap_set_tips", "tr_roadmap_nearest_tips", "tr_roadmap_nearest_tips_dev", "tr_roadmap_ik_batch", "tr_roadmap_solve_tips",
     "tr_roadmap_tip_query_profile",
     "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev",
+    "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
 )
 
 
@@ -70,6 +71,13 @@ class TrIkParams(C.Structure):
 class TrShootParams(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("mu_init", C.c_double), ("stop_threshold_JT_err_inf", C.c_double),
                 ("stop_threshold_Dp", C.c_double), ("finite_difference_delta", C.c_double)]
+
+
+TR_LOAD_FRAME_BASE, TR_LOAD_FRAME_WORLD = 0, 1
+
+
+class TrEdgeLoads(C.Structure):
+    _fields_ = [("wrench", C.c_double * 6), ("dist", C.c_double * 6), ("frame", C.c_int32), ("warm_start", C.c_int32)]
 
 
 class TrTipQueryParams(C.Structure):
@@ -342,6 +350,11 @@ def lib():
     shp = P(TrShootParams)
     L.tr_fk_loaded_batch.argtypes = [vp, shp, dp, i64, dp, i64, dp, i64, dp, dp, dp, dp, dp, P(C.c_uint8), i32p, dp, dp, dp, i32p, i32p, P(i64)]
     L.tr_fk_loaded_batch_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
+    elp = P(TrEdgeLoads)
+    L.tr_validate_edges_loaded.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, dp, i64, P(C.c_uint64), dp, i32p, P(i64), P(i64), P(i64)]
+    L.tr_validate_edges_loaded_indexed.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, i64, i32p, i64, P(C.c_uint64), i32p, P(i64), P(i64), P(i64)]
+    L.tr_edges_loaded_vertex_strains.argtypes = [vp, i64, dp]
+    L.tr_edges_loaded_last.argtypes = [vp, P(i64)]
     tqp = P(TrTipQueryParams)
     L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
     L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]

@@ -176,6 +176,10 @@ struct EdgeRun {
   double *lvl_states = nullptr; trk::EdgeIv *open = nullptr, *frontier = nullptr;
   int64_t pool = 0, n_bound = 0;
   bool slots_only = false;      // the samples go through the verdict-only kernels and nobody reads their points: the pool is EdgeDev's arrays
+  // A sample evaluator in the place of launch_fk_sweep (loaded_edges_host.inc: the loaded FK, then K2 on the stored planes): it leaves
+  // the points of the m level states in workspace columns [s0, s0 + m) and their verdicts in bits.  Such a run lives in the point
+  // workspace and compares stored points (no signatures)
+  std::function<int(EdgeRun &, int64_t, int64_t)> eval;
 
   static dim3 blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
@@ -186,9 +190,10 @@ struct EdgeRun {
     trk::FkOut out{};
     trk::SweepIn in{};
     if (!slots_only) { out = ws_fk_out(c, s0); in = ws_sweep_in(c, s0); }    // (a slots-only pool may be larger than the workspace: no plane is addressed by slot then)
-    if ((r = launch_fk_sweep(c, lvl_states, m, cap, out, in, sample_test, d.bits + s0 / 64, nullptr, L.s,
-                             sig ? sig + s0 * d.sig_stride : nullptr, d.sig_stride, /*points_unused=*/sig != nullptr && !vox,
-                             (sig && ret) ? d.sig_np + s0 : nullptr, L.lane))) return r;
+    if (eval) { if ((r = eval(*this, s0, m))) return r; }
+    else if ((r = launch_fk_sweep(c, lvl_states, m, cap, out, in, sample_test, d.bits + s0 / 64, nullptr, L.s,
+                                  sig ? sig + s0 * d.sig_stride : nullptr, d.sig_stride, /*points_unused=*/sig != nullptr && !vox,
+                                  (sig && ret) ? d.sig_np + s0 : nullptr, L.lane))) return r;
     ProfScope ps(c, 3, L.s);
     hipLaunchKernelGGL(trk::edge_fold, blocks(m), dim3(256), 0, L.s, st, s0, m, until);
     HIP_TRY(c, hipGetLastError());
@@ -211,7 +216,7 @@ struct EdgeRun {
     S = c->K.state_size; P = c->K.n_points;
     cap = w.ld; E = e1 - e0;
     base = ix ? ix->pool_base : 0;
-    slots_only = c->edge_slots_now > 0 && !vox && c->fuse == 2 && edge_signatures(c, false);
+    slots_only = !eval && c->edge_slots_now > 0 && !vox && c->fuse == 2 && edge_signatures(c, false);
     if (!slots_only && L.slot_hi > cap) return fail(c, TR_ERR_RUNTIME, "pool slots beyond the point workspace");
     if (!ix && L.slot_lo != 0) return fail(c, TR_ERR_RUNTIME, "pairwise edges start at pool slot 0");
     if (ix ? (L.slot_lo < base || 2 * E > L.slot_hi) : (2 * E > L.slot_hi - L.slot_lo)) return EDGE_OVERFLOW;
@@ -229,7 +234,7 @@ struct EdgeRun {
     sk = edge_space(c, sp);
     const int64_t eo = L.eoff;
     st = edge_state(c, eo, L.counters);
-    sig = edge_signatures(c, vox != nullptr) ? d.sig : nullptr;      // the fused launches write them, edge_filter compares them
+    sig = (!eval && edge_signatures(c, vox != nullptr)) ? d.sig : nullptr;      // the fused launches write them, edge_filter compares them
     filter_np = ret ? (sig ? d.sig_np : w.np) : nullptr;             // point counts next to what the interval test reads
     lvl_states = d.lvl_states + L.level_off * S; open = d.open + L.level_off; frontier = d.frontier + 2 * L.level_off;
 

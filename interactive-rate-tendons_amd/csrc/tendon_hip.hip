@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <chrono>
 #include <thread>
 #include <ctime>
@@ -41,6 +42,7 @@
 #include "sample.hpp"
 #include "ik_kernel.hpp"
 #include "fk_loaded_kernel.hpp"
+#include "loaded_edge_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
 struct tr_ctx;
@@ -267,6 +269,15 @@ struct tr_ctx {
     int32_t *io_np = nullptr, *io_it = nullptr, *io_fc = nullptr;
     uint8_t *io_conv = nullptr;
   } shoot;
+  // loaded edges (loaded_edges_host.inc): per pool sample the accepted base strains [cap][6]; per level sample the load rows, the
+  // start strains [cap][6] each and the integrations [cap]; the run's tally (unconverged samples, integrations)
+  struct LoadedEdgeDev {
+    int64_t cap = 0, n_vertices = 0;        // n_vertices: rows [0, n) of vu_pool are the vertices of the last indexed call
+    double *vu_pool = nullptr, *w = nullptr, *d = nullptr, *g = nullptr;
+    int32_t *calls = nullptr;
+    unsigned long long *tally = nullptr;
+    int64_t last[4] = {0, 0, 0, 0};         // tr_edges_loaded_last
+  } ledge;
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
   bool profiling = false;
@@ -1130,6 +1141,11 @@ void tr_destroy(tr_ctx *c) {
   }
   ik_release(c);
   shoot_release(c);
+  {
+    tr_ctx::LoadedEdgeDev &le = c->ledge;
+    void *lp[] = {le.vu_pool, le.w, le.d, le.g, le.calls, le.tally};
+    for (void *q : lp) if (q) (void)hipFree(q);
+  }
   delete c;
 }
 
@@ -2237,3 +2253,4 @@ int tr_profile_end(tr_ctx *c) {
 #include "sample_host.inc"
 #include "ik_host.inc"
 #include "loaded_host.inc"
+#include "loaded_edges_host.inc"

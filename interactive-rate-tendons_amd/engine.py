@@ -29,6 +29,28 @@ def unpack_bits(words, n):
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
+def edge_sincos(x):
+    """(sin x, cos x) by the operation sequence of csrc/loaded_edge_kernel.hpp's edge_sincos -- two-term reduction by pi/2, Taylor
+    polynomials in Horner form, IEEE fp64 without contraction -- so the rows of Engine.sample_loads are the device's, bit for bit."""
+    x = np.asarray(x, dtype=np.float64)
+    k = np.rint(x * 0.63661977236758138)
+    r = (x - k * 1.57079632673412561417e+00) - k * 6.07710050650619224932e-11
+    z = r * r
+    ps = np.full_like(z, 1.0 / 355687428096000.0)
+    for f in (-1.0 / 1307674368000.0, 1.0 / 6227020800.0, -1.0 / 39916800.0, 1.0 / 362880.0, -1.0 / 5040.0, 1.0 / 120.0, -1.0 / 6.0):
+        ps = f + z * ps
+    sr = r + r * (z * ps)
+    pc = np.full_like(z, -1.0 / 6402373705728000.0)
+    for f in (1.0 / 20922789888000.0, -1.0 / 87178291200.0, 1.0 / 479001600.0, -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0,
+              1.0 / 24.0, -0.5):
+        pc = f + z * pc
+    cr = 1.0 + z * pc
+    q = k.astype(np.int64) & 3
+    s = np.where(q == 0, sr, np.where(q == 1, cr, np.where(q == 2, -sr, -cr)))
+    c = np.where(q == 0, cr, np.where(q == 1, -sr, np.where(q == 2, -cr, sr)))
+    return s, c
+
+
 class Engine:
     """One context of libtendon_hip.so: tr_create ... tr_destroy."""
 
@@ -404,6 +426,102 @@ class Engine:
             self._ctx, C.byref(sp), _dp(a), _dp(b), n, bits.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(lvt),
             nfk.ctypes.data_as(C.POINTER(C.c_int32))))
         return dict(valid=unpack_bits(bits, n), last_valid_t=lvt, n_fk=nfk)
+
+    # ---- loaded edges (tr_validate_edges_loaded*, include/tendon_hip.h): checkMotion on shapes under a tip wrench and gravity ----
+    #: Python default of warm_start: cold, until bench_loaded_edges.py has shown that the warm start saves integrations
+    LOADED_EDGES_WARM_START = False
+
+    @staticmethod
+    def _edge_loads(wrench, dist, frame, warm_start):
+        ld = L.TrEdgeLoads()
+        for name, a in (("wrench", wrench), ("dist", dist)):
+            v = np.zeros(6) if a is None else _f64(a)
+            if v.shape != (6,):
+                raise L.InvalidArgument("%s must be (6,): one load set per call" % name)
+            getattr(ld, name)[:] = [float(x) for x in v]
+        if frame not in ("base", "world"):
+            raise L.InvalidArgument("frame must be 'base' or 'world'")
+        ld.frame = L.TR_LOAD_FRAME_WORLD if frame == "world" else L.TR_LOAD_FRAME_BASE
+        ld.warm_start = int(bool(Engine.LOADED_EDGES_WARM_START if warm_start is None else warm_start))
+        return ld
+
+    def sample_loads(self, states, wrench=None, dist=None, frame="base"):
+        """The (n, 6) wrench and distributed-load rows the loaded edge calls give the samples `states`, restated on the host with the
+        kernel's own operation sequence (csrc/loaded_edge_kernel.hpp: edge_sincos, loaded_sample_loads): bit for bit the device's
+        rows.  frame='base': the call's 12 numbers for every state; 'world': turned by Rz(-theta) of the state's rotation."""
+        st = self._states(states)
+        ld = self._edge_loads(wrench, dist, frame, False)
+        w, d = np.array(ld.wrench[:]), np.array(ld.dist[:])
+        n = st.shape[0]
+        _, rot, _ = self.state_layout()
+        if frame == "base" or not rot:
+            return np.tile(w, (n, 1)), np.tile(d, (n, 1))
+        s, c = edge_sincos(st[:, self.n_tendons])
+        out = []
+        for v in (w, d):
+            r = np.empty((n, 6))
+            for h in (0, 3):
+                r[:, h + 0] = c * v[h + 0] + s * v[h + 1]
+                r[:, h + 1] = c * v[h + 1] - s * v[h + 0]
+                r[:, h + 2] = v[h + 2]
+            out.append(r)
+        return out[0], out[1]
+
+    def validate_edges_loaded(self, a, b, wrench=None, dist=None, frame="base", warm_start=None, last_valid=False,
+                              min_tension_change=0.02, min_rotation_change=0.01, min_retraction_change=0.0001, **shoot):
+        """checkMotion(s1, s2) (last_valid=False) or checkMotion(s1, s2, last_valid) on LOADED shapes: tr_validate_edges /
+        tr_validate_edges_last_valid with every sample taken from the loaded FK under wrench = (F_e, L_e) and dist = (f_e, l_e),
+        one (6,) row each.  A sample whose shooting does not converge is an invalid sample.  **shoot: fk_loaded_batch's solver
+        arguments.  Returns dict(valid, bits, n_fk, last_valid_t (None without last_valid), n_domain_errors, n_unconverged,
+        n_integrations)."""
+        a, b = self._states(a), self._states(b)
+        if a.shape != b.shape:
+            raise L.InvalidArgument("start and end are different sizes")
+        n = a.shape[0]
+        sp = L.TrSpaceParams(min_tension_change, min_rotation_change, min_retraction_change)
+        ld = self._edge_loads(wrench, dist, frame, warm_start)
+        prm = self._shoot_params(**{**dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
+                                           finite_difference_delta=1e-6), **shoot})
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        lvt = np.zeros(n) if last_valid else None
+        nfk = np.zeros(n, dtype=np.int32)
+        nd, nu, ni = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_validate_edges_loaded(
+            self._ctx, C.byref(sp), C.byref(prm), C.byref(ld), _dp(a), _dp(b), n, bits.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _dp(lvt) if last_valid else None, nfk.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nd), C.byref(nu), C.byref(ni)))
+        return dict(valid=unpack_bits(bits, n), bits=bits, n_fk=nfk, last_valid_t=lvt, n_domain_errors=int(nd.value),
+                    n_unconverged=int(nu.value), n_integrations=int(ni.value))
+
+    def validate_edges_loaded_indexed(self, states, edges, wrench=None, dist=None, frame="base", warm_start=None,
+                                      min_tension_change=0.02, min_rotation_change=0.01, min_retraction_change=0.0001, **shoot):
+        """Roadmap form of validate_edges_loaded: edges (n_edges, 2) index rows of states; every vertex is solved once."""
+        st = self._states(states)
+        e = np.ascontiguousarray(np.asarray(edges).reshape(-1, 2), dtype=np.int32)
+        n = e.shape[0]
+        sp = L.TrSpaceParams(min_tension_change, min_rotation_change, min_retraction_change)
+        ld = self._edge_loads(wrench, dist, frame, warm_start)
+        prm = self._shoot_params(**{**dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
+                                           finite_difference_delta=1e-6), **shoot})
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        nfk = np.zeros(n, dtype=np.int32)
+        nd, nu, ni = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_validate_edges_loaded_indexed(
+            self._ctx, C.byref(sp), C.byref(prm), C.byref(ld), _dp(st), st.shape[0], e.ctypes.data_as(C.POINTER(C.c_int32)), n,
+            bits.ctypes.data_as(C.POINTER(C.c_uint64)), nfk.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nd), C.byref(nu), C.byref(ni)))
+        return dict(valid=unpack_bits(bits, n), bits=bits, n_fk=nfk, last_valid_t=None, n_domain_errors=int(nd.value),
+                    n_unconverged=int(nu.value), n_integrations=int(ni.value))
+
+    def edges_loaded_last(self):
+        """How the last loaded edge call ran: dict(samples, levels, rounds, chunks) (tr_edges_loaded_last)."""
+        st = (C.c_int64 * 4)()
+        L.check(self._ctx, self.lib.tr_edges_loaded_last(self._ctx, st))
+        return dict(samples=int(st[0]), levels=int(st[1]), rounds=int(st[2]), chunks=int(st[3]))
+
+    def edges_loaded_vertex_strains(self, n_states):
+        """(n_states, 6) accepted base strains of the vertices of the last validate_edges_loaded_indexed call."""
+        out = np.empty((int(n_states), 6))
+        L.check(self._ctx, self.lib.tr_edges_loaded_vertex_strains(self._ctx, int(n_states), _dp(out)))
+        return out
 
     def validate_edges_discrete(self, a, b, min_tension_change=0.02, min_rotation_change=0.01,
                                 min_retraction_change=0.0001, last_valid=True):

@@ -153,8 +153,34 @@ class VoxelBackboneValidityChecker:
         """AbstractValidityChecker::fk (AbstractValidityChecker.cpp:80-97) for a batch."""
         return self._timers["fk"].time(self.engine.fk_batch, robot_states)
 
+    # ---- loads: AbstractValidityChecker::set_fk_func with TendonRobot::general_shape under a load
+    # (apps/profile_chained_plan.cpp:407-451): from then on the checker's FK, and with it the motion validator's, is the loaded one ----
+    _loads = None
+
+    def set_loads(self, wrench=None, dist=None, frame="base", warm_start=None, **shoot):
+        """wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, one (6,) row each (None: zero).  frame='base': fixed before the
+        state's rotation (fk_loaded_batch's frame); 'world': fixed behind it, every state's rows turned by Rz(-theta).  Afterwards
+        is_valid and the motion validators on this checker judge LOADED shapes; clear_loads() restores the unloaded checks."""
+        self.engine._edge_loads(wrench, dist, frame, warm_start)              # argument checks
+        self._loads = dict(wrench=wrench, dist=dist, frame=frame, warm_start=warm_start, **shoot)
+
+    def clear_loads(self):
+        self._loads = None
+
+    def loads(self):
+        return self._loads
+
+    def _is_valid_loaded(self, robot_states):
+        ld = dict(self._loads)
+        frame = ld.pop("frame")
+        ld.pop("warm_start")
+        w, d = self.engine.sample_loads(robot_states, ld.pop("wrench"), ld.pop("dist"), frame)
+        return self.engine.validate_loaded(robot_states, wrench=w, dist=d, **ld)
+
     def is_valid(self, robot_states):
         """bool[n]: full state validity (FK, converged, lengths, self collision, voxel collision)."""
+        if self._loads is not None:
+            return self._timers["is_valid"].time(self._is_valid_loaded, robot_states)["valid"]
         return self._timers["is_valid"].time(self.engine.validate_batch, robot_states, False, False)["valid"]
 
     def is_valid_detail(self, robot_states):
@@ -227,7 +253,13 @@ class VoxelBackboneMotionValidator:
     def timers(self): return self._timers
     def num_voxelize_errors(self): return self._num_voxelize_errors
 
+    def _resolutions(self):
+        return dict(min_tension_change=self.min_tension_change, min_rotation_change=self.min_rotation_change,
+                    min_retraction_change=self.min_retraction_change)
+
     def check_motion_detail(self, a, b):
+        if self._vc.loads() is not None:              # the checker's FK is the loaded one (set_loads): so is every sample's
+            return self._timers["voxelize-swept-volume"].time(self.engine.validate_edges_loaded, a, b, **self._vc.loads(), **self._resolutions())
         return self._timers["voxelize-swept-volume"].time(
             self.engine.validate_edges, a, b, self.min_tension_change, self.min_rotation_change,
             self.min_retraction_change)
@@ -238,6 +270,9 @@ class VoxelBackboneMotionValidator:
     def check_motion_indexed(self, states, edges):
         """checkMotion for roadmap edges given as index pairs into one vertex array: same verdicts and n_fk, but
         every vertex is evaluated once for all of its edges (tr_validate_edges_indexed)."""
+        if self._vc.loads() is not None:
+            return self._timers["voxelize-swept-volume"].time(self.engine.validate_edges_loaded_indexed, states, edges, **self._vc.loads(),
+                                                              **self._resolutions())
         return self._timers["voxelize-swept-volume"].time(
             self.engine.validate_edges_indexed, states, edges, self.min_tension_change, self.min_rotation_change,
             self.min_retraction_change)
@@ -245,6 +280,9 @@ class VoxelBackboneMotionValidator:
     def check_motion_last_valid(self, a, b):
         """checkMotion(s1, s2, last_valid) for a batch: (valid, last_valid_t); last_valid.first is
         interpolate(s1, s2, last_valid_t) in the caller's state space."""
+        if self._vc.loads() is not None:
+            d = self.engine.validate_edges_loaded(a, b, last_valid=True, **self._vc.loads(), **self._resolutions())
+            return d["valid"], d["last_valid_t"]
         d = self.engine.validate_edges_last_valid(a, b, self.min_tension_change, self.min_rotation_change,
                                                   self.min_retraction_change)
         return d["valid"], d["last_valid_t"]
@@ -258,6 +296,8 @@ class VoxelBackboneDiscreteMotionValidator(VoxelBackboneMotionValidator):
     sampled at a, interpolate(i / validSegmentCount), b instead of bisected adaptively."""
 
     def check_motion_detail(self, a, b, last_valid=False):
+        if self._vc.loads() is not None:
+            raise L.Unsupported("the discrete motion validator is not built for loaded shapes (set_loads)")
         return self._timers["voxelize-swept-volume"].time(
             self.engine.validate_edges_discrete, a, b, self.min_tension_change, self.min_rotation_change,
             self.min_retraction_change, last_valid)
