@@ -442,6 +442,47 @@ int tr_edges_loaded_vertex_strains(tr_ctx *ctx, int64_t n_states, double *vu0_ou
  * synchronisation each), chunk attempts. */
 int tr_edges_loaded_last(const tr_ctx *ctx, int64_t stats[4]);
 
+/* ---- the roadmap build on loaded shapes -------------------------------------------------- */
+
+/* In the reference set_fk_func(general_shape ...) changes createRoadmap's vertex loop, voxelizeVertex and voxelizeEdge at once,
+ * because they all take their shapes from voxelStateChecker_->fk (motion-planning/VoxelCachedLazyPRM.cpp:1415-1439, 2803-2837,
+ * 2879-2902).  These calls are those loops on the loaded FK.  shoot == NULL: the solver's defaults; loads == NULL: no load.  Every
+ * vertex is solved cold, so it has the same strains, points and tip -- bit for bit -- in the vertex phase, in
+ * tr_voxelize_batch_loaded, as an end state of the indexed edge calls and in tr_fk_loaded_batch with the per-state load rows.
+ * All report n_unconverged and n_integrations as the loaded edge calls do (optional).  Robots with retraction:
+ * TR_ERR_UNSUPPORTED; a bad frame or no grid: TR_ERR_INVALID_ARG; an empty call: TR_OK before the grid is asked for. */
+
+/* tr_sample_valid_vertices on loaded shapes: the accepted set is the first n_want candidates i of the sequence (seed, first_candidate
+ * + i) whose loaded shape -- tr_fk_loaded_batch's, cold, under the candidate's load rows (BASE or WORLD) -- is valid under the
+ * installed checker; an unconverged candidate is an invalid one.  A pure function of (seed, first_candidate, box, loads, shoot): it
+ * does not depend on the batch size or on TENDON_HIP_SHOOT_CHUNK.  vu0 (optional): n_want x 6, the accepted base strains.
+ * n_unconverged / n_integrations: sums over the n_tried candidates consumed.  Each batch of candidates is generated, loaded, solved,
+ * swept and compacted on the device; the host reads one counter block per batch. */
+int tr_sample_valid_vertices_loaded(tr_ctx *ctx, const tr_shoot_params *shoot, const tr_edge_loads *loads, uint64_t seed,
+                                    uint64_t first_candidate, const double *lo, const double *hi, int64_t n_want, int64_t max_candidates,
+                                    double *states, double *tips, int64_t *index, double *vu0, int64_t *n_accepted, int64_t *n_tried,
+                                    int64_t *n_unconverged, int64_t *n_integrations);
+/* ... with device outputs (d_tips, d_index, d_vu0 optional).  The run is the null stream's and ends synchronised. */
+int tr_sample_valid_vertices_loaded_dev(tr_ctx *ctx, const tr_shoot_params *shoot, const tr_edge_loads *loads, uint64_t seed,
+                                        uint64_t first_candidate, const double *lo, const double *hi, int64_t n_want,
+                                        int64_t max_candidates, double *d_states, double *d_tips, int64_t *d_index, double *d_vu0,
+                                        int64_t *n_accepted, int64_t *n_tried, int64_t *n_unconverged, int64_t *n_integrations,
+                                        void *stream);
+/* tr_voxelize_batch (voxelizeVertex: shape validity, block list, tip) on loaded shapes, cold start; the same CSR and the
+ * tr_voxelize_fetch* protocol. */
+int tr_voxelize_batch_loaded(tr_ctx *ctx, const tr_shoot_params *shoot, const tr_edge_loads *loads, const double *states, int64_t n,
+                             int64_t *offsets, uint64_t *shape_valid_bits, double *tips, int64_t *n_unconverged,
+                             int64_t *n_integrations);
+/* tr_voxelize_edges_indexed / tr_connect_edges_indexed on loaded samples: tr_validate_edges_loaded_indexed's bisection (warm_start
+ * honoured the same way) with the voxelize forms' sample tests and block lists.  tr_edges_loaded_vertex_strains and
+ * tr_edges_loaded_last also answer for these calls. */
+int tr_voxelize_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                                     const double *states, int64_t n_states, const int32_t *edges, int64_t n_edges, int64_t *offsets,
+                                     uint64_t *fully_valid_bits, int32_t *n_fk, int64_t *n_unconverged, int64_t *n_integrations);
+int tr_connect_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                                    const double *states, int64_t n_states, const int32_t *edges, int64_t n_edges, int64_t *offsets,
+                                    uint64_t *valid_bits, int32_t *n_fk, int64_t *n_unconverged, int64_t *n_integrations);
+
 /* ---- cached voxel sets vs obstacles: VoxelOctree::collides on roadmap caches ------------ */
 
 /* Batched `obstacles.collides(*cached_voxels)` for roadmap vertices / edges
@@ -794,6 +835,8 @@ int tr_edge_schedule_last(const tr_ctx *ctx, uint32_t stats[4]);
  *   TENDON_HIP_EDGE_POOL=n          upper bound of the FK sample pool (tests: forces chunking / the overflow paths)
  *   TENDON_HIP_FB_CAP=n             columns of the fallback pass's point workspace (default: one resident round of waves)
  *   TENDON_HIP_SHOOT_CHUNK=n        problems per chunk of tr_fk_loaded_batch* (tests: forces chunking; default: what 2^19 lanes hold)
+ *   TENDON_HIP_LOADED_VERTEX_BATCH=n  candidates per batch of tr_sample_valid_vertices_loaded* and states per chunk of
+ *                                   tr_voxelize_batch_loaded (tests: several batches; default: 2^16, what the workspace is grown to)
  *   TENDON_HIP_RETRACT_SORT=n       retraction robots: batches of at least n configurations are ordered by backbone length
  *                                   (0 = never); TENDON_HIP_RETRACT_KBEGIN_OFF: no per-wave loop start in that order
  * Read per call (the tests switch between two paths inside one process; the switches of tr_roadmap_*: once, at the start of the call

@@ -513,7 +513,8 @@ inline void fetch(tr_ctx *c, VoxelCaches &vc) {
 }  // namespace detail
 
 /// AbstractVoxelValidityChecker::voxelize for a batch of states (VoxelCachedLazyPRM.cpp:2816-2823):
-/// the backbone voxel set of every shape-valid state, plus fk_shape.p.back() as the vertex tip.
+/// the backbone voxel set of every shape-valid state, plus fk_shape.p.back() as the vertex tip.  After setLoads the shapes are the
+/// loaded ones (tr_voxelize_batch_loaded).
 inline VoxelCaches voxelize_states(const VoxelBackboneValidityChecker &vc, const std::vector<double> &states, size_t n,
                                    std::vector<double> *tips = nullptr) {
   if (states.size() != n * vc.robot().state_size()) throw std::invalid_argument("State is not the right size");
@@ -521,8 +522,12 @@ inline VoxelCaches voxelize_states(const VoxelBackboneValidityChecker &vc, const
   out.offsets.assign(n + 1, 0);
   std::vector<uint64_t> bits((n + 63) / 64);
   if (tips) tips->resize(3 * n);
-  check(vc.context(), tr_voxelize_batch(vc.context(), states.data(), (int64_t)n, out.offsets.data(), bits.data(),
-                                        tips ? tips->data() : nullptr));
+  if (const tr_edge_loads *ld = vc.loads())               // the checker's FK is the loaded one (setLoads)
+    check(vc.context(), tr_voxelize_batch_loaded(vc.context(), nullptr, ld, states.data(), (int64_t)n, out.offsets.data(), bits.data(),
+                                                 tips ? tips->data() : nullptr, nullptr, nullptr));
+  else
+    check(vc.context(), tr_voxelize_batch(vc.context(), states.data(), (int64_t)n, out.offsets.data(), bits.data(),
+                                          tips ? tips->data() : nullptr));
   out.usable = detail::unpack(bits, n);
   detail::fetch(vc.context(), out);
   return out;
@@ -610,12 +615,21 @@ class VoxelBackboneMotionValidator {
     VoxelCaches out;
     out.offsets.assign(n + 1, 0);
     std::vector<uint64_t> bits((n + 63) / 64);
-    check(vc_.context(), (validate ? tr_connect_edges_indexed : tr_voxelize_edges_indexed)(
-                             vc_.context(), &space, states.data(), (int64_t)n_states, edges.data(), (int64_t)n,
-                             out.offsets.data(), bits.data(), nullptr));
+    check(vc_.context(), indexed_lists(vc_, space, states.data(), (int64_t)n_states, edges.data(), (int64_t)n, validate, out.offsets.data(),
+                                       bits.data(), nullptr));
     out.usable = detail::unpack(bits, n);
     detail::fetch(vc_.context(), out);
     return out;
+  }
+  /// tr_voxelize_edges_indexed / tr_connect_edges_indexed (validate), or after setLoads their loaded forms (n_unconverged and
+  /// n_integrations, optional, are theirs; without loads they stay as they are)
+  static int indexed_lists(const VoxelBackboneValidityChecker &vc, const tr_space_params &sp, const double *states, int64_t n_states,
+                           const int32_t *edges, int64_t n, bool validate, int64_t *offsets, uint64_t *bits, int32_t *n_fk,
+                           int64_t *n_unconverged = nullptr, int64_t *n_integrations = nullptr) {
+    if (const tr_edge_loads *ld = vc.loads())             // the checker's FK is the loaded one (setLoads)
+      return (validate ? tr_connect_edges_loaded_indexed : tr_voxelize_edges_loaded_indexed)(vc.context(), &sp, nullptr, ld, states, n_states, edges, n,
+                                                                                             offsets, bits, n_fk, n_unconverged, n_integrations);
+    return (validate ? tr_connect_edges_indexed : tr_voxelize_edges_indexed)(vc.context(), &sp, states, n_states, edges, n, offsets, bits, n_fk);
   }
   /// CompoundStateSpace::interpolate as wired by Problem.cpp:101-163: linear, shortest arc on the SO2 rotation
   std::vector<double> interpolate(const std::vector<double> &a, const std::vector<double> &b, double t) const {
@@ -738,6 +752,8 @@ class VoxelCachedLazyPRM {
   struct BuildReport {
     std::vector<int32_t> candidate_edges; std::vector<bool> accepted; std::vector<int32_t> n_fk;
     int64_t candidates_tried = 0; std::vector<int64_t> candidate_index; int32_t k = 0; double max_distance = 0;
+    /// a build under setLoads: shootings that did not converge (invalid candidates / samples) and integrations, vertex phase + edge phase
+    int64_t n_unconverged = 0, n_integrations = 0;
   };
 
   /// a planner with an empty roadmap: createRoadmap / precompute* build it (`mv` supplies checkMotion and the space resolution)
@@ -823,7 +839,11 @@ class VoxelCachedLazyPRM {
       next_candidate_ += add;
     } else if (validate_verts) {                                                 // ... until valid shape and no collision (:1421-1436)
       int64_t acc = 0, tried = 0;
-      check(c, tr_sample_valid_vertices(c, seed_, first, lo, hi, (int64_t)add, 0, st.data(), tips.data(), report_.candidate_index.data(), &acc, &tried));
+      if (const tr_edge_loads *ld = vc_.loads())          // the checker's FK is the loaded one (setLoads)
+        check(c, tr_sample_valid_vertices_loaded(c, nullptr, ld, seed_, first, lo, hi, (int64_t)add, 0, st.data(), tips.data(),
+                                                 report_.candidate_index.data(), nullptr, &acc, &tried, &report_.n_unconverged, &report_.n_integrations));
+      else
+        check(c, tr_sample_valid_vertices(c, seed_, first, lo, hi, (int64_t)add, 0, st.data(), tips.data(), report_.candidate_index.data(), &acc, &tried));
       if ((size_t)acc < add) throw std::runtime_error("createRoadmap: only " + std::to_string(acc) + " valid milestones in " + std::to_string(tried) + " candidates");
       next_candidate_ += (uint64_t)tried;
     } else {                                                                     // ... until valid shape (:1421-1426)
@@ -834,11 +854,19 @@ class VoxelCachedLazyPRM {
         std::vector<uint64_t> bits((m + 63) / 64);
         std::vector<uint8_t> flags(m);
         check(c, tr_candidate_states(c, seed_, next_candidate_, (int64_t)m, lo, hi, cand.data()));
-        check(c, tr_validate_batch(c, cand.data(), (int64_t)m, bits.data(), nullptr, flags.data()));
+        const tr_edge_loads *ld = vc_.loads();
+        if (ld) {                                         // is_valid_shape of the LOADED shapes: voxelizeVertex's own test
+          std::vector<int64_t> off(m + 1);
+          int64_t nu = 0, ni = 0;
+          check(c, tr_voxelize_batch_loaded(c, nullptr, ld, cand.data(), (int64_t)m, off.data(), bits.data(), nullptr, &nu, &ni));
+          report_.n_unconverged += nu; report_.n_integrations += ni;
+        } else {
+          check(c, tr_validate_batch(c, cand.data(), (int64_t)m, bits.data(), nullptr, flags.data()));
+        }
         const unsigned shape_ok = TR_FLAG_CONVERGED | TR_FLAG_LENGTH_OK | TR_FLAG_NO_SELFCOL;
         size_t used = m;
         for (size_t i = 0; i < m; i++) {
-          if ((flags[i] & (shape_ok | TR_FLAG_DOMAIN)) != shape_ok) continue;
+          if (ld ? !((bits[i >> 6] >> (i & 63)) & 1u) : (flags[i] & (shape_ok | TR_FLAG_DOMAIN)) != shape_ok) continue;
           std::copy(cand.begin() + i * S_, cand.begin() + (i + 1) * S_, st.begin() + have * S_);
           report_.candidate_index[have] = (int64_t)(next_candidate_ + i);
           if (++have == add) { used = i + 1; break; }
@@ -883,8 +911,10 @@ class VoxelCachedLazyPRM {
       enew.offsets.assign((size_t)ne + 1, 0);
       std::vector<uint64_t> bits((size_t)(ne + 63) / 64);
       report_.n_fk.resize((size_t)ne);
-      check(c, (validate_edges ? tr_connect_edges_indexed : tr_voxelize_edges_indexed)(
-                   c, &mv_->space, states_.data(), (int64_t)N, cand.data(), ne, enew.offsets.data(), bits.data(), report_.n_fk.data()));
+      int64_t nu = 0, ni = 0;
+      check(c, VoxelBackboneMotionValidator::indexed_lists(vc_, mv_->space, states_.data(), (int64_t)N, cand.data(), ne, validate_edges,
+                                                          enew.offsets.data(), bits.data(), report_.n_fk.data(), &nu, &ni));
+      report_.n_unconverged += nu; report_.n_integrations += ni;
       enew.usable = detail::unpack(bits, (size_t)ne);
       detail::fetch(c, enew);
       report_.accepted = enew.usable;
@@ -1044,6 +1074,7 @@ class VoxelCachedLazyPRM {
   /// removed from the roadmap.
   std::optional<IKResult> roadmapIk(const std::array<double, 3> &request, double tolerance = 1e-4, size_t k = 5, int opts = RMAP_IK_SIMPLE) {
     if (opts != RMAP_IK_SIMPLE) throw std::invalid_argument("roadmapIk: only RMAP_IK_SIMPLE is supported");
+    refuse_loaded("roadmapIk");
     absorb();
     const auto &rb = vc_.robot();
     auto tip_dist2 = [&](const double *t) {
@@ -1128,6 +1159,7 @@ class VoxelCachedLazyPRM {
   /// solutions whose tip is nearest the request.
   TipResults roadmapIkBatch(const std::vector<std::array<double, 3>> &requests, double tolerance = 1e-4, size_t k = 5) {
     need_validators("roadmapIkBatch");
+    refuse_loaded("roadmapIkBatch");
     sync_tips();
     const size_t n = requests.size();
     TipResults r = tip_results(n);
@@ -1142,6 +1174,7 @@ class VoxelCachedLazyPRM {
                           size_t k = 5, int n_threads = 0) {
     if (starts.size() != requests.size()) throw std::invalid_argument("starts and requests differ in length");
     need_validators("solveToTips");
+    refuse_loaded("solveToTips");
     sync_tips();
     const size_t n = requests.size();
     TipSolution s;
@@ -1184,6 +1217,10 @@ class VoxelCachedLazyPRM {
   }
   void need_validators(const char *what) const {
     if (!mv_) throw std::runtime_error(std::string(what) + ": missing voxel motion validator");      // the reference's setup_ == false (:1286-1298)
+  }
+  /// tip inverse kinematics under load does not exist: a checker with loads (setLoads) would be answered with unloaded shapes
+  void refuse_loaded(const char *what) const {
+    if (vc_.loads()) throw std::logic_error(std::string(what) + " is not built for a checker with loads (setLoads): tip inverse kinematics under load does not exist");
   }
   TipResults tip_results(size_t n) const {
     TipResults r;
@@ -1267,8 +1304,8 @@ class VoxelCachedLazyPRM {
     VoxelCaches got;
     got.offsets.assign(list.size() + 1, 0);
     std::vector<uint64_t> bits((list.size() + 63) / 64);
-    check(c, (collide ? tr_connect_edges_indexed : tr_voxelize_edges_indexed)(c, &mv_->space, states_.data(), (int64_t)milestoneCount(), sub.data(),
-                                                                              (int64_t)list.size(), got.offsets.data(), bits.data(), nullptr));
+    check(c, VoxelBackboneMotionValidator::indexed_lists(vc_, mv_->space, states_.data(), (int64_t)milestoneCount(), sub.data(), (int64_t)list.size(),
+                                                        collide, got.offsets.data(), bits.data(), nullptr));
     got.usable = detail::unpack(bits, list.size());
     detail::fetch(c, got);
     detail::replace_items(ecache_, list, got);

@@ -41,6 +41,8 @@ ABI_SYMBOLS = (
     "tr_roadmap_tip_query_profile",
     "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev",
     "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
+    "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
+    "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
 )
 
 
@@ -355,6 +357,11 @@ def lib():
     L.tr_validate_edges_loaded_indexed.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, i64, i32p, i64, P(C.c_uint64), i32p, P(i64), P(i64), P(i64)]
     L.tr_edges_loaded_vertex_strains.argtypes = [vp, i64, dp]
     L.tr_edges_loaded_last.argtypes = [vp, P(i64)]
+    L.tr_sample_valid_vertices_loaded.argtypes = [vp, shp, elp, u64, u64, dp, dp, i64, i64, dp, dp, P(i64), dp, P(i64), P(i64), P(i64), P(i64)]
+    L.tr_sample_valid_vertices_loaded_dev.argtypes = [vp, shp, elp, u64, u64, dp, dp, i64, i64, vp, vp, vp, vp, P(i64), P(i64), P(i64), P(i64), vp]
+    L.tr_voxelize_batch_loaded.argtypes = [vp, shp, elp, dp, i64, P(i64), P(C.c_uint64), dp, P(i64), P(i64)]
+    L.tr_voxelize_edges_loaded_indexed.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, i64, i32p, i64, P(i64), P(C.c_uint64), i32p, P(i64), P(i64)]
+    L.tr_connect_edges_loaded_indexed.argtypes = L.tr_voxelize_edges_loaded_indexed.argtypes
     tqp = P(TrTipQueryParams)
     L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
     L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]

@@ -20,6 +20,7 @@ struct LoadedEdges {
   tr_ctx *c; trk::ShootParams prm; trk::EdgeLoadsK loads; bool warm;
   int64_t rounds = 0;                  // Levenberg-Marquardt rounds of all solves (one host synchronisation each)
   int64_t n_samples = 0, n_levels = 0, n_chunks = 0;     // evaluated (retried chunks included), evaluator calls, chunk attempts
+  EdgeVoxOut *vox = nullptr;           // the voxelize / connect forms (loaded_roadmap_host.inc): the run's vox branch on the workspace planes
 
   // what tr_edges_loaded_last reports
   void note() {
@@ -103,7 +104,7 @@ struct LoadedEdges {
     int rc;
     n_chunks++;
     if ((rc = ensure_edge_dev(c, c->ws.ld)) || (rc = ensure_edge_lanes(c)) || (rc = clear_tally())) return rc;
-    EdgeRun r{c, sp, A, B, e0, e1, &ok, &nfk, nd, nullptr, last_valid, ix};
+    EdgeRun r{c, sp, A, B, e0, e1, &ok, &nfk, nd, vox, last_valid, ix};
     r.L = EdgeLane{nullptr, 0, ix ? ix->pool_base : 0, c->ws.ld, 0, 0, c->lane[0].counters, c->lane[0].hc};
     r.eval = [this](EdgeRun &run, int64_t s0, int64_t m) {
       return samples(run.lvl_states, s0, m, s0 == 0 ? nullptr : run.open, run.sample_test);      // (s0 == 0: the end states of pairwise edges)
@@ -122,8 +123,10 @@ struct LoadedEdges {
             std::vector<int32_t> &nfk, int64_t *n_domain, double *last_valid, const EdgeIndexed *ix, int64_t *n_unconverged, int64_t *n_integrations) {
     for (int64_t e = e0; e < e1; e++) { ok[(size_t)e] = 1; nfk[(size_t)e] = 0; }
     int64_t nd = 0;
+    const int64_t vox_mark = c->vstore.n;
     int rc = chunk(sp, A, B, e0, e1, ok, nfk, &nd, last_valid, ix, n_unconverged, n_integrations);
     if (rc == EDGE_OVERFLOW) {
+      if (vox) c->vstore.n = vox_mark;
       if (e1 - e0 <= 1) return fail(c, TR_ERR_RUNTIME, "an edge needs more FK samples than the workspace holds");
       const int64_t mid = e0 + (e1 - e0) / 2;
       if ((rc = range(sp, A, B, e0, mid, ok, nfk, n_domain, last_valid, ix, n_unconverged, n_integrations))) return rc;

@@ -43,6 +43,7 @@
 #include "ik_kernel.hpp"
 #include "fk_loaded_kernel.hpp"
 #include "loaded_edge_kernel.hpp"
+#include "loaded_roadmap_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
 struct tr_ctx;
@@ -277,7 +278,13 @@ struct tr_ctx {
     int32_t *calls = nullptr;
     unsigned long long *tally = nullptr;
     int64_t last[4] = {0, 0, 0, 0};         // tr_edges_loaded_last
+    // the loaded vertex phase (loaded_roadmap_host.inc): the accepted strain rows and candidate indices when the caller keeps none;
+    // its tally (unconverged candidates and integrations among those tried); the acceptance rate last seen
+    double *out_vu = nullptr; int64_t *out_index = nullptr; int64_t out_cap = 0;
+    unsigned long long *vtally = nullptr;
+    double rate_seen = 0.0;
   } ledge;
+  int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
   bool profiling = false;
@@ -991,6 +998,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
     if (v >= 256 && v <= (1ll << 24)) c->edge_pool_max = c->edge_slots_max = (int64_t)round_up(v, 64);
   }
   if (const char *e = std::getenv("TENDON_HIP_SHOOT_CHUNK")) { const long long v = std::atoll(e); if (v >= 1 && v <= (1ll << 20)) c->shoot_chunk = (int64_t)v; }
+  if (const char *e = std::getenv("TENDON_HIP_LOADED_VERTEX_BATCH")) { const long long v = std::atoll(e); if (v >= 64 && v <= (1ll << 20)) c->loaded_vertex_batch = (int64_t)round_up(v, 64); }
   if (hipSetDevice(device) != hipSuccess) { delete c; return fail(nullptr, TR_ERR_HIP, "hipSetDevice failed"); }
   {
     int cus = 0;
@@ -1143,7 +1151,7 @@ void tr_destroy(tr_ctx *c) {
   shoot_release(c);
   {
     tr_ctx::LoadedEdgeDev &le = c->ledge;
-    void *lp[] = {le.vu_pool, le.w, le.d, le.g, le.calls, le.tally};
+    void *lp[] = {le.vu_pool, le.w, le.d, le.g, le.calls, le.tally, le.out_vu, le.out_index, le.vtally};
     for (void *q : lp) if (q) (void)hipFree(q);
   }
   delete c;
@@ -2254,3 +2262,4 @@ int tr_profile_end(tr_ctx *c) {
 #include "ik_host.inc"
 #include "loaded_host.inc"
 #include "loaded_edges_host.inc"
+#include "loaded_roadmap_host.inc"

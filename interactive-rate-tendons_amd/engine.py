@@ -523,6 +523,73 @@ class Engine:
         L.check(self._ctx, self.lib.tr_edges_loaded_vertex_strains(self._ctx, int(n_states), _dp(out)))
         return out
 
+    # ---- the roadmap build on loaded shapes (tr_sample_valid_vertices_loaded .. tr_connect_edges_loaded_indexed, include/tendon_hip.h) ----
+    _SHOOT_DEFAULTS = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6)
+
+    def sample_valid_vertices_loaded(self, n_want, wrench=None, dist=None, frame="base", seed=0, first_candidate=0, box=None,
+                                     max_candidates=0, want_index=False, warm_start=None, **shoot):
+        """sample_valid_vertices on LOADED shapes: the first n_want candidates of the sequence whose shape under the load (cold
+        start; frame='world': the candidate's rows turned by Rz(-theta)) is valid under the installed checker.  Returns
+        dict(states, tips, index (None without want_index), vu0 (accepted base strains), accepted, tried, n_unconverged,
+        n_integrations -- sums over the `tried` candidates).  warm_start is accepted and ignored: every vertex starts cold."""
+        keep, plo, phi = self._box(box)
+        n_want = int(n_want)
+        ld = self._edge_loads(wrench, dist, frame, False)
+        prm = self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+        states = np.empty((n_want, self.state_size))
+        tips = np.empty((n_want, 3))
+        vu0 = np.empty((n_want, 6))
+        index = np.empty(n_want, dtype=np.int64) if want_index else None
+        n_acc, n_tried, nu, ni = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_sample_valid_vertices_loaded(
+            self._ctx, C.byref(prm), C.byref(ld), int(seed), int(first_candidate), plo, phi, n_want, int(max_candidates), _dp(states),
+            _dp(tips), index.ctypes.data_as(C.POINTER(C.c_int64)) if want_index else None, _dp(vu0), C.byref(n_acc), C.byref(n_tried),
+            C.byref(nu), C.byref(ni)))
+        k = n_acc.value
+        return dict(states=states[:k], tips=tips[:k], index=index[:k] if want_index else None, vu0=vu0[:k], accepted=k,
+                    tried=n_tried.value, n_unconverged=int(nu.value), n_integrations=int(ni.value))
+
+    def voxelize_batch_loaded(self, states, wrench=None, dist=None, frame="base", device=False, warm_start=None, **shoot):
+        """voxelize_batch on LOADED shapes (cold start): CSR (offsets, block_ids, masks), shape validity, tips, n_unconverged,
+        n_integrations."""
+        st = self._states(states)
+        n = st.shape[0]
+        ld = self._edge_loads(wrench, dist, frame, False)
+        prm = self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        tips = np.empty((n, 3))
+        nu, ni = C.c_int64(0), C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_voxelize_batch_loaded(self._ctx, C.byref(prm), C.byref(ld), _dp(st), n,
+                                                             offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                             bits.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(tips), C.byref(nu), C.byref(ni)))
+        ids, masks = self._fetch_lists(int(offsets[-1]), device)
+        return dict(offsets=offsets, block_ids=ids, masks=masks, shape_valid=unpack_bits(bits, n), tips=tips,
+                    n_unconverged=int(nu.value), n_integrations=int(ni.value))
+
+    def voxelize_edges_loaded_indexed(self, states, edges, wrench=None, dist=None, frame="base", warm_start=None, min_tension_change=0.02,
+                                      min_rotation_change=0.01, min_retraction_change=0.0001, device=False, validate=False, **shoot):
+        """voxelize_edges_indexed on LOADED samples (validate=True: tr_connect_edges_loaded_indexed): the bisection of
+        validate_edges_loaded_indexed with the voxelize forms' sample tests and block lists."""
+        st = self._states(states)
+        e = np.ascontiguousarray(np.asarray(edges).reshape(-1, 2), dtype=np.int32)
+        n = e.shape[0]
+        sp = L.TrSpaceParams(min_tension_change, min_rotation_change, min_retraction_change)
+        ld = self._edge_loads(wrench, dist, frame, warm_start)
+        prm = self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        nfk = np.zeros(n, dtype=np.int32)
+        nu, ni = C.c_int64(0), C.c_int64(0)
+        fn = self.lib.tr_connect_edges_loaded_indexed if validate else self.lib.tr_voxelize_edges_loaded_indexed
+        L.check(self._ctx, fn(
+            self._ctx, C.byref(sp), C.byref(prm), C.byref(ld), _dp(st), st.shape[0], e.ctypes.data_as(C.POINTER(C.c_int32)), n,
+            offsets.ctypes.data_as(C.POINTER(C.c_int64)), bits.ctypes.data_as(C.POINTER(C.c_uint64)),
+            nfk.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nu), C.byref(ni)))
+        ids, masks = self._fetch_lists(int(offsets[-1]), device)
+        return dict(offsets=offsets, block_ids=ids, masks=masks, fully_valid=unpack_bits(bits, n), n_fk=nfk,
+                    n_unconverged=int(nu.value), n_integrations=int(ni.value))
+
     def validate_edges_discrete(self, a, b, min_tension_change=0.02, min_rotation_change=0.01,
                                 min_retraction_change=0.0001, last_valid=True):
         """last_valid = True: checkMotion(s1, s2, last_valid) (the installed state checker judges every sample);

@@ -160,7 +160,8 @@ class VoxelBackboneValidityChecker:
     def set_loads(self, wrench=None, dist=None, frame="base", warm_start=None, **shoot):
         """wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, one (6,) row each (None: zero).  frame='base': fixed before the
         state's rotation (fk_loaded_batch's frame); 'world': fixed behind it, every state's rows turned by Rz(-theta).  Afterwards
-        is_valid and the motion validators on this checker judge LOADED shapes; clear_loads() restores the unloaded checks."""
+        is_valid and the motion validators on this checker judge LOADED shapes, and a RoadmapBuilder on it builds on them (vertex
+        phase, connect, both voxel caches; roadmap.py); clear_loads() restores the unloaded checks."""
         self.engine._edge_loads(wrench, dist, frame, warm_start)              # argument checks
         self._loads = dict(wrench=wrench, dist=dist, frame=frame, warm_start=warm_start, **shoot)
 

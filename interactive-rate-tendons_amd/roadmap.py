@@ -21,6 +21,16 @@ class RoadmapBuilder:
         self.seed, self.tau_max = seed, tau_max
         self.timing = {}
 
+    def _loads(self):
+        """The checker's load set (set_loads), or None: with one, every phase takes its shapes from the loaded FK, as the reference's
+        loops do after set_fk_func (they all go through voxelStateChecker_->fk)."""
+        return self.checker.loads() if hasattr(self.checker, "loads") else None
+
+    def _refuse_loaded(self, what):
+        if self._loads() is not None:
+            raise L.Unsupported("%s is not built for loaded shapes (set_loads): it would answer with unloaded shapes; "
+                                "use create_roadmap, or clear_loads()" % what)
+
     # ---- createRoadmap phase 1: rejection sampling until N valid vertices ----------------------------
     def sample_valid_vertices(self, N, batch=None):
         """createRoadmap's vertex phase on the device (tr_sample_valid_vertices): the candidates are a counter-based sequence
@@ -29,9 +39,17 @@ class RoadmapBuilder:
         is a deterministic prefix-filter of the sequence (independent of the batch sizes; `batch` is accepted and ignored)."""
         t0 = time.perf_counter()
         box = D.sampling_box(self.robot, self.tau_max)
+        loads = self._loads()
         try:
-            out = self.engine.sample_valid_vertices(N, seed=self.seed, box=box)
+            if loads is not None:               # (its own Unsupported -- a retraction robot -- is the caller's: no unloaded way round)
+                out = self.engine.sample_valid_vertices_loaded(N, seed=self.seed, box=box, **loads)
+                self.timing["vertices_loaded"] = dict(n_unconverged=out["n_unconverged"], n_integrations=out["n_integrations"],
+                                                      **self.engine.edges_loaded_last())
+            else:
+                out = self.engine.sample_valid_vertices(N, seed=self.seed, box=box)
         except L.Unsupported:
+            if loads is not None:
+                raise
             # a context on another schedule than the verdict-only one (TENDON_HIP_FUSED=0 / 1: A/B runs): the rejection loop over
             # batches of the SAME candidate sequence through validate_candidates -- the same accepted set, candidate by candidate
             out = self._sample_valid_vertices_batches(N, box, batch or (1 << 16))
@@ -98,6 +116,7 @@ class RoadmapBuilder:
         builder renumbers by backbone length (sample_valid_vertices) and this call leaves in acceptance order: the same vertex SET and
         the same edges between them, under different indices."""
         import torch
+        self._refuse_loaded("the device-resident build (build_on_device)")
         t0 = time.perf_counter()
         eng, dev = self.engine, "cuda:%d" % self.engine.device
         n, S, sw = int(n_vertices), eng.state_size, eng.signature_words()
@@ -149,7 +168,9 @@ class RoadmapBuilder:
         """voxelizeVertex for every vertex.  device=True: block ids / masks stay in HBM as torch tensors (for
         VoxelCachedLazyPRM.set_caches / DeviceCaches on the same GPU); offsets and flags are host arrays either way."""
         t0 = time.perf_counter()
-        out = self.engine.voxelize_batch(states, device=device)
+        loads = self._loads()
+        out = self.engine.voxelize_batch(states, device=device) if loads is None else \
+            self.engine.voxelize_batch_loaded(states, device=device, **loads)
         self.timing["vertex_caches"] = dict(seconds=time.perf_counter() - t0, items=len(states), blocks=int(out["offsets"][-1]))
         return out
 
@@ -160,6 +181,7 @@ class RoadmapBuilder:
         and d_vertex_sig (the vertices' signature rows gathered with the vertex mask, ShardedVertexValidator.run_with_rows) select
         the device-resident form: with the signatures no rank integrates the vertices again."""
         import torch
+        self._refuse_loaded("the sharded edge validation (validate_edges_sharded)")
         dev = device if device is not None else ("cuda:%d" % self.engine.device if torch.cuda.is_available() else "cpu")
         mv = self.mv
         if d_states is not None:
@@ -190,12 +212,23 @@ class RoadmapBuilder:
         self.timing["knn_sharded"] = dict(seconds=time.perf_counter() - t0, n=len(st), k=k, edges=len(edges))
         return edges
 
+    def _voxelize_edges_indexed(self, states, edges, device, validate):
+        mv, loads = self.mv, self._loads()
+        if loads is None:
+            return self.engine.voxelize_edges_indexed(states, edges, mv.min_tension_change, mv.min_rotation_change, mv.min_retraction_change,
+                                                      device=device, validate=validate)
+        out = self.engine.voxelize_edges_loaded_indexed(states, edges, min_tension_change=mv.min_tension_change,
+                                                        min_rotation_change=mv.min_rotation_change,
+                                                        min_retraction_change=mv.min_retraction_change, device=device, validate=validate, **loads)
+        self.timing["edges_loaded"] = dict(n_unconverged=out["n_unconverged"], n_integrations=out["n_integrations"],
+                                           **self.engine.edges_loaded_last())
+        return out
+
     def connect(self, states, edges, device=False):
         """createRoadmap's edge phase in one pass (tr_connect_edges_indexed): checkMotion on every candidate edge and the voxel
         sets of the accepted ones -> (accepted edges, their caches as CSR over the accepted edges only)."""
         t0 = time.perf_counter()
-        out = self.engine.voxelize_edges_indexed(states, edges, self.mv.min_tension_change, self.mv.min_rotation_change,
-                                                 self.mv.min_retraction_change, device=device, validate=True)
+        out = self._voxelize_edges_indexed(states, edges, device, True)
         keep = np.flatnonzero(out["fully_valid"])                      # (one index list for all four selections: boolean masks re-scan per use)
         off = out["offsets"]
         new_off = np.empty(len(keep) + 1, dtype=off.dtype)              # rejected edges own nothing: dropping them leaves the lists as they are
@@ -250,8 +283,7 @@ class RoadmapBuilder:
 
     def edge_caches(self, states, edges, device=False):
         t0 = time.perf_counter()
-        out = self.engine.voxelize_edges_indexed(states, edges, self.mv.min_tension_change,
-                                                 self.mv.min_rotation_change, self.mv.min_retraction_change, device=device)
+        out = self._voxelize_edges_indexed(states, edges, device, False)
         self.timing["edge_caches"] = dict(seconds=time.perf_counter() - t0, items=len(edges), blocks=int(out["offsets"][-1]))
         return out
 
@@ -565,6 +597,13 @@ class VoxelCachedLazyPRM:
         pd = eng._check_dev(d_dist2, torch.float64, n * k, "d_dist2") if d_dist2 is not None else None
         self._check(self.lib.tr_roadmap_nearest_tips_dev(self._rm, pr, int(n), int(k), pv, pd))
 
+    def _refuse_loaded(self, what):
+        """Tip IK under load does not exist: a roadmap whose checker has loads (set_loads) would be joined to goal states found on
+        unloaded shapes."""
+        if getattr(self.checker, "loads", None) is not None and self.checker.loads() is not None:
+            raise self._L.Unsupported("%s is not built for a checker with loads (set_loads): tip inverse kinematics under load "
+                                      "does not exist; clear_loads() for unloaded tip queries" % what)
+
     def _tip_params(self, k, tolerance, ik, motion_validator):
         L_ = self._L
         ikd = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, stop_threshold_err=tolerance,
@@ -597,6 +636,7 @@ class VoxelCachedLazyPRM:
         error, neighbor_vertex, outcome (TR_TIPQ_*), last_valid_t).  motion_validator: its state-space resolutions (None: the
         defaults of Problem); ik: overrides of the IK arguments."""
         C = self._C
+        self._refuse_loaded("roadmap_ik_batch")
         r = self._requests(requests)
         n = len(r)
         prm, sp = self._tip_params(k, tolerance, ik, motion_validator)
@@ -612,6 +652,7 @@ class VoxelCachedLazyPRM:
         cost = roadmap cost + state-space distance from the connection vertex to the goal state (`controls`), which follows the
         last vertex of paths[q].  A request without a neighbour ends TR_QUERY_INVALID_GOAL."""
         C, L_ = self._C, self._L
+        self._refuse_loaded("solve_to_tips")
         r = self._requests(requests)
         n = len(r)
         s = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
@@ -683,6 +724,7 @@ def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_valid
     roadmap from the connection vertex.  A chain stops at its first hop that is not solved.
     -> dict(hops: per hop the solve_to_tips result plus start_state (C, S), prefix_cost (C,), total_cost (C,), active (C,);
             cost (C,): the sum over the chain's solved hops; solved (C,): every hop solved)."""
+    prm._refuse_loaded("chained_plan")
     wp = np.asarray(waypoints, dtype=np.float64)
     if wp.ndim == 2:
         wp = wp[None]
