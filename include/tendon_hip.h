@@ -483,6 +483,38 @@ int tr_connect_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, cons
                                     const double *states, int64_t n_states, const int32_t *edges, int64_t n_edges, int64_t *offsets,
                                     uint64_t *valid_bits, int32_t *n_fk, int64_t *n_unconverged, int64_t *n_integrations);
 
+/* ---- tip inverse kinematics on loaded shapes --------------------------------------------- */
+
+/* tip_control::inverse_kinematics (tip-control/tip_control.cpp:35-140) takes any FKFunc; with TendonRobot::general_shape installed
+ * it solves for the tip of the LOADED shape.  These calls are tr_ik_batch for that case: the same projected Levenberg-Marquardt on
+ * the state, bounds, stop tests and canonical rotation (`params`, NULL: tr_ik_batch's defaults), under ONE load set per call
+ * (`loads`, tr_edge_loads' meaning of BASE and WORLD; NULL: no load; warm_start is not read).
+ * The tip Jacobian is not differenced through shooting solves.  At base strains y that balance the tip, e_w(y, p) = 0, the tip
+ * x(y, p) moves with the state as dx/dp = X_p - X_y J_y^-1 J_p; the four blocks are central differences of 13 + 2 S integrations
+ * from one point (the state's steps are levmar's max(|1e-4 p|, delta), the strains' the shooting's finite_difference_delta itself).
+ * Per outer round every active problem's trial state is equilibrated by tr_fk_loaded_batch's shooting (`shoot`, NULL: its defaults
+ * with stop_threshold_Dp = 0 -- the steps from a predicted start are small by construction) from the predicted strains y - J_y^-1 J_p (p_trial - p); a trial whose shooting does not converge is a
+ * rejected step, a start whose shooting does not converge ends its problem (equilibrium = 0, error = inf, tip = NaN).
+ *   initial_states  n x S, clipped to the bounds;  des: goals, row i at des + i des_ld (des_ld = 0: one goal for all)
+ *   lo, hi          S bounds each, or NULL: Bounds::from_robot
+ *   guess           optional n x 6 start strains (v0, u0) of the starts' shooting (NULL: the unloaded solution)
+ *   states_out n x S, tips_out n x 3 (the loaded tip at states_out), error_out n (|des - tip|), iters_out n (outer iterations),
+ *   fk_calls_out n (integrations: the shooting's and the 13 + 2 S per round), vu0_out n x 6 (the base strains of the returned
+ *   state's equilibrium: tr_fk_loaded_batch's `guess` for it), equilibrium_out n -- all optional
+ *   rounds_out      optional int64[2]: outer rounds, shooting rounds (one host synchronisation each)
+ * Robots with retraction: TR_ERR_UNSUPPORTED; a bad frame or lo > hi: TR_ERR_INVALID_ARG; n == 0: TR_OK.  A problem's result does
+ * not depend on the batch size, the order, the chunking (TENDON_HIP_SHOOT_CHUNK) or the other problems of the call. */
+int tr_ik_loaded_batch(tr_ctx *ctx, const tr_ik_params *params, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                       const double *initial_states, int64_t n, const double *des, int64_t des_ld, const double *lo, const double *hi,
+                       const double *guess, double *states_out, double *tips_out, double *error_out, int32_t *iters_out,
+                       int32_t *fk_calls_out, double *vu0_out, uint8_t *equilibrium_out, int64_t *rounds_out);
+/* ... with device arrays (lo, hi and rounds_out stay host pointers); the run is ordered on `stream` and ends synchronised. */
+int tr_ik_loaded_batch_dev(tr_ctx *ctx, const tr_ik_params *params, const tr_shoot_params *shoot, const tr_edge_loads *loads,
+                           const double *d_initial_states, int64_t n, const double *d_des, int64_t des_ld, const double *lo,
+                           const double *hi, const double *d_guess, double *d_states_out, double *d_tips_out, double *d_error_out,
+                           int32_t *d_iters_out, int32_t *d_fk_calls_out, double *d_vu0_out, uint8_t *d_equilibrium_out,
+                           int64_t *rounds_out, void *stream);
+
 /* ---- cached voxel sets vs obstacles: VoxelOctree::collides on roadmap caches ------------ */
 
 /* Batched `obstacles.collides(*cached_voxels)` for roadmap vertices / edges

@@ -342,6 +342,69 @@ inline IKResult inverse_kinematics(const tendon::TendonRobot &robot, const std::
                                   stop_threshold_err, finite_difference_delta)[0];
 }
 
+/// What inverseKinematicsLoaded* return per problem beyond IKResult: the base strains (v0, u0) of the returned state's equilibrium
+/// (generalShape's guess for it) and whether the start reached one (false: error = inf, no iteration was made)
+struct LoadedIKResult : IKResult {
+  std::array<double, 6> vu0{};
+  bool equilibrium = false;
+};
+
+/// Solver arguments of inverseKinematicsLoaded*: tip_control.h:88-100's, and the load's frame
+struct LoadedIKOptions {
+  int max_iters = 100;
+  double mu_init = 0.1, stop_threshold_JT_err_inf = 1e-9, stop_threshold_Dp = 1e-4, stop_threshold_err = 1e-4, finite_difference_delta = 1e-6;
+  bool world = false;               // the load is fixed in the frame after the state's rotation (gravity), else before it
+  const Bounds *bounds = nullptr;   // null = Bounds::from_robot
+};
+
+/// inverse_kinematics with TendonRobot::general_shape as its FKFunc, for n start states at once (tr_ik_loaded_batch): `wrench` holds
+/// (F_e, L_e), `dist` (f_e, l_e) per unit length, 6 values each or empty (zero), ONE set per call.  One goal (`des` of size 1) or one
+/// per start.  rounds (optional): outer rounds, shooting rounds.
+inline std::vector<LoadedIKResult> inverseKinematicsLoadedBatch(const tendon::TendonRobot &robot, const std::vector<double> &initial_states,
+                                                                size_t n, const std::vector<std::array<double, 3>> &des,
+                                                                const std::vector<double> &wrench, const std::vector<double> &dist,
+                                                                const LoadedIKOptions &opt = LoadedIKOptions(), int64_t *rounds = nullptr) {
+  const size_t S = robot.state_size();
+  if (initial_states.size() != n * S) throw std::invalid_argument("State is not the right size");
+  if (des.size() != 1 && des.size() != n) throw std::invalid_argument("one goal, or one goal per start state");
+  if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6)) throw std::invalid_argument("loads: 6 values or none");
+  if (opt.bounds && (opt.bounds->lower.size() != S || opt.bounds->upper.size() != S)) throw std::invalid_argument("State is not the right size");
+  tr_ctx *c = robot.context();
+  const tr_ik_params prm{opt.max_iters, opt.mu_init, opt.stop_threshold_JT_err_inf, opt.stop_threshold_Dp, opt.stop_threshold_err,
+                         opt.finite_difference_delta};
+  tr_edge_loads ld{};
+  for (size_t q = 0; q < wrench.size(); q++) ld.wrench[q] = wrench[q];
+  for (size_t q = 0; q < dist.size(); q++) ld.dist[q] = dist[q];
+  ld.frame = opt.world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
+  std::vector<double> d(3 * des.size()), st(n * S), tips(3 * n), err(n), vu(6 * n);
+  for (size_t i = 0; i < des.size(); i++) for (int k = 0; k < 3; k++) d[3 * i + k] = des[i][k];
+  std::vector<int32_t> iters(n), calls(n);
+  std::vector<uint8_t> eq(n);
+  int64_t r2[2] = {0, 0};
+  check(c, tr_ik_loaded_batch(c, &prm, nullptr, (wrench.empty() && dist.empty()) ? nullptr : &ld, initial_states.data(), (int64_t)n, d.data(),
+                              des.size() == 1 ? 0 : 3, opt.bounds ? opt.bounds->lower.data() : nullptr,
+                              opt.bounds ? opt.bounds->upper.data() : nullptr, nullptr, st.data(), tips.data(), err.data(), iters.data(),
+                              calls.data(), vu.data(), eq.data(), r2));
+  if (rounds) { rounds[0] = r2[0]; rounds[1] = r2[1]; }
+  std::vector<LoadedIKResult> out(n);
+  for (size_t i = 0; i < n; i++) {
+    out[i].state.assign(st.begin() + i * S, st.begin() + (i + 1) * S);
+    out[i].tip = {tips[3 * i], tips[3 * i + 1], tips[3 * i + 2]};
+    out[i].error = err[i]; out[i].iters = iters[i]; out[i].num_fk_calls = calls[i];
+    for (int q = 0; q < 6; q++) out[i].vu0[q] = vu[6 * i + q];
+    out[i].equilibrium = eq[i] != 0;
+  }
+  return out;
+}
+
+/// ... for one start state
+inline LoadedIKResult inverseKinematicsLoaded(const tendon::TendonRobot &robot, const std::vector<double> &initial_state,
+                                              const std::array<double, 3> &des, const std::vector<double> &wrench,
+                                              const std::vector<double> &dist, const LoadedIKOptions &opt = LoadedIKOptions()) {
+  if (initial_state.size() != robot.state_size()) throw std::invalid_argument("State is not the right size");
+  return inverseKinematicsLoadedBatch(robot, initial_state, 1, {des}, wrench, dist, opt)[0];
+}
+
 }  // namespace tip_control
 
 namespace collision {

@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
     "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
     "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
+    "tr_ik_loaded_batch", "tr_ik_loaded_batch_dev",
 )
 
 
@@ -136,13 +137,15 @@ OBJ_DIR = os.path.join(SRC_DIR, "_obj")
 def _units():
     """(object name, source, extra flags): the C ABI + K2..K6, the cache merge, and K1 once per
     (tendon count, kernel: shared grid / retraction / fused with K2 / verdict-only / verdict-only with retraction / edge queue /
-    loaded) so its instantiations compile in parallel."""
+    loaded) so its instantiations compile in parallel, and the linearisation kernel of the loaded IK once per tendon count
+    (fk_lin_inst.hip: files of its own, so the K1 units keep their dependencies)."""
     fk_deps = ["fk_inst.hip", "fk_launch.hpp", "fk_kernel.hpp", "fk_retract_kernel.hpp", "fused_kernel.hpp", "verdict_kernel.hpp",
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
                     "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp"]
-    fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp"] + roadmap_deps
+    fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
+               "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
     u = [("tendon_hip.o", "tendon_hip.hip", [], main_deps + [HEADER]),
          ("cache_merge.o", "cache_merge.hip", [], ["cache_merge.hip", "cache_merge.hpp"]),
@@ -154,6 +157,10 @@ def _units():
         for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l")):
             u.append(("fk_%s%d.o" % (tag, n), "fk_inst.hip", ["-DTRK_INST_N=%d" % n, "-DTRK_INST_KIND=%d" % kind],
                       q_deps if kind == 5 else (l_deps if kind == 6 else fk_deps)))
+    lin_deps = ["fk_lin_inst.hip", "fk_lin_launch.hpp", "fk_loaded_lin_kernel.hpp", "fk_loaded_kernel.hpp", "edge_sincos.hpp", "fk_launch.hpp",
+                "fk_kernel.hpp", "tr_types.hpp"]
+    for n in range(1, 9):
+        u.append(("fk_i%d.o" % n, "fk_lin_inst.hip", ["-DTRK_INST_N=%d" % n], lin_deps))
     return u
 
 
@@ -362,6 +369,8 @@ def lib():
     L.tr_voxelize_batch_loaded.argtypes = [vp, shp, elp, dp, i64, P(i64), P(C.c_uint64), dp, P(i64), P(i64)]
     L.tr_voxelize_edges_loaded_indexed.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, i64, i32p, i64, P(i64), P(C.c_uint64), i32p, P(i64), P(i64)]
     L.tr_connect_edges_loaded_indexed.argtypes = L.tr_voxelize_edges_loaded_indexed.argtypes
+    L.tr_ik_loaded_batch.argtypes = [vp, P(TrIkParams), shp, elp, dp, i64, dp, i64, dp, dp, dp, dp, dp, dp, i32p, i32p, dp, P(C.c_uint8), P(i64)]
+    L.tr_ik_loaded_batch_dev.argtypes = [vp, P(TrIkParams), shp, elp, vp, i64, vp, i64, dp, dp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     tqp = P(TrTipQueryParams)
     L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
     L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]

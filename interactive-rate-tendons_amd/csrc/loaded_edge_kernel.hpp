@@ -15,41 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "edge_kernel.hpp"
+#include "edge_sincos.hpp"
 
 namespace trk {
 
 struct EdgeLoadsK { double wrench[6], dist[6]; int32_t world, pad_; };
-
-// sin and cos of x, |x| of a few turns at most, to ~1e-16: k = rint(x 2/pi), r = (x - k hi) - k lo with hi the leading 33 bits of
-// pi/2 (k hi is exact), sin r and cos r by their Taylor polynomials to r^17 and r^18 (|r| <= pi/4: the next terms are below 1e-18)
-__device__ __host__ inline void edge_sincos(double x, double &s, double &c) {
-#pragma clang fp contract(off)
-  const double k = rint(x * 0.63661977236758138);                       // 2 / pi
-  const double r = (x - k * 1.57079632673412561417e+00) - k * 6.07710050650619224932e-11;
-  const double z = r * r;
-  double ps = 1.0 / 355687428096000.0;                                  // 1 / 17!
-  ps = -1.0 / 1307674368000.0 + z * ps;                                 // 15!
-  ps = 1.0 / 6227020800.0 + z * ps;                                     // 13!
-  ps = -1.0 / 39916800.0 + z * ps;                                      // 11!
-  ps = 1.0 / 362880.0 + z * ps;                                         // 9!
-  ps = -1.0 / 5040.0 + z * ps;                                          // 7!
-  ps = 1.0 / 120.0 + z * ps;                                            // 5!
-  ps = -1.0 / 6.0 + z * ps;                                             // 3!
-  const double sr = r + r * (z * ps);
-  double pc = -1.0 / 6402373705728000.0;                                // 18!
-  pc = 1.0 / 20922789888000.0 + z * pc;                                 // 16!
-  pc = -1.0 / 87178291200.0 + z * pc;                                   // 14!
-  pc = 1.0 / 479001600.0 + z * pc;                                      // 12!
-  pc = -1.0 / 3628800.0 + z * pc;                                       // 10!
-  pc = 1.0 / 40320.0 + z * pc;                                          // 8!
-  pc = -1.0 / 720.0 + z * pc;                                           // 6!
-  pc = 1.0 / 24.0 + z * pc;                                             // 4!
-  pc = -0.5 + z * pc;                                                   // 2!
-  const double cr = 1.0 + z * pc;
-  const int q = (int)((long long)k & 3);                                // quadrant (two's complement: also for negative k)
-  s = q == 0 ? sr : (q == 1 ? cr : (q == 2 ? -sr : -cr));
-  c = q == 0 ? cr : (q == 1 ? -sr : (q == 2 ? -cr : sr));
-}
 
 // rows [m][6] of the tip wrench and of the distributed load for the m states of a level; theta_col < 0: the rows are the call's
 __global__ __launch_bounds__(256) void loaded_sample_loads(const double *__restrict__ states, int64_t m, int S, int theta_col, EdgeLoadsK k,

@@ -133,7 +133,7 @@ int shoot_fk(tr_ctx *c, const double *d_states, int64_t lanes, int64_t ld, const
 int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, int64_t m, int64_t ld, const double *d_wrench,
                       int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess, const trk::FkOut &out,
                       uint8_t *d_conv, double *d_vu0, double *d_vuL, double *d_res, int32_t *d_iters, int32_t *d_calls, hipStream_t s,
-                      int64_t &rounds) {
+                      int64_t &rounds, bool final_launch = true) {
   tr_ctx::ShootDev &k = c->shoot;
   constexpr int Q = trk::kShootQ;
   const trk::ShootState st{k.p, k.pn, k.e, k.J, k.err2, k.mu, k.nu, k.iters, k.calls};
@@ -186,8 +186,8 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
     if ((rc = read_count(nxt, active))) return rc;
     cur = nxt;
   }
-  // the outputs: every problem once more at its final strains
-  {
+  // the outputs: every problem once more at its final strains (final_launch false: the caller wants the strains and flags only)
+  if (final_launch) {
     trk::LoadedIn in = base;
     in.vu = k.p; in.res = nullptr; in.vu_tip = d_vuL;
     if ((rc = shoot_fk(c, d_states, m, ld, out, in, s))) return rc;

@@ -31,6 +31,7 @@
 #include "../../include/tendon_hip.h"
 #include "tr_types.hpp"
 #include "fk_launch.hpp"
+#include "fk_lin_launch.hpp"
 #include "sweep_kernel.hpp"
 #include "sphere_kernel.hpp"
 #include "verdict_kernel.hpp"
@@ -44,11 +45,13 @@
 #include "fk_loaded_kernel.hpp"
 #include "loaded_edge_kernel.hpp"
 #include "loaded_roadmap_kernel.hpp"
+#include "loaded_ik_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
 struct tr_ctx;
 namespace { void ik_release(tr_ctx *c); }   // ik_host.inc
 namespace { void shoot_release(tr_ctx *c); }   // loaded_host.inc
+namespace { void ikl_release(tr_ctx *c); }   // loaded_ik_host.inc
 
 namespace {
 
@@ -284,6 +287,22 @@ struct tr_ctx {
     unsigned long long *vtally = nullptr;
     double rate_seen = 0.0;
   } ledge;
+  // tip IK on loaded shapes (loaded_ik_host.inc): the per-problem state of one chunk of problems, the rows of one round in list
+  // order, the [9][lanes] planes of the linearisation launch and the staging of the host-array form, grow-only
+  struct IklDev {
+    int64_t probs = 0, lanes = 0;
+    double *lin = nullptr;                                          // [9][lanes]
+    double *p = nullptr, *pn = nullptr, *y = nullptr, *W = nullptr, *J = nullptr, *f = nullptr, *des = nullptr;   // [probs][S | S | 6 | 6 S | 3 S | 3 | 3]
+    double *err2 = nullptr, *mu = nullptr, *nu = nullptr;
+    int32_t *iters = nullptr, *calls = nullptr, *list[2] = {nullptr, nullptr};
+    uint8_t *eq = nullptr;
+    double *row_s = nullptr, *row_w = nullptr, *row_d = nullptr, *row_g = nullptr, *row_vu = nullptr;   // [probs][S | 6 | 6 | 6 | 6]
+    uint8_t *row_conv = nullptr; int32_t *row_calls = nullptr;
+    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    double *io_s = nullptr, *io_3 = nullptr, *io_g = nullptr, *io_e = nullptr, *io_vu = nullptr;
+    int32_t *io_i = nullptr, *io_c = nullptr;
+    uint8_t *io_eq = nullptr;
+  } ikl;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
@@ -1149,6 +1168,7 @@ void tr_destroy(tr_ctx *c) {
   }
   ik_release(c);
   shoot_release(c);
+  ikl_release(c);
   {
     tr_ctx::LoadedEdgeDev &le = c->ledge;
     void *lp[] = {le.vu_pool, le.w, le.d, le.g, le.calls, le.tally, le.out_vu, le.out_index, le.vtally};
@@ -2263,3 +2283,4 @@ int tr_profile_end(tr_ctx *c) {
 #include "loaded_host.inc"
 #include "loaded_edges_host.inc"
 #include "loaded_roadmap_host.inc"
+#include "loaded_ik_host.inc"

@@ -523,6 +523,79 @@ class Engine:
         L.check(self._ctx, self.lib.tr_edges_loaded_vertex_strains(self._ctx, int(n_states), _dp(out)))
         return out
 
+    # ---- tip IK on loaded shapes (tr_ik_loaded_batch*, include/tendon_hip.h) -------------------------------------------------------
+    def _ik_loaded_args(self, wrench, dist, frame, bounds, lm):
+        """(loads or None, bounds keep-alive, lo, hi, tr_ik_params, tr_shoot_params) of the loaded IK calls.  lm: tr_ik_params'
+        fields by name; the shooting's by name with the prefix shoot_ (shoot_max_iters ...), defaults as in fk_loaded_batch except
+        shoot_stop_threshold_Dp = 0 (tr_ik_loaded_batch's defaults, include/tendon_hip.h)."""
+        lm = dict(lm)
+        sh = {k[6:]: lm.pop(k) for k in list(lm) if k.startswith("shoot_")}
+        ikd = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, stop_threshold_err=1e-4,
+                   finite_difference_delta=1e-6)
+        shd = {**self._SHOOT_DEFAULTS, "stop_threshold_Dp": 0.0}
+        for name, given, known in (("IK", lm, ikd), ("shooting", sh, shd)):
+            bad = set(given) - set(known)
+            if bad:
+                raise TypeError("unknown %s parameter(s): %s" % (name, ", ".join(sorted(bad))))
+        ld = None if wrench is None and dist is None else self._edge_loads(wrench, dist, frame, False)
+        if frame not in ("base", "world"):
+            raise L.InvalidArgument("frame must be 'base' or 'world'")
+        keep, plo, phi = self._ik_bounds(bounds)
+        return ld, keep, plo, phi, self._ik_params(**{**ikd, **lm}), self._shoot_params(**{**shd, **sh})
+
+    def ik_loaded_batch(self, initial_states, des, wrench=None, dist=None, frame="base", guess=None, bounds=None, **lm):
+        """Batched tip IK on LOADED shapes (tr_ik_loaded_batch): ik_batch under one load set, wrench = (F_e, L_e) and dist =
+        (f_e, l_e) of (6,) each (None: zero), frame 'base' or 'world' as in validate_edges_loaded.  guess: optional (n, 6) start
+        strains of the starts' shooting.  **lm: ik_batch's solver arguments, the shooting's with the prefix shoot_.
+        Returns dict(state, tip, error, iters, num_fk_calls (integrations), vu0, equilibrium, rounds, shoot_rounds)."""
+        st = self._states(initial_states)
+        n, S = st.shape
+        d = _f64(des)
+        if d.shape == (3,):
+            d_ld = 0
+        elif d.shape == (n, 3):
+            d_ld = 3
+        else:
+            raise L.InvalidArgument("des must be (3,) or (n, 3)")
+        g = None
+        if guess is not None:
+            g = _f64(guess)
+            if g.shape != (n, 6):
+                raise L.InvalidArgument("guess must be (n, 6)")
+        ld, keep, plo, phi, prm, sprm = self._ik_loaded_args(wrench, dist, frame, bounds, lm)
+        state, tip, err, vu0 = np.empty((n, S)), np.empty((n, 3)), np.empty(n), np.empty((n, 6))
+        iters, calls = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        eq = np.empty(n, dtype=np.uint8)
+        rounds = (C.c_int64 * 2)()
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        L.check(self._ctx, self.lib.tr_ik_loaded_batch(
+            self._ctx, C.byref(prm), C.byref(sprm), C.byref(ld) if ld is not None else None, _dp(st), n, _dp(d), d_ld, plo, phi,
+            _dp(g) if g is not None else None, _dp(state), _dp(tip), _dp(err), i32(iters), i32(calls), _dp(vu0),
+            eq.ctypes.data_as(C.POINTER(C.c_uint8)), rounds))
+        return dict(state=state, tip=tip, error=err, iters=iters, num_fk_calls=calls, vu0=vu0, equilibrium=eq.astype(bool),
+                    rounds=int(rounds[0]), shoot_rounds=int(rounds[1]))
+
+    def ik_loaded_batch_dev(self, d_initial_states, n, d_des, d_states_out, d_tips_out=None, d_error_out=None, d_iters_out=None,
+                            d_fk_calls_out=None, d_vu0_out=None, d_equilibrium_out=None, d_guess=None, des_ld=3, wrench=None, dist=None,
+                            frame="base", bounds=None, stream=None, **lm):
+        """tr_ik_loaded_batch_dev: device tensors in and out (des_ld = 0: one goal row for all); returns (outer rounds, shooting
+        rounds)."""
+        torch = _torch()
+        S = self.state_size
+        f64 = torch.float64
+        opt = lambda t, dt, m, nm: self._check_dev(t, dt, m, nm) if t is not None else None
+        ld, keep, plo, phi, prm, sprm = self._ik_loaded_args(wrench, dist, frame, bounds, lm)
+        rounds = (C.c_int64 * 2)()
+        L.check(self._ctx, self.lib.tr_ik_loaded_batch_dev(
+            self._ctx, C.byref(prm), C.byref(sprm), C.byref(ld) if ld is not None else None,
+            self._check_dev(d_initial_states, f64, n * S, "d_initial_states"), int(n),
+            self._check_dev(d_des, f64, 3 if des_ld == 0 else (n - 1) * des_ld + 3, "d_des"), int(des_ld), plo, phi,
+            opt(d_guess, f64, 6 * n, "d_guess"), self._check_dev(d_states_out, f64, n * S, "d_states_out"),
+            opt(d_tips_out, f64, 3 * n, "d_tips_out"), opt(d_error_out, f64, n, "d_error_out"), opt(d_iters_out, torch.int32, n, "d_iters_out"),
+            opt(d_fk_calls_out, torch.int32, n, "d_fk_calls_out"), opt(d_vu0_out, f64, 6 * n, "d_vu0_out"),
+            opt(d_equilibrium_out, torch.uint8, n, "d_equilibrium_out"), rounds, self._stream_ptr(stream)))
+        return int(rounds[0]), int(rounds[1])
+
     # ---- the roadmap build on loaded shapes (tr_sample_valid_vertices_loaded .. tr_connect_edges_loaded_indexed, include/tendon_hip.h) ----
     _SHOOT_DEFAULTS = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6)
 

@@ -76,23 +76,25 @@ def _tips(robot, states, device):
     return tips
 
 
-def _eval(robot, p, delta, device):
+def _eval(robot, p, delta, device, fk=None):
     """f(p) and the central-difference Jacobian (levmar's: d_j = max(1e-4 |p_j|, delta), misc_core.c:175-211)
-    of every row of p in ONE FK batch: (n, 3), (n, 3, S)."""
+    of every row of p in ONE FK batch: (n, 3), (n, 3, S).  fk: the FKFunc, states (m, S) -> tips (m, 3); None: the engine's FK."""
     n, S = p.shape
     d = np.maximum(np.abs(1e-4 * p), delta)
     batch = np.repeat(p[:, None, :], 2 * S + 1, axis=1)                # (n, 2S+1, S): [p, p - d e_j, p + d e_j ...]
     j = np.arange(S)
     batch[:, 1 + 2 * j, j] -= d
     batch[:, 2 + 2 * j, j] += d
-    tips = _tips(robot, batch.reshape(-1, S), device).reshape(n, 2 * S + 1, 3)
+    tips = (_tips(robot, batch.reshape(-1, S), device) if fk is None else np.asarray(fk(batch.reshape(-1, S)), float)).reshape(n, 2 * S + 1, 3)
     J = (tips[:, 2::2, :] - tips[:, 1::2, :]) * (0.5 / d)[:, :, None]  # (n, S, 3)
     return tips[:, 0, :], np.transpose(J, (0, 2, 1))
 
 
 def inverse_kinematics_batch(robot, initial_states, des, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9,
-                             stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6, device=0):
+                             stop_threshold_Dp=1e-4, stop_threshold_err=1e-4, finite_difference_delta=1e-6, device=0, fk=None):
     """Solve tip(state) = des from every row of initial_states at once (des: (3,) or one row per start).
+    fk: tip_control::inverse_kinematics' FKFunc for a batch, states (m, S) -> tips (m, 3) (None: the engine's unloaded FK); with a
+    loaded FK every difference goes through a shooting solve -- inverse_kinematics_loaded_batch_device is the call built for that.
     Returns dict(state (n, S), tip (n, 3), error (n,), iters (n,), num_fk_calls (n,), launches)."""
     p = np.ascontiguousarray(np.asarray(initial_states, dtype=np.float64))
     if p.ndim == 1:
@@ -104,7 +106,7 @@ def inverse_kinematics_batch(robot, initial_states, des, max_iters=100, mu_init=
     b = Bounds.from_robot(robot)
     p = np.clip(p, b.lower, b.upper)
     eps1, eps2_sq, eps3_sq = stop_threshold_JT_err_inf, stop_threshold_Dp ** 2, stop_threshold_err ** 2
-    f, J = _eval(robot, p, finite_difference_delta, device)
+    f, J = _eval(robot, p, finite_difference_delta, device, fk)
     fk_calls = np.full(n, 2 * S + 1)
     launches = 1
     e = des - f
@@ -137,7 +139,7 @@ def inverse_kinematics_batch(robot, initial_states, des, max_iters=100, mu_init=
         if not go.any():
             continue
         k = idx[go]
-        fn, Jn = _eval(robot, pn[go], finite_difference_delta, device)
+        fn, Jn = _eval(robot, pn[go], finite_difference_delta, device, fk)
         launches += 1
         fk_calls[k] += 2 * S + 1
         en = des[k] - fn
@@ -194,6 +196,34 @@ def inverse_kinematics_device(robot, initial_state, des, max_iters=100, mu_init=
     """tip_control::inverse_kinematics for one start state, on the device."""
     r = inverse_kinematics_batch_device(robot, np.asarray(initial_state, float).reshape(1, -1), des, max_iters, mu_init,
                                         stop_threshold_JT_err_inf, stop_threshold_Dp, stop_threshold_err, finite_difference_delta, device)
+    return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
+
+
+def inverse_kinematics_loaded_batch_device(robot, initial_states, des, wrench=None, dist=None, frame="base", guess=None, device=0, **lm):
+    """tip_control::inverse_kinematics with TendonRobot::general_shape as its FK, for a batch, on the device (tr_ik_loaded_batch):
+    solve tip(state under the load) = des from every row of initial_states.  wrench = (F_e, L_e), dist = (f_e, l_e): one (6,) set
+    per call, frame 'base' (fixed before the state's rotation) or 'world' (fixed behind rotate_z, e.g. gravity).  **lm:
+    inverse_kinematics_batch's solver arguments, the shooting's with the prefix shoot_ (shoot_max_iters ...).  The scheme is
+    tests/loaded_ik_reference.py's.  Returns inverse_kinematics_batch_device's fields (num_fk_calls: integrations; launches: outer
+    rounds) plus vu0 (the base strains of each returned state's equilibrium), equilibrium (False: the start's shooting did not
+    converge, error = inf) and shoot_rounds."""
+    p = np.asarray(initial_states, dtype=np.float64)
+    if p.ndim == 1:
+        p = p.reshape(1, -1)
+    if p.shape[1] != robot.state_size():
+        raise L.InvalidArgument("State is not the right size")
+    des = np.asarray(des, dtype=np.float64)
+    if des.ndim == 2 and des.shape[0] == 1 and p.shape[0] != 1:
+        des = des[0]
+    r = robot.engine(device).ik_loaded_batch(p, des, wrench=wrench, dist=dist, frame=frame, guess=guess, **lm)
+    return dict(state=r["state"], tip=r["tip"], error=r["error"], iters=r["iters"].astype(int), num_fk_calls=r["num_fk_calls"].astype(int),
+                launches=r["rounds"], vu0=r["vu0"], equilibrium=r["equilibrium"], shoot_rounds=r["shoot_rounds"])
+
+
+def inverse_kinematics_loaded_device(robot, initial_state, des, wrench=None, dist=None, frame="base", guess=None, device=0, **lm):
+    """inverse_kinematics_loaded_batch_device for one start state: an IKResult (error = inf without an equilibrium at the start)."""
+    g = None if guess is None else np.asarray(guess, float).reshape(1, 6)
+    r = inverse_kinematics_loaded_batch_device(robot, np.asarray(initial_state, float).reshape(1, -1), des, wrench, dist, frame, g, device, **lm)
     return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
 
 

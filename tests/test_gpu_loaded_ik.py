@@ -1,0 +1,267 @@
+"""Tip IK on loaded shapes on the device (tr_ik_loaded_batch*, csrc/loaded_ik_host.inc) against the numpy restatements
+(tests/loaded_ik_reference.py, tests/loaded_fk_reference.py) and the loaded-FK fixtures (tests/golden/loaded_fk_<name>.npz).
+
+Goals are the fixtures' loaded tips, starts the fixture states plus seeded normal offsets (loaded_ik_reference.offset_starts, seed 5).
+The ABI takes one load set per call: cases whose rows differ per state (case C's wrenches, config3_rot's rows in the BASE frame) are
+solved one problem per call.
+
+Tolerances: 1e-4 m is stop_threshold_err.  bound_i is make_loaded_fk.py's: 1e-9 m + 1.5 C_i (residual_threshold + |e_i|) with C_i
+from a cold numpy shooting at the returned state -- the displacement between two shapes whose tip wrenches both miss by at most the
+threshold.  The device's own loaded FK lies within bound_i of that cold solve too, hence 2 bound_i where the two are chained."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (HERE, os.path.join(HERE, "golden")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import loaded_fk_reference as ref                                    # noqa: E402
+import loaded_ik_reference as ikr                                    # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GRAVITY = np.array([0.0, -2.4525, 0.0, 0.0, 0.0, 0.0])
+TOL = 1e-4
+KEYS = ("state", "tip", "error", "iters", "num_fk_calls", "vu0", "equilibrium")
+#            fixture, case, frame, sigma of the tension offsets [N], of the rotation offsets [rad]
+PROBLEMS = {"config1_B": ("config1", "B", "base", 3.0, 0.0),
+            "config1_C": ("config1", "C", "base", 3.0, 0.0),
+            "n1_B": ("n1", "B", "world", 1.5, 0.3),
+            "config3_rot_base": ("config3_rot", "B", "base", 0.5, 0.1),
+            "config3_rot_world": ("config3_rot", "B", "world", 0.5, 0.1)}
+
+
+@pytest.fixture(scope="module")
+def gen(orc):
+    import make_loaded_fk
+    return make_loaded_fk
+
+
+@pytest.fixture(scope="module")
+def world(gen, irt):
+    """name -> (robot, oracle robot, fixture arrays, engine), built on first use"""
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            robot, rob, st = gen.fixture(name)
+            fx = dict(np.load(gen.path(name)))
+            assert np.array_equal(st, fx["states"])
+            cache[name] = (robot, rob, fx, robot.engine(0))
+        return cache[name]
+    return get
+
+
+def _one_set(rows):
+    return rows is None or rows.ndim == 1
+
+
+def ik(eng, starts, goals, wrench, dist, frame, **kw):
+    """ik_loaded_batch; load rows that differ per problem are solved one problem per call"""
+    if _one_set(wrench) and _one_set(dist):
+        return eng.ik_loaded_batch(starts, goals, wrench=wrench, dist=dist, frame=frame, **kw)
+    row = lambda a, i: a if _one_set(a) else a[i]
+    outs = [eng.ik_loaded_batch(starts[i:i + 1], goals[i:i + 1], wrench=row(wrench, i), dist=row(dist, i), frame=frame, **kw)
+            for i in range(len(starts))]
+    out = {k: np.concatenate([o[k] for o in outs]) for k in KEYS}
+    out["rounds"] = sum(o["rounds"] for o in outs)
+    out["shoot_rounds"] = sum(o["shoot_rounds"] for o in outs)
+    return out
+
+
+@pytest.fixture(scope="module")
+def solved(world):
+    """key of PROBLEMS -> dict(starts, goals, wrench, dist, frame, out (the device's result), cold (numpy's cold shooting at the
+    returned states under their load rows), tip_cold, bound), computed once"""
+    cache = {}
+
+    def get(key):
+        if key in cache:
+            return cache[key]
+        name, case, frame, s_tau, s_rot = PROBLEMS[key]
+        robot, rob, fx, eng = world(name)
+        starts = ikr.offset_starts(rob, fx["states"], s_tau, s_rot)
+        goals = np.ascontiguousarray(fx["p_" + case][:, -1])
+        if frame == "world":
+            wrench, dist = None, GRAVITY
+        else:
+            wrench, dist = fx["wrench_" + case], fx["dist_" + case]
+            if (wrench == wrench[0]).all():
+                wrench = wrench[0] if wrench.any() else None
+            if (dist == dist[0]).all():
+                dist = dist[0]
+        out = ik(eng, starts, goals, wrench, dist, frame)
+        w, d = ikr.load_rows(rob, out["state"], wrench, dist, frame)
+        with np.errstate(all="ignore"):
+            cold = ref.shoot(rob, out["state"], F_e=w[:, :3], L_e=w[:, 3:], f_e=d[:, :3], l_e=d[:, 3:])
+        bound = 1e-9 + 1.5 * cold["C"] * (robot.residual_threshold + cold["e"])
+        cache[key] = dict(starts=starts, goals=goals, wrench=wrench, dist=dist, frame=frame, out=out, cold=cold,
+                          tip_cold=cold["p"][:, -1], bound=bound)
+        return cache[key]
+    return get
+
+
+def _same(a, b, rows_a=slice(None), rows_b=slice(None)):
+    for k in KEYS:
+        assert np.array_equal(a[k][rows_a], b[k][rows_b], equal_nan=True), k
+
+
+@pytest.mark.parametrize("key", ["config1_B", "config1_C", "n1_B"])
+def test_it_is_a_solution(world, solved, key):
+    robot, rob, fx, eng = world(PROBLEMS[key][0])
+    s = solved(key)
+    out, goals, bound = s["out"], s["goals"], s["bound"]
+    lo, hi = ikr.bounds(rob)
+    miss_cold = np.linalg.norm(s["tip_cold"] - goals, axis=1)
+    off = np.linalg.norm(out["tip"] - s["tip_cold"], axis=1)
+    print("%s: error <= %.3g m, iters <= %d, integrations %.1f per problem, rounds %d + %d; cold numpy tip misses by <= %.3g m, tips_out "
+          "off it by <= %.3g of bound (bound <= %.3g m)" % (key, out["error"].max(), out["iters"].max(), out["num_fk_calls"].mean(),
+                                                           out["rounds"], out["shoot_rounds"], miss_cold.max(), (off / bound).max(), bound.max()))
+    assert out["equilibrium"].all()
+    assert (out["error"] <= TOL).all(), np.nonzero(~(out["error"] <= TOL))[0]
+    assert ((out["state"] >= lo) & (out["state"] <= hi)).all()
+    if robot.enable_rotation:
+        th = out["state"][:, len(robot.tendons)]
+        assert ((th >= -np.pi) & (th < np.pi)).all()
+    assert s["cold"]["converged"].all()
+    assert (miss_cold <= TOL + bound).all()
+    assert (off <= bound).all()
+    assert np.abs(out["error"] - np.linalg.norm(goals - out["tip"], axis=1)).max() <= 1e-12
+
+
+@pytest.mark.parametrize("key", ["config3_rot_base", "config3_rot_world"])
+def test_rotation_in_both_frames(solved, key):
+    s = solved(key)
+    out, goals, bound = s["out"], s["goals"], s["bound"]
+    reached = out["error"] <= TOL
+    miss_cold = np.linalg.norm(s["tip_cold"] - goals, axis=1)
+    print("%s: reached %d of 24, iters <= %d, integrations %.1f per problem; reported error off the cold numpy solve's by <= %.3g of bound"
+          % (key, reached.sum(), out["iters"].max(), out["num_fk_calls"].mean(), (np.abs(miss_cold - out["error"]) / bound).max()))
+    assert out["equilibrium"].all() and s["cold"]["converged"].all()
+    assert reached.sum() >= 21
+    assert (np.abs(miss_cold - out["error"]) <= bound).all()
+    th = out["state"][:, -1]
+    assert ((th >= -np.pi) & (th < np.pi)).all()
+
+
+def test_the_load_matters(world, solved):
+    _, _, fx, eng = world("config1")
+    s = solved("config1_B")
+    un = eng.ik_batch(s["starts"], s["goals"])
+    sag = np.linalg.norm(eng.fk_loaded_batch(un["state"], dist=s["dist"])["p"][:, -1] - s["goals"], axis=1)
+    new = eng.fk_loaded_batch(s["out"]["state"], dist=s["dist"])
+    miss = np.linalg.norm(new["p"][:, -1] - s["goals"], axis=1)
+    print("tr_ik_batch's answers under the load miss by %.3g .. %.3g m (median %.3g); tr_ik_loaded_batch's by <= %.3g m"
+          % (sag.min(), sag.max(), np.median(sag), miss.max()))
+    assert (sag > 10 * TOL).sum() > 12
+    assert new["converged"].all()
+    assert (miss <= TOL + 2 * s["bound"]).all()
+
+
+def test_zero_load_is_the_unloaded_ik(world, solved):
+    _, _, fx, eng = world("config1")
+    starts = solved("config1_B")["starts"]
+    goals, conv = eng.fk_tips(fx["states"])
+    assert conv.sum() >= 20
+    a = eng.ik_batch(starts, goals)
+    b = eng.ik_loaded_batch(starts, goals)
+    ra, rb = a["error"] <= TOL, b["error"] <= TOL
+    close = (np.abs(a["state"] - b["state"]) <= 1e-6 * (1 + np.abs(a["state"]))).all(axis=1)
+    print("reached %d (unloaded) and %d (loaded call, no load); states agree on %d of the %d reached; largest difference %.3g"
+          % (ra.sum(), rb.sum(), (close & ra).sum(), ra.sum(), np.abs(a["state"] - b["state"])[ra].max()))
+    assert b["equilibrium"].all()
+    assert np.array_equal(ra, rb)
+    assert (close & ra).sum() >= 0.9 * ra.sum()
+
+
+def test_shapes_of_the_launch_do_not_change_a_bit(world, solved, irt, monkeypatch):
+    """19 lanes; 95 lanes (problem 3 lies across two waves); all 24; reversed; 300 problems in chunks of 7 and in one chunk"""
+    robot, _, _, eng = world("config1")
+    s = solved("config1_B")
+    st, g, full = s["starts"], s["goals"], s["out"]
+    kw = dict(dist=s["dist"], frame="base")
+    for n in (1, 5):
+        _same(eng.ik_loaded_batch(st[:n], g[:n], **kw), full, rows_b=slice(0, n))
+    _same(eng.ik_loaded_batch(st[::-1], g[::-1], **kw), full, rows_b=slice(None, None, -1))
+    idx = np.arange(300) % 24
+    monkeypatch.setenv("TENDON_HIP_SHOOT_CHUNK", "7")
+    chunked = irt.Engine(robot, 0)
+    monkeypatch.delenv("TENDON_HIP_SHOOT_CHUNK")
+    a = chunked.ik_loaded_batch(st[idx], g[idx], **kw)
+    chunked.close()
+    b = eng.ik_loaded_batch(st[idx], g[idx], **kw)
+    assert a["rounds"] > b["rounds"]
+    _same(a, full, rows_b=idx)
+    _same(b, full, rows_b=idx)
+
+
+def test_a_hopeless_problem_does_not_touch_the_others(world, solved):
+    """One load set per call: the hopeless goal sits in one row; the hopeless load is a call of its own; a row that finds no
+    equilibrium beside rows that do comes from hopeless start strains"""
+    _, _, _, eng = world("config1")
+    s = solved("config1_B")
+    g = s["goals"].copy()
+    g[11] = [10.0, 0.0, 0.0]
+    out = eng.ik_loaded_batch(s["starts"], g, dist=s["dist"])                 # returns: no stop is an error of the call
+    assert out["equilibrium"][11] and not out["error"][11] <= TOL
+    keep = np.arange(24) != 11
+    _same(out, s["out"], keep, keep)
+    lost = eng.ik_loaded_batch(s["starts"], s["goals"], wrench=[1e6, 0.0, 0.0, 0.0, 0.0, 0.0], dist=s["dist"])
+    assert not lost["equilibrium"].any()
+    assert np.isinf(lost["error"]).all() and (lost["iters"] == 0).all()
+    # a start without an equilibrium among starts that have one: hopeless start strains in one row of `guess`
+    _, _, fx, _ = world("config1")
+    guess = fx["vu0_B"].copy()
+    with_guess = eng.ik_loaded_batch(s["starts"], s["goals"], dist=s["dist"], guess=guess)
+    assert with_guess["equilibrium"].all() and (with_guess["error"] <= TOL).all()
+    guess[11] = 1e6
+    out = eng.ik_loaded_batch(s["starts"], s["goals"], dist=s["dist"], guess=guess)
+    assert not out["equilibrium"][11] and np.isinf(out["error"][11]) and out["iters"][11] == 0
+    _same(out, with_guess, keep, keep)
+
+
+def test_device_form_equals_host_form(world, solved):
+    import torch
+    _, _, _, eng = world("n1")
+    s = solved("n1_B")
+    n, S = s["starts"].shape
+    dev = "cuda:0"
+    t = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)
+    o = dict(state=t((n, S)), tip=t((n, 3)), error=t(n), iters=t(n, torch.int32), num_fk_calls=t(n, torch.int32), vu0=t((n, 6)),
+             equilibrium=t(n, torch.uint8))
+    rounds = eng.ik_loaded_batch_dev(torch.from_numpy(s["starts"]).to(dev), n, torch.from_numpy(s["goals"]).to(dev), o["state"], o["tip"],
+                                     o["error"], o["iters"], o["num_fk_calls"], o["vu0"], o["equilibrium"], dist=GRAVITY, frame="world")
+    torch.cuda.synchronize()
+    assert rounds == (s["out"]["rounds"], s["out"]["shoot_rounds"])
+    got = {k: v.cpu().numpy() for k, v in o.items()}
+    got["equilibrium"] = got["equilibrium"].astype(bool)
+    _same(got, s["out"])
+
+
+def test_errors(world, irt):
+    robot, _, fx, eng = world("config1")
+    ret = irt.workloads.robot_config1()
+    ret.enable_retraction = True
+    with pytest.raises(irt.Unsupported, match="loaded FK \\(general_shape\\) is not built for robots with retraction"):
+        bad = irt.Engine(ret, 0)
+        bad.ik_loaded_batch(np.zeros((2, bad.state_size)), np.zeros(3))
+    st = np.ascontiguousarray(fx["states"][:2])
+    goal = np.zeros(3)
+    with pytest.raises(irt.InvalidArgument):
+        eng.ik_loaded_batch(st, goal, dist=GRAVITY, frame="tool")
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    ld = irt._lib.TrEdgeLoads()
+    ld.frame = 7
+    tail = (None,) * 9
+    assert eng.lib.tr_ik_loaded_batch(eng._ctx, None, None, C.byref(ld), dp(st), 2, dp(goal), 0, None, None, *tail) == irt._lib.TR_ERR_INVALID_ARG
+    lo, hi = np.zeros(st.shape[1]), np.full(st.shape[1], 5.0)
+    hi[1] = -1.0
+    with pytest.raises(irt.InvalidArgument):
+        eng.ik_loaded_batch(st, goal, bounds=(lo, hi))
+    empty = eng.ik_loaded_batch(np.zeros((0, st.shape[1])), goal, dist=GRAVITY)
+    assert empty["state"].shape == (0, st.shape[1]) and empty["rounds"] == 0
