@@ -871,6 +871,12 @@ int tr_edge_schedule_last(const tr_ctx *ctx, uint32_t stats[4]);
  *                                   tr_voxelize_batch_loaded (tests: several batches; default: 2^16, what the workspace is grown to)
  *   TENDON_HIP_RETRACT_SORT=n       retraction robots: batches of at least n configurations are ordered by backbone length
  *                                   (0 = never); TENDON_HIP_RETRACT_KBEGIN_OFF: no per-wave loop start in that order
+ *   TENDON_HIP_ROUTING=table        the general (table) form of the strain right-hand side for every robot.  Unset: a robot without
+ *                                   retraction whose tendons all have constant radius and at most linear angle, with ONE pitch and
+ *                                   ONE radius (compared bit for bit; straight tendons: pitch 0), of at most six tendons, gets the
+ *                                   uniform-helix form in every unloaded shared-grid kernel (csrc/fk_kernel.hpp: UniformHelix): the
+ *                                   same quantities from fewer instructions, equal to the table form's up to the rounding of the
+ *                                   last bits (both within the bound of tests/test_gpu_fk_truth.py)
  * Read per call (the tests switch between two paths inside one process; the switches of tr_roadmap_*: once, at the start of the call
  * that uses them -- csrc/roadmap.hip: read_switches):
  *   TENDON_HIP_KNN=lanes            neighbour search by the lane-per-query kernel for every k (default: wave per query up to k = 64);

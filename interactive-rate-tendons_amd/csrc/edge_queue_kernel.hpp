@@ -150,7 +150,7 @@ __device__ __forceinline__ bool eq_claim(const EdgeQueueArgs &q, int &pos, int &
   }
 }
 
-template <int N, bool ROT>
+template <int N, bool ROT, class Form = TableRouting>
 __global__ __launch_bounds__(64, (N <= TRK_VERDICT_TWO_WAVE_MAXN ? 2 : 1)) void fk_edge_queue(
     RobotK K, const double *__restrict__ tab, const StepK *__restrict__ steps, int nsteps,
     const VerdictArgs *__restrict__ va, const EdgeQueueArgs *__restrict__ qa, const FusedSweepArgs *__restrict__ sa) {
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64, (N <= TRK_VERDICT_TWO_WAVE_MAXN ? 2 : 1)) void 
     FkLane<N> fl_;
     {
       FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      fk_uniform_body<N, ROT, false, false>(st_eff, n_eff, 0, K, tab, steps, nsteps, out, ps, nullptr, &fl_);
+      fk_uniform_body<N, ROT, false, false, Form>(st_eff, n_eff, 0, K, tab, steps, nsteps, out, ps, nullptr, &fl_);
     }
     ps.template sig_finish<false>();
     ps.finish();
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(64, (N <= TRK_VERDICT_TWO_WAVE_MAXN ? 2 : 1)) void 
       __syncthreads();
       const double *st2 = q2.states + ((int64_t)h2 - (int64_t)blockIdx.x * 64) * K.state_size;
       const int64_t n2 = (int64_t)blockIdx.x * 64 + cnt2;
-      fk_uniform_body<N, ROT, false, false>(st2, n2, q2.fb_ld, K, tab, steps, nsteps, q2.fb_out, NoPointHook(), nullptr, nullptr);
+      fk_uniform_body<N, ROT, false, false, Form>(st2, n2, q2.fb_ld, K, tab, steps, nsteps, q2.fb_out, NoPointHook(), nullptr, nullptr);
       __syncthreads();
       const FusedSweepArgs fa = *sa;
       bool exact = false;

@@ -76,15 +76,30 @@ struct NoLoad {
   __device__ __forceinline__ void operator()(double &, double &, double &, double &, double &, double &) const {}
 };
 
+// What the right-hand side may assume about the routing.  TableRouting (the default) assumes nothing: r, r', r'' are six
+// independent numbers per tendon and abscissa, and every kernel compiles to the instructions it had before the policy existed.
+// UniformHelix: every tendon is r = rho (sin(theta_j + omega s), cos(theta_j + omega s)) with ONE pitch omega and ONE radius rho
+// (straight tendons: omega = 0), so at every abscissa, exactly,
+//   r' = omega (ry, -rx)   =>  pd = v + r' + u x r = v + (u - omega e3) x r:  pdx = v0 - k ry, pdy = v1 + k rx, k = u2 - omega
+//                              formed once per evaluation -- one FMA each where an add and an FMA were;
+//   rx^2 + ry^2 = rho^2    =>  the rhat^2 term of H_zz is -rho^2 sum cs2 = -rho^2 Z, one FMA per evaluation on the Z the loop
+//                              sums anyway, where two FMAs per tendon were.
+// (2 + 2) N - 2 instructions fewer per evaluation.  omega and rho^2 are RobotK's (helix_omega, helix_rho2); the host decides
+// once per context which form its robot gets (routing_form.hpp) and the table keeps its layout: h = pd + r' still reads r'.
+struct TableRouting { static constexpr bool kHelix = false; };
+struct UniformHelix { static constexpr bool kHelix = true; };
+
 // Right-hand side for the strain part of the state: (v', u') and the length rates.
 // route(j, r6) yields tendon j's routing {rx, ry, rdx, rdy, rddx, rddy} when the tendon loop reaches it
 // (a table row for the shared-grid kernel, an on-the-fly evaluation for the retraction kernel).
 // load(cx, cy, cz, dx, dy, dz) takes R^T l_e from c and R^T f_e from d (tendon/tendon_deriv.cpp:331-332).
-template <int N, class Route, class Load = NoLoad>
+template <int N, class Route, class Load = NoLoad, class Form = TableRouting>
 __device__ __forceinline__ void strain_rates_routed(const double v[3], const double u[3], const double (&tau)[N],
                                                     Route &&route, const RobotK &K,
                                                     double dv[3], double du[3], double (&sdot)[N], const Load &load = Load()) {
 #pragma clang fp contract(fast)
+  double kh = 0;
+  if constexpr (Form::kHelix) kh = u[2] - K.helix_omega;
   // Sums over tendons, using A_i = c (pd pd^T - |pd|^2 I), c = -tau/|pd|^3, q = c pd, e = r x pd, g = c e:
   //   A = sum q pd^T - (sum c|pd|^2) I
   //   B = sum rhat A_i   = sum g pd^T - sum c|pd|^2 rhat
@@ -105,8 +120,14 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double rdx = r6[2], rdy = r6[3];
     const double rddx = r6[4], rddy = r6[5];
     // pd = u x r + r' + v
-    const double pdx = (v[0] + rdx) - u[2] * ry;
-    const double pdy = (v[1] + rdy) + u[2] * rx;
+    double pdx, pdy;
+    if constexpr (Form::kHelix) {
+      pdx = __builtin_fma(-kh, ry, v[0]);
+      pdy = __builtin_fma(kh, rx, v[1]);
+    } else {
+      pdx = (v[0] + rdx) - u[2] * ry;
+      pdy = (v[1] + rdy) + u[2] * rx;
+    }
     const double pdz = __builtin_fma(u[0], ry, __builtin_fma(-u[1], rx, v[2]));
     // (sums of products are FMA chains written out, here and below: left to contraction, the compiler picks per kernel which
     // product goes inside the FMA, and the kernels that hold this body differ in the last bit)
@@ -132,7 +153,7 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     const double mxy = c * sxy, mx = mxy * rx, my = mxy * ry;
     Hxx -= my * ry; Hxy += mx * ry; Hyy -= mx * rx;
     const double t1 = cs2 * rx, t2 = cs2 * ry;
-    Hzz -= t1 * rx; Hzz -= t2 * ry;
+    if constexpr (!Form::kHelix) { Hzz -= t1 * rx; Hzz -= t2 * ry; }      // (UniformHelix: -rho^2 Z, behind the loop)
     // The same difference, c pdz^2 - c|pd|^2 = -mxy, is all of the z-z entry of A_i, and times (ry, -rx) all of the third column
     // of the first two rows of B_i (g pd^T gives (ry, -rx) c pdz^2, the rhat term (ry, -rx) (-c|pd|^2)); the third row of B_i takes
     // its rhat term (t2, -t1, 0) here too.  These five are sums of products that exist already: plain adds (contracted, each
@@ -156,6 +177,7 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
     ax = __builtin_fma(cs2, px, ax); ay = __builtin_fma(cs2, py, ay); az = __builtin_fma(cs2, pz, az);
     bx = __builtin_fma(t2, pz, bx); by = __builtin_fma(-t1, pz, by); bz = __builtin_fma(t1, py, __builtin_fma(-t2, px, bz));
   }
+  if constexpr (Form::kHelix) Hzz = __builtin_fma(-K.helix_rho2, Z, Hzz);
   // The tail below is written as explicit FMA chains: without re-association the compiler keeps the a - (b*c + d*e)
   // shapes as written and spends an extra add / negate on each (~90 instructions per RK4 step).
 #define TRK_FMA __builtin_fma
@@ -268,14 +290,15 @@ __device__ __forceinline__ void strain_rates_routed(const double v[3], const dou
 }
 
 // ri: wave-uniform pointer to N x 6 doubles {rx, ry, rdx, rdy, rddx, rddy} per tendon.
-template <int N, class Load = NoLoad>
+template <int N, class Load = NoLoad, class Form = TableRouting>
 __device__ __forceinline__ void strain_rates(const double v[3], const double u[3], const double (&tau)[N],
                                              const double *__restrict__ ri, const RobotK &K,
                                              double dv[3], double du[3], double (&sdot)[N], const Load &load = Load()) {
-  strain_rates_routed<N>(v, u, tau, [&](int j, double (&r6)[6]) {
+  auto row = [&](int j, double (&r6)[6]) {
 #pragma unroll
     for (int q = 0; q < 6; q++) r6[q] = ri[6 * j + q];
-  }, K, dv, du, sdot, load);
+  };
+  strain_rates_routed<N, decltype(row) &, Load, Form>(v, u, tau, row, K, dv, du, sdot, load);
 }
 
 // solve_initial_bending + base residual.  Written without contraction and with IEEE div/sqrt so
@@ -472,7 +495,9 @@ template <class OnPoint> __host__ __device__ constexpr bool li_in_lds(int N) {
 // on_point(j, x, y, z): called for every observed backbone point (after rotate_z), in order j = 0 .. P-1 -- the
 // verdict-only kernel sweeps the point there instead of storing it; on_point.begin(converged && live) precedes point 0.  row_map (optional): lane i integrates
 // configuration row_map[i] of `states` (the fallback pass of the verdict path works on a compacted list).
-template <int N, bool ROT, bool WRITE_R, bool WANT_L = true, class OnPoint = NoPointHook>
+// Form: the routing form of the right-hand side (TableRouting | UniformHelix); the last template argument a caller names, the
+// hook's type behind it is deduced.
+template <int N, bool ROT, bool WRITE_R, bool WANT_L = true, class Form = TableRouting, class OnPoint = NoPointHook>
 __device__ __forceinline__ void fk_uniform_body(
     const double *__restrict__ states, int64_t n, int64_t ld, const RobotK &K,
     const double *__restrict__ tab, const StepK *__restrict__ steps, int nsteps, const FkOut &out,
@@ -561,7 +586,7 @@ __device__ __forceinline__ void fk_uniform_body(
       const double bw = (st == 0 || st == 3) ? b1 : b2;      // weight of this stage in the update
       const double aw = (st == 2) ? h : hh;                  // coefficient towards the next stage
       double dv[3], du[3], sd[N];
-      strain_rates<N>(sv, su, tau, ri, K, dv, du, sd);
+      strain_rates<N, NoLoad, Form>(sv, su, tau, ri, K, dv, du, sd);
       // quadratures: p' = R v, L' = |v|, L_i' = |pd_i|
       position_quadrature(st, sR, sv, b1, qs, qm, p);
       if (WANT_L && out.L) {                               // wave-uniform
@@ -621,11 +646,11 @@ __device__ __forceinline__ void fk_uniform_body(
   }
 }
 
-template <int N, bool ROT, bool WRITE_R>
+template <int N, bool ROT, bool WRITE_R, class Form = TableRouting>
 __global__ __launch_bounds__(64, (N <= TRK_K1_TWO_WAVE_MAXN ? 2 : 1)) void fk_rk4_batch_uniform(
     const double *__restrict__ states, int64_t n, int64_t ld, RobotK K,
     const double *__restrict__ tab, const StepK *__restrict__ steps, int nsteps, FkOut out) {
-  fk_uniform_body<N, ROT, WRITE_R>(states, n, ld, K, tab, steps, nsteps, out);
+  fk_uniform_body<N, ROT, WRITE_R, true, Form>(states, n, ld, K, tab, steps, nsteps, out);
 }
 
 }  // namespace trk

@@ -57,8 +57,9 @@ template <int N> void launch_fk_sweep_retract_list(const FkLaunch &a, const Fuse
 // grid): `waves` workgroups of one wave; va / qa / sweep are device pointers, `lds` the verdict body's image with the signature tile
 template <int N> void launch_fk_edge_queue(const FkLaunch &a, const VerdictArgs *va, size_t lds, const EdgeQueueArgs *qa,
                                            const FusedSweepArgs *sweep, unsigned waves);
-// workgroups of that kernel one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0 on error)
-template <int N> int fk_edge_queue_waves_per_cu(bool rotation, size_t lds);
+// workgroups of that kernel one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0 on error), for the rotation flag and the
+// routing form of K
+template <int N> int fk_edge_queue_waves_per_cu(const RobotK &K, size_t lds);
 
 // the loaded FK (fk_loaded_kernel.hpp): a.n lanes, a.d_states the problems' states, a.out the outputs (column = lane)
 template <int N> void launch_fk_loaded(const FkLaunch &a, const LoadedIn &in);
@@ -73,7 +74,7 @@ template <int N> void launch_shoot_start(const FkLaunch &a, const double *guess,
   template <> void launch_fk_verdict_retract<N>(const FkLaunch &, const VerdictArgs *, size_t, bool, bool); \
   template <> void launch_fk_sweep_retract_list<N>(const FkLaunch &, const FusedSweepArgs *, size_t, const int32_t *, const uint32_t *); \
   template <> void launch_fk_edge_queue<N>(const FkLaunch &, const VerdictArgs *, size_t, const EdgeQueueArgs *, const FusedSweepArgs *, unsigned); \
-  template <> int fk_edge_queue_waves_per_cu<N>(bool, size_t);
+  template <> int fk_edge_queue_waves_per_cu<N>(const RobotK &, size_t);
 TRK_DECL_FK(1) TRK_DECL_FK(2) TRK_DECL_FK(3) TRK_DECL_FK(4) TRK_DECL_FK(5) TRK_DECL_FK(6) TRK_DECL_FK(7) TRK_DECL_FK(8)
 #undef TRK_DECL_FK
 

@@ -44,14 +44,14 @@ __device__ __forceinline__ FusedKernargsPtr fused_kernargs() {
   return p;
 }
 
-template <int N, bool ROT>
+template <int N, bool ROT, class Form = TableRouting>
 __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk_sweep_fused(
     const double *__restrict__ states, int64_t n, int64_t ld, RobotK K, const double *__restrict__ tab,
     const StepK *__restrict__ steps, int nsteps, FkOut out, const FusedSweepArgs *__restrict__ sa) {
   // (the verdict paths never ask for the backbone length)  Edge samples also get their cell signatures, point by point
   SignatureHook hook{sa, n, sa->sig != nullptr, {}};
   hook.st.init();
-  fk_uniform_body<N, ROT, false, false>(states, n, ld, K, tab, steps, nsteps, out, hook);
+  fk_uniform_body<N, ROT, false, false, Form>(states, n, ld, K, tab, steps, nsteps, out, hook);
   hook.finish();
   __syncthreads();
   const FusedKernargsPtr ka = fused_kernargs();
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk
 // columns.  Block b owns columns [64 b, 64 b + 64) and walks the list in strides of `cap`: in round r its lane i takes
 // configuration list[r cap + 64 b + i] (while that index is below *count) and ORs its verdict bit into the mask.  A block
 // leaves as soon as its slice of the list is exhausted, so with an empty list the launch costs nothing.
-template <int N, bool ROT>
+template <int N, bool ROT, class Form = TableRouting>
 __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk_sweep_fused_list(
     const double *__restrict__ states, int64_t cap, int64_t ld, RobotK K, const double *__restrict__ tab,
     const StepK *__restrict__ steps, int nsteps, FkOut out, const FusedSweepArgs *__restrict__ sa,
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(64, (N <= TRK_FUSED_TWO_WAVE_MAXN ? 2 : 1)) void fk
     const int64_t left = total - offset;
     const int64_t m = left < cap ? left : cap;
     if ((int64_t)blockIdx.x * 64 >= m) break;                     // wave-uniform
-    fk_uniform_body<N, ROT, false, false>(states, m, ld, K, tab, steps, nsteps, out, NoPointHook(), list + offset);
+    fk_uniform_body<N, ROT, false, false, Form>(states, m, ld, K, tab, steps, nsteps, out, NoPointHook(), list + offset);
     __syncthreads();
     const FusedKernargsPtr ka = fused_kernargs();
     const FusedSweepArgs a = *ka->sa;

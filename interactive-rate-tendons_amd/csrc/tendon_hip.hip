@@ -37,6 +37,7 @@
 #include "verdict_kernel.hpp"
 #include "edge_kernel.hpp"
 #include "edge_plan.hpp"
+#include "routing_form.hpp"
 #include "knn_kernel.hpp"
 #include "cache_merge.hpp"
 #include "env_kernel.hpp"
@@ -337,27 +338,10 @@ std::vector<double> t_range(double start, double end, double dt) {
 
 // tendon/get_r_info.cpp:17-40,105-144: routing r, r', r'' of every tendon at arc length t.
 // out: N x 6 {rx, ry, rdx, rdy, rddx, rddy} (z components are identically zero).
-void routing_at(const tr_ctx *c, double t, double *out) {
-  const int N_a = c->K.n_a, N_m = c->K.n_m, N_s = std::max(N_a, N_m);
-  double S[TRK_MAX_COEF], Sd[TRK_MAX_COEF], Sdd[TRK_MAX_COEF];
-  S[0] = 1; Sd[0] = 0; Sdd[0] = 0;
-  if (N_s >= 2) { S[1] = t; Sd[1] = 1; Sdd[1] = 0; }
-  for (int i = 2; i < N_s; i++) { S[i] = t * S[i - 1]; Sd[i] = i * S[i - 1]; Sdd[i] = i * (i - 1) * S[i - 2]; }
-  for (int j = 0; j < c->K.n_tendons; j++) {
-    const double *Cj = &c->C[(size_t)j * N_a], *Dj = &c->D[(size_t)j * N_m];
-    double C_a = 0, C_ad = 0, C_add = 0, D_m = 0, D_md = 0, D_mdd = 0;
-    for (int i = 0; i < N_a; i++) { C_a += Cj[i] * S[i]; C_ad += Cj[i] * Sd[i]; C_add += Cj[i] * Sdd[i]; }
-    for (int i = 0; i < N_m; i++) { D_m += Dj[i] * S[i]; D_md += Dj[i] * Sd[i]; D_mdd += Dj[i] * Sdd[i]; }
-    const double sa = std::sin(C_a), ca = std::cos(C_a);
-    double *o = out + 6 * j;
-    o[0] = D_m * sa;
-    o[1] = D_m * ca;
-    o[2] = D_md * sa + D_m * (ca * C_ad);
-    o[3] = D_md * ca + D_m * (-sa * C_ad);
-    o[4] = D_mdd * sa + 2 * D_md * (ca * C_ad) - D_m * (sa * C_ad * C_ad) + D_m * (ca * C_add);
-    o[5] = D_mdd * ca + 2 * D_md * (-sa * C_ad) - D_m * (ca * C_ad * C_ad) + D_m * (-sa * C_add);
-  }
+routing_form::Spec routing_spec(const tr_ctx *c) {
+  return routing_form::Spec{c->K.n_tendons, c->K.n_a, c->K.n_m, c->C.data(), c->D.data(), c->K.enable_retraction != 0};
 }
+void routing_at(const tr_ctx *c, double t, double *out) { routing_form::row(routing_spec(c), t, out); }
 
 int poly_degree(const double *c, int n) {
   for (int i = n - 1; i > 0; i--) if (std::fabs(c[i]) > 0.0) return i;
@@ -901,7 +885,7 @@ int edge_queue_waves(tr_ctx *ctx) {
   const size_t lds_v = std::max(trk::verdict_lds_bytes(NM, true) + (size_t)trk::EQ_STASH_WORDS * 4, lds_k2);
   int per_cu = 0;
   switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: per_cu = trk::fk_edge_queue_waves_per_cu<N>((bool)ctx->K.enable_rotation, lds_v); break;
+#define TRK_CASE(N) case N: per_cu = trk::fk_edge_queue_waves_per_cu<N>(ctx->K, lds_v); break;
     TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
 #undef TRK_CASE
     default: break;
@@ -1008,6 +992,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
   if (const char *e = std::getenv("TENDON_HIP_FUSED")) { const int v = std::atoi(e); c->fuse = v < 0 ? 0 : (v > 2 ? 2 : v); }
   if (const char *e = std::getenv("TENDON_HIP_RETRACT_SORT")) c->retract_sort_min = std::atoll(e);
   if (std::getenv("TENDON_HIP_RETRACT_KBEGIN_OFF")) c->retract_wave_start = false;
+  const char *routing_env = std::getenv("TENDON_HIP_ROUTING");      // "table": the table form of the right-hand side for every robot (A/B)
   if (const char *e = std::getenv("TENDON_HIP_EDGE_LANES")) { c->edge_lanes = std::max(1, std::min(tr_ctx::kMaxLanes, std::atoi(e))); c->edge_lanes_fixed = true; }
   if (const char *e = std::getenv("TENDON_HIP_EDGE_QUEUE")) { c->edge_queue = std::atoi(e) != 0; c->edge_queue_forced = c->edge_queue; }
   if (const char *e = std::getenv("TENDON_HIP_EDGE_QUEUE_WAVES")) { const int v = std::atoi(e); if (v >= 1 && v <= 8192) c->edge_queue_waves = v; }
@@ -1039,6 +1024,10 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
   c->D.assign(rb->D, rb->D + (size_t)N * rb->n_m);
   c->max_tension.assign(rb->max_tension, rb->max_tension + N);
   for (int j = 0; j < N; j++) { K.min_len[j] = rb->min_length[j]; K.max_len[j] = rb->max_length[j]; }
+  {  // the routing form of the unloaded shared-grid kernels: decided here, once, for all of them (fk_inst.hip: helix_form)
+    const routing_form::Form rf = routing_form::classify(routing_spec(c), routing_env, TRK_K1_TWO_WAVE_MAXN);
+    K.routing_form = rf.form; K.helix_omega = rf.omega; K.helix_rho2 = rf.rho * rf.rho;
+  }
   {  // get_stiffness_matrices, tendon/TendonRobot.cpp:105-148
     const double ro2 = rb->ro * rb->ro, ri2 = rb->ri * rb->ri;
     const double I = (1.0 / 4.0) * M_PI * (ro2 * ro2 - ri2 * ri2);

@@ -19,12 +19,18 @@ struct RobotK {
   double min_len[TRK_MAX_TENDONS];
   double max_len[TRK_MAX_TENDONS];
   double home_Li[TRK_MAX_TENDONS];   // home_shape(0).L_i  (used when retraction is disabled)
+  // the uniform-helix routing form (routing_form.hpp; fk_kernel.hpp: UniformHelix): the pitch every tendon shares and the square
+  // of the radius every tendon shares, formed once on the host.  Read by the kernels of that form only.
+  double helix_omega, helix_rho2;
   int32_t n_tendons, n_a, n_m;
   int32_t enable_rotation, enable_retraction;
   int32_t state_size;
   int32_t n_points;           // P = |t_range(0, L, dL)|
-  int32_t pad_;
+  int32_t routing_form;       // TRK_ROUTING_TABLE | TRK_ROUTING_HELIX: which instantiation the launchers of the unloaded shared-grid
+                              // kernels pick (fk_inst.hip) -- one decision per context (tr_create), never read on the device
 };
+#define TRK_ROUTING_TABLE 0
+#define TRK_ROUTING_HELIX 1
 
 // Tendon routing polynomials and home-length classification, read by the retraction kernel
 // (per-lane arc-length grid) through wave-uniform scalar loads.

@@ -586,7 +586,7 @@ __device__ __forceinline__ LaneVerdict verdict_decide(const VerdictArgs &a, cons
 #ifndef TRK_VERDICT_TWO_WAVE_MAXN
 #define TRK_VERDICT_TWO_WAVE_MAXN 4
 #endif
-template <int N, bool ROT, bool SPH, bool SIG = false>
+template <int N, bool ROT, bool SPH, bool SIG = false, class Form = TableRouting>
 __global__ __launch_bounds__(64, (N <= TRK_VERDICT_TWO_WAVE_MAXN ? 2 : 1)) void fk_verdict(
     const double *__restrict__ states, int64_t n, RobotK K, const double *__restrict__ tab, const StepK *__restrict__ steps,
     int nsteps, double *__restrict__ tips, const VerdictArgs *__restrict__ va) {
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(64, (N <= TRK_VERDICT_TWO_WAVE_MAXN ? 2 : 1)) void 
 
   FkLane<N> fl_;
   FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  fk_uniform_body<N, ROT, false, false>(states, n, 0, K, tab, steps, nsteps, out, ps, nullptr, &fl_);
+  fk_uniform_body<N, ROT, false, false, Form>(states, n, 0, K, tab, steps, nsteps, out, ps, nullptr, &fl_);
 
   // ---- what sweep_body does after its pass 1 (comparisons and one subtraction: nothing here can contract) ----
   ps.template sig_finish<false>();

@@ -46,6 +46,20 @@ template <int N> __global__ __launch_bounds__(64, 2) void rk4_step_only(const do
 template __global__ void trk::rk4_step_only<%d>(const double*, int64_t, int64_t, RobotK, const double*, const StepK*, int, trk::FkOut);
 '''
 
+# the same with the uniform-helix routing form of the right-hand side (fk_kernel.hpp: UniformHelix)
+_RK4_ONLY_HELIX = r'''
+#include <hip/hip_runtime.h>
+#include "tr_types.hpp"
+#include "fk_kernel.hpp"
+namespace trk {
+template <int N> __global__ __launch_bounds__(64, 2) void rk4_step_only_helix(const double *states, int64_t n, int64_t ld, RobotK K,
+                                                                               const double *tab, const StepK *steps, int nsteps, FkOut out) {
+  fk_uniform_body<N, false, false, false, UniformHelix>(states, n, ld, K, tab, steps, nsteps, out);
+}
+}
+template __global__ void trk::rk4_step_only_helix<%d>(const double*, int64_t, int64_t, RobotK, const double*, const StepK*, int, trk::FkOut);
+'''
+
 KERNELS = {
     # name -> (translation unit, steps per configuration are supplied by the caller: P - 1)
     "rk4_step<3>": _RK4_ONLY % 3,
@@ -89,6 +103,21 @@ template __global__ void trk::fk_rk4_batch_uniform<3, false, false>(const double
 #include "fk_kernel.hpp"
 template __global__ void trk::fk_rk4_batch_uniform<4, false, false>(const double*, int64_t, int64_t, RobotK,
                                                                      const double*, const StepK*, int, trk::FkOut);
+''',
+    "rk4_step_helix<3>": _RK4_ONLY_HELIX % 3,
+    "rk4_step_helix<4>": _RK4_ONLY_HELIX % 4,
+    "fk_verdict_helix<3,false>": r'''
+#include <hip/hip_runtime.h>
+#include "tr_types.hpp"
+#include "verdict_kernel.hpp"
+template __global__ void trk::fk_verdict<3, false, false, false, trk::UniformHelix>(const double*, int64_t, RobotK, const double*, const StepK*, int, double*, const trk::VerdictArgs*);
+''',
+    "fk_sweep_fused_helix<3,false>": r'''
+#include <hip/hip_runtime.h>
+#include "tr_types.hpp"
+#include "fused_kernel.hpp"
+template __global__ void trk::fk_sweep_fused<3, false, trk::UniformHelix>(const double*, int64_t, int64_t, RobotK, const double*, const StepK*, int,
+                                                                          trk::FkOut, const trk::FusedSweepArgs*);
 ''',
 }
 

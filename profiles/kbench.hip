@@ -8,6 +8,8 @@
 // Robots: KB_N == 3 -> config 2's helical robot, KB_N == 4 -> config 3's quadratic routing; 129 points, tau ~ U[0, tmax)^N from a
 // small LCG.  Prints the best and the median of KB_REPS launches over 2^KB_LOG2 configurations, the tips' checksum (so variants
 // can be compared bit for bit) and the resources hipcc gave the kernel.  Test infrastructure: nothing here ships.
+// -DKB_HELIX: the uniform-helix routing form of the right-hand side (fk_kernel.hpp: UniformHelix) instead of the table form, for
+// rk4_only and for -DKB_VERDICT alike (KB_N == 3 only: config 3's routing is no helix).  One binary per form.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -28,6 +30,12 @@ constexpr bool kSig = false;
 #ifndef KB_N
 #define KB_N 3
 #endif
+#ifdef KB_HELIX
+static_assert(KB_N == 3, "-DKB_HELIX: only the KB_N == 3 robot is a uniform helix");
+using KbForm = trk::UniformHelix;
+#else
+using KbForm = trk::TableRouting;
+#endif
 #ifndef KB_LOG2
 #define KB_LOG2 20
 #endif
@@ -43,7 +51,7 @@ template <int N> __global__ __launch_bounds__(64, KB_WAVES) void rk4_only(const 
                                                                            const double *__restrict__ tab, const StepK *__restrict__ steps,
                                                                            int nsteps, double *__restrict__ tips) {
   FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tips, nullptr, nullptr, nullptr};
-  fk_uniform_body<N, false, false, false>(states, n, 0, K, tab, steps, nsteps, out);
+  fk_uniform_body<N, false, false, false, KbForm>(states, n, 0, K, tab, steps, nsteps, out);
 }
 }  // namespace trk
 
@@ -77,6 +85,9 @@ int main() {
     const double ro2 = ro * ro, ri2 = ri * ri, I = 0.25 * M_PI * (ro2 * ro2 - ri2 * ri2), Ar = M_PI * (ro2 - ri2), J = 2 * I, G = E / (2 * (1 + nu));
     K.kb0 = E * I; K.kb2 = J * G; K.dkb = K.kb2 - K.kb0; K.ikb0 = 1 / K.kb0; K.ikb2 = 1 / K.kb2; K.ks0 = G * Ar; K.ks2 = E * Ar; K.iks0 = 1 / K.ks0; K.iks2 = 1 / K.ks2;
   }
+#ifdef KB_HELIX
+  K.routing_form = TRK_ROUTING_HELIX; K.helix_omega = C[0][1]; K.helix_rho2 = D[0][0] * D[0][0];
+#endif
   K.residual_threshold = 5e-6; K.radius = 0.015; K.L = L; K.dL = dL; K.n_tendons = N; K.n_a = 3; K.n_m = 3; K.state_size = N; K.n_points = 129;
   std::vector<StepK> steps;
   std::vector<double> tab((1 + 3 * 128) * N * 6);
@@ -124,7 +135,7 @@ int main() {
   for (int r = 0; r < KB_REPS + 2; r++) {
     CK(hipEventRecord(a));
 #ifdef KB_VERDICT
-    hipLaunchKernelGGL((trk::fk_verdict<N, false, false, kSig>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, nullptr, d_st, n, K, d_tab, d_steps, 128, d_tips, d_va);
+    hipLaunchKernelGGL((trk::fk_verdict<N, false, false, kSig, KbForm>), dim3((unsigned)((n + 63) / 64)), dim3(64), lds, nullptr, d_st, n, K, d_tab, d_steps, 128, d_tips, d_va);
 #else
     hipLaunchKernelGGL((trk::rk4_only<N>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, d_st, n, K, d_tab, d_steps, 128, d_tips);
 #endif
@@ -138,7 +149,7 @@ int main() {
   std::sort(ms.begin(), ms.end());
   hipFuncAttributes fa;
 #ifdef KB_VERDICT
-  CK(hipFuncGetAttributes(&fa, (const void *)trk::fk_verdict<N, false, false, kSig>));
+  CK(hipFuncGetAttributes(&fa, (const void *)trk::fk_verdict<N, false, false, kSig, KbForm>));
   {
     std::vector<uint64_t> bits((size_t)((n + 63) / 64));
     CK(hipMemcpy(bits.data(), d_bits, bits.size() * 8, hipMemcpyDeviceToHost));
@@ -148,6 +159,11 @@ int main() {
   }
 #else
   CK(hipFuncGetAttributes(&fa, (const void *)trk::rk4_only<N>));
+#endif
+#ifdef KB_HELIX
+  std::printf("routing form: uniform helix   ");
+#else
+  std::printf("routing form: table   ");
 #endif
   std::printf("N=%d n=%ld (2^%d unless KB_COUNT) waves/SIMD<=%d: best %.3f ms  median %.3f ms  -> %.4g FK/s   regs %d  scratch %zu B   tips sum %.17g abs %.17g\n", N, (long)n, KB_LOG2, KB_WAVES,
               ms.front(), ms[ms.size() / 2], (double)n / (ms.front() * 1e-3), fa.numRegs, (size_t)fa.localSizeBytes, sum, asum);
