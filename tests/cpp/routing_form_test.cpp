@@ -121,6 +121,21 @@ int main() {
     identities(r, f);
   }
   {
+    // the robots of the truth fixtures helix2, helix5, helix6 (tests/golden/make_fk_truth.py) and the common-pitch 7-tendon robot
+    // of tests/test_gpu_rhs_helix.py: 2, 5 and 6 tendons take the helix form, 7 is wider than it is instantiated for
+    const int n[3] = {2, 5, 6};
+    const double omega[3] = {5.0, -4.0, 3.0};
+    for (int q = 0; q < 3; q++) {
+      const Robot r = helix(n[q], omega[q], 0.01);
+      const routing_form::Form f = classify(r.spec(), nullptr, kMaxN);
+      CHECK(f.form == TRK_ROUTING_HELIX && f.omega == omega[q] && f.rho == 0.01);
+      identities(r, f);
+      CHECK(classify(r.spec(), "table", kMaxN).form == TRK_ROUTING_TABLE);
+    }
+    const routing_form::Form f7 = classify(helix(7, 2.0, 0.01).spec(), nullptr, kMaxN);
+    CHECK(kMaxN == 6 && f7.form == TRK_ROUTING_TABLE && f7.omega == 0.0 && f7.rho == 0.0);
+  }
+  {
     // polynomials padded with zero coefficients are what they are without the padding
     Robot r{3, 3, 2, {}, {}};
     for (int k = 0; k < 3; k++) { r.C.insert(r.C.end(), {2 * kPi * k / 3, 5.0, 0.0}); r.D.insert(r.D.end(), {0.01, 0.0}); }

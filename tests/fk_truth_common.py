@@ -28,7 +28,9 @@ import numpy as np
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NEW_RETRACTION = ("config3_ret_edges", "config2_ret_edges", "n1_ret", "n8_ret")       # dL = L / 40, the special s_start values
-FIXTURES = ("config1", "config2", "config3", "config3_rot", "config3_rot_ret", "config2_dl35", "n1", "n8") + NEW_RETRACTION
+NEW_WIDTHS = ("n2", "n5", "n6", "n7")                 # the launch classes between the older widths (two waves / one wave per kernel)
+NEW_HELIX = ("helix2", "helix5", "helix6")            # common-pitch robots: the UniformHelix instantiations of those widths
+FIXTURES = ("config1", "config2", "config3", "config3_rot", "config3_rot_ret", "config2_dl35", "n1", "n8") + NEW_RETRACTION + NEW_WIDTHS + NEW_HELIX
 RETRACTION = ("config3_rot_ret",) + NEW_RETRACTION
 N_STATES = 24
 NEWTON_REL = 2e-14            # fk_kernel.hpp: one Newton step leaves ~2e-14 relative error in 1/x and 1/sqrt(x)
@@ -96,16 +98,44 @@ def abscissae(fx, i):
 
 def robot_from_fixture(irt, fx, **limits):
     """The package robot of a fixture; limits: min_length= / max_length= as (N,) arrays; enable_rotation= overrides the
-    fixture's switch (the states then need a rotation column)."""
+    fixture's switch (the states then need a rotation column); max_tension= one value for every tendon."""
     N = fx["C"].shape[0]
     L, dL, ro, ri, E, nu, r, res, rot, ret = fx["consts"]
     lo = limits.get("min_length", np.full(N, -0.015))
     hi = limits.get("max_length", np.full(N, 0.035))
-    tendons = [irt.TendonSpecs(C=[float(x) for x in fx["C"][j]], D=[float(x) for x in fx["D"][j]], max_tension=float(fx["max_tension"][j]),
+    tendons = [irt.TendonSpecs(C=[float(x) for x in fx["C"][j]], D=[float(x) for x in fx["D"][j]],
+                               max_tension=float(limits.get("max_tension", fx["max_tension"][j])),
                                min_length=float(lo[j]), max_length=float(hi[j])) for j in range(N)]
     return irt.TendonRobot(tendons=tendons, specs=irt.BackboneSpecs(L=float(L), dL=float(dL), ro=float(ro), ri=float(ri), E=float(E), nu=float(nu)),
                            r=float(limits.get("r", r)), enable_rotation=bool(limits.get("enable_rotation", rot)), enable_retraction=bool(ret),
                            residual_threshold=float(res))
+
+
+CURL_TENSION, CURL_RADIUS, N_CURLS = 80.0, 0.012, 64
+
+
+def curled_states(fx):
+    """(64, N + 1) tightly curled states of a fixture's robot with max_tension = CURL_TENSION, r = CURL_RADIUS and length limits of
+    +- 1 m (the recipe of test_self_collision_cases, tests/test_gpu_parity.py), rotation on.  A backbone of 0.2 m closes on itself
+    where ONE tendon pulls with ~40 N or more; equal pulls all round only compress it, and beyond ~50 N the initial bending no
+    longer converges.  So: one tendon at U[36, 56) N, its neighbour at up to 15 % of that, the others below 0.5 N -- self-
+    colliding, free and unconverged states side by side (counted with the oracle alone in tests/test_fk_truth.py)."""
+    N = fx["C"].shape[0]
+    rng = np.random.default_rng(21 + N)
+    rows = np.arange(N_CURLS)
+    main = rng.integers(0, N, N_CURLS)
+    T = rng.uniform(36.0, 56.0, N_CURLS)
+    st = rng.uniform(0.0, 0.5, (N_CURLS, N + 1))
+    st[rows, main] = T
+    st[rows, (main + 1) % N] = rng.uniform(0.0, 0.15, N_CURLS) * T
+    st[:, N] = rng.uniform(-np.pi, np.pi, N_CURLS)
+    return np.ascontiguousarray(st)
+
+
+def curled_robot(irt, fx):
+    N = fx["C"].shape[0]
+    return robot_from_fixture(irt, fx, enable_rotation=True, max_tension=CURL_TENSION, r=CURL_RADIUS, min_length=np.full(N, -1.0),
+                              max_length=np.full(N, 1.0))
 
 
 def err_vs_truth(x, hi, lo):

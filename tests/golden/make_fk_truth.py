@@ -44,6 +44,12 @@ taut tendon, two states with every tendon at 95 - 100 % of max_tension.  With re
 the fixtures of fk_truth_common.NEW_RETRACTION (dL = L / 40) give rows 0 .. 14 the s_start values of
 fk_truth_common.special_s_start instead: aligned grids, first intervals of two RK4 steps, two- and one-point backbones, s_start
 = L and beyond.
+
+Robots: BASELINE configs 1 - 3 and their variants; n<k>, the k-tendon robots of test_fk_other_tendon_counts (random pitches, a
+radius slope: table form), k = 1, 2, 5, 6, 7, 8 -- every launch class of the per-N choices in fk_launch.hpp (two waves up to 6 for
+the stored-point kernels, up to 5 for the fused kernel, up to 4 for the verdict kernels); helix<k>, k = 2, 5, 6: one pitch and one
+radius on all tendons, the UniformHelix instantiations (fk_kernel.hpp) that the 256-state fixtures of make_fk_truth_helix.py
+(N = 1, 3, 4) do not reach.
 """
 import importlib
 import importlib.util
@@ -352,6 +358,17 @@ def _counted_robot(irt, n_tendons, retraction=False):
                            enable_retraction=retraction)
 
 
+HELIX_PITCH = {"helix2": 5.0, "helix5": -4.0, "helix6": 3.0}          # rad/m, one pitch and one radius per robot
+
+
+def _helix_robot(irt, name):
+    """Common-pitch robots of the tendon counts whose UniformHelix instantiation (fk_kernel.hpp) no other fixture runs: the
+    frame of _counted_robot (rotation on, dL = 4 mm, max_tension 12) with C = [2 pi k / n, omega], D = [0.01]."""
+    n = int(name[5:])
+    tendons = [irt.TendonSpecs(C=[2 * np.pi * k / n, HELIX_PITCH[name]], D=[0.01], max_tension=12.0) for k in range(n)]
+    return irt.TendonRobot(tendons=tendons, specs=irt.BackboneSpecs(dL=0.004), enable_rotation=True)
+
+
 def fixture_robot(irt, name):
     """(robot, tension cap of its random states, seed of its random states)"""
     W = irt.workloads
@@ -374,6 +391,8 @@ def fixture_robot(irt, name):
         if name in ftc.NEW_RETRACTION:
             r.specs.dL = r.specs.L / 40
         return r, (15.0 if r.enable_retraction else None), 44 + 100 * (name in ftc.NEW_RETRACTION)
+    if name in HELIX_PITCH:
+        return _helix_robot(irt, name), 12.0 / np.sqrt(int(name[5:])), 300 + int(name[5:])
     n = int(name[1:].split("_")[0])
     return _counted_robot(irt, n, name.endswith("_ret")), 12.0 / np.sqrt(n), 7 + n + 100 * name.endswith("_ret")
 

@@ -30,7 +30,7 @@ for _p in (ROOT, TESTS, HERE):
 import loaded_fk_reference as ref                                    # noqa: E402
 import make_fk_truth as mft                                          # noqa: E402
 
-NAMES = ("config1", "n1", "n8", "config3_rot")
+NAMES = ("config1", "n1", "n8", "config3_rot", "n5", "n6")          # new names go last: case C is seeded by position
 CASES = ("A", "B", "C")
 WRENCH_A = np.array([0.05, -0.03, 0.02, 1e-3, -2e-3, 5e-4])
 GRAVITY = np.array([0.0, -2.4525, 0.0])

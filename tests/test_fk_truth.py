@@ -186,6 +186,56 @@ def test_bounds_see_what_the_parity_bar_lets_through(orc, monkeypatch):
     assert np.abs(d[0]).max() <= 1e-9 and np.abs(d[2]).max() <= 1e-10 and np.abs(d[3]).max() <= 1e-10
 
 
+@pytest.mark.parametrize("name", ["n5", "helix5"])
+def test_bounds_of_the_five_tendon_fixtures_see_tendon_4(orc, monkeypatch, name):
+    """test_bounds_see_what_the_parity_bar_lets_through on the widths of round 19, at the LAST tendon of five -- the one a
+    kernel of another width would drop or misplace: its r'' scaled by 1 + 1e-9 leaves the bound on most states and stays under
+    1e-9 m / 1e-10."""
+    import test_oracle as to
+    fx = ftc.load(name)
+    assert fx["C"].shape[0] == 5
+    _, (p, R, L, Li) = _oracle_result(orc, fx)
+    plain = to.np_rinfo
+
+    def run():
+        out = [_np_rk4(fx, i, _steps(fx, i)) for i in range(ftc.N_STATES)]
+        pts = np.array([o[0] for o in out])
+        th = fx["states"][:, 5]                                          # rotate_z of the points; the frame, L and L_i shifts stay unrotated
+        c, s = np.cos(th)[:, None], np.sin(th)[:, None]
+        rot = np.stack([c * pts[:, :, 0] - s * pts[:, :, 1], s * pts[:, :, 0] + c * pts[:, :, 1], pts[:, :, 2]], axis=2)
+        return [rot] + [np.array([o[k] for o in out]) for k in (2, 3)]
+
+    base = run()
+    monkeypatch.setattr(to, "np_rinfo", lambda C, D, t: [(r, rd, rdd * (1 + 1e-9) if j == 4 else rdd) for j, (r, rd, rdd) in enumerate(plain(C, D, t))])
+    bent = run()
+    d = [b - a for a, b in zip(base, bent)]
+    ratio, ok = ftc.compare(fx, p + d[0], R, L + d[1], Li + d[2])
+    print("%s, r'' of tendon 4 scaled by 1 + 1e-9: %d of 24 states outside their bound, worst error / bound %.3g, largest point shift %.3g m"
+          % (name, (~ok).sum(), ratio, np.abs(d[0]).max()))
+    assert (~ok).sum() > ftc.N_STATES // 2
+    assert np.abs(d[0]).max() <= 1e-9 and np.abs(d[1]).max() <= 1e-10 and np.abs(d[2]).max() <= 1e-10
+
+
+@pytest.mark.parametrize("name", ["n5", "n6", "helix5", "helix6"])
+def test_curled_states_collide_by_the_oracle_alone(orc, name):
+    """The states of test_fallback_pass_on_curled_states (tests/test_gpu_fk_truth.py), here with the oracle's own shapes: at
+    least 8 converge and collide with themselves, at least 8 converge and do not, all of those within the +- 1 m length limits."""
+    fx = ftc.load(name)
+    N = fx["C"].shape[0]
+    L, dL, ro, ri, E, nu, r, res, rot, ret = (float(x) for x in fx["consts"])
+    rob = orc.Robot(fx["C"].tolist(), fx["D"].tolist(), r=ftc.CURL_RADIUS, L=L, dL=dL, ro=ro, ri=ri, E=E, nu=nu, max_tension=[ftc.CURL_TENSION] * N,
+                    min_length=[-1.0] * N, max_length=[1.0] * N, enable_rotation=True, enable_retraction=False, residual_threshold=res)
+    st = ftc.curled_states(fx)
+    assert st.shape == (ftc.N_CURLS, N + 1) and (st[:, :N] <= ftc.CURL_TENSION).all()
+    shapes = [rob.shape(s) for s in st]
+    home = rob.home_shape()["L_i"]
+    conv = np.array([bool(s["converged"]) for s in shapes])
+    hits = np.array([rob.collides_self(s["p"]) for s in shapes])
+    assert all(rob.is_within_length_limits(home, s["L_i"]) for s, c in zip(shapes, conv) if c)
+    print("%s: %d converged and self-colliding, %d converged and free, %d unconverged" % (name, (conv & hits).sum(), (conv & ~hits).sum(), (~conv).sum()))
+    assert (conv & hits).sum() >= 8 and (conv & ~hits).sum() >= 8
+
+
 def test_point_bound_sees_one_long_step_in_the_first_interval(orc):
     """A retracted lane whose own first interval is longer than dL takes two RK4 steps there (dL, then the rest), as
     integrate_times does.  One step over the whole interval instead -- 1.25 dL for dL + 0.25 dL -- is a fourth-order difference

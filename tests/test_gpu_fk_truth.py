@@ -1,6 +1,6 @@
 """The integrator of the FK kernels against an extended-precision evaluation of the scheme they restate.
 
-The fixtures tests/golden/fk_truth_*.npz (tests/golden/make_fk_truth.py) hold, for 24 states of twelve small robots, the
+The fixtures tests/golden/fk_truth_*.npz (tests/golden/make_fk_truth.py) hold, for 24 states of nineteen small robots, the
 40-digit result of the discrete scheme (dense 6x6 right-hand side, classical RK4 over the oracle's step sequence, exact
 start values) and two CPU-side error figures per state: E_ref, how far the fp64 oracle is from that truth, and E_design,
 how far one Newton step's 2e-14 in the kernels' reciprocals moves it.  Every output of every state must lie within
@@ -21,7 +21,12 @@ but the .npz files: no mpmath, no oracle, no reference.
   (e) fk_verdict_retract (prologue launch -> hand-over planes -> tip-aligned launch) through the same comparator, with the
       length change home - L_i taken per state from the two truths, and the tips all verdict kernels report;
   (f) fk_edge_queue, alone: edges that turn a state about the z axis, whose interior samples only the queue integrates and
-      which all have the state's L_i, with the vertices' signature rows given so that no other kernel sees them."""
+      which all have the state's L_i, with the vertices' signature rows given so that no other kernel sees them;
+  (g) the fused stored-point kernel fk_sweep_fused<N> (voxel caches, tr_connect_edges_indexed, TENDON_HIP_FUSED=1) and the
+      separate K1 + K2 launches beside it, on every fixture without retraction, in both routing forms where the robot is a
+      uniform helix;
+  (h) fk_sweep_fused_list, the fallback pass of the verdict path, on tightly curled states of the 5- and 6-tendon robots -- the
+      one test here that asks the oracle: its pairwise self-collision sweep on the device's own points."""
 import numpy as np
 import pytest
 
@@ -125,9 +130,11 @@ def _probe_limit(fx, dl, b, i, j, which, limit, passes, got, what):
                            (dl[bad, j] - limit), b[bad, j])
 
 
-@pytest.mark.parametrize("name,spheres", [("config2", False), ("config3", False), ("n1", False), ("n8", False), ("config2", True)])
+@pytest.mark.parametrize("name,spheres", [("config2", False), ("config3", False), ("n1", False), ("n8", False), ("config2", True), ("n5", False),
+                                          ("n6", False), ("n7", False), ("helix5", False), ("helix6", False), ("n5", True)])
 def test_verdict_kernel_length_test_as_comparator(irt, name, spheres):
-    """fk_verdict<3>, <4>, <1>, <8> and the sphere-checker form of <3>.  Probes: the four states with the largest bound and the
+    """fk_verdict<3>, <4>, <1>, <8> and the sphere-checker form of <3>; fk_verdict<5> (the first width at one wave), <6>, <7>, the
+    UniformHelix form of <5> and <6>, and the sphere-checker form of <5>.  Probes: the four states with the largest bound and the
     four with the smallest, each on its tendon with the largest |home - L_i|; per probe four robots that differ in one limit
     of that tendon (all other limits wide open), an empty voxel grid, all 24 states per launch.
     A state that passes the kernel's length test and then needs the exact self-collision sweep has its flags written again
@@ -158,6 +165,83 @@ def test_verdict_kernel_length_test_as_comparator(irt, name, spheres):
             bad = np.flatnonzero((got != want) & ~near)
             assert bad.size == 0, (name, "state %d tendon %d %s_length %s" % (i, j, which, "passes" if passes else "fails"), bad,
                                    (dl[bad, j] - limit), b[bad, j])
+
+
+# ---- the fused stored-point kernels ------------------------------------------------------------------------------------------
+NO_RETRACTION = [n for n in ftc.FIXTURES if n not in ftc.RETRACTION]
+UNIFORM_HELIX = ("config1", "config2", "config2_dl35") + ftc.NEW_HELIX       # one pitch, one radius: routing_form.hpp picks UniformHelix
+
+
+@pytest.mark.parametrize("name", NO_RETRACTION)
+def test_fused_stored_point_kernels_against_truth(irt, name):
+    """Which kernel an entry launches (tendon_hip.hip: launch_fk_sweep and launch_fused, validate_batch_dev_impl, tr_voxelize_batch),
+    backbone checker, no retraction, empty 64^3 grid:
+      TENDON_HIP_FUSED=1  is_valid_detail -> launch_fk_sweep -> launch_fused: fk_sweep_fused<N>, K1 + K2 over stored points in one
+                          launch, tips from its own integration; voxelize_batch -> the same kernel with voxel_test = 0 (then
+                          the block-list kernels, which do not touch the tips);
+      TENDON_HIP_FUSED=0  is_valid_detail -> launch_fk (fk_rk4_batch_uniform<N>) + launch_sweep (the K2 sweep) as separate
+                          launches; voxelize_batch likewise;
+      TENDON_HIP_FUSED=2  is_valid_detail -> launch_verdict: fk_verdict<N>, then fk_sweep_fused_list<N> over the pending states
+                          (test_verdict_kernels_tips_against_truth has its tips).
+    (i) FUSED=1 and (ii) FUSED=0: both entries' tips within the point bound of the truth's last point, every state converged;
+    robots that are uniform helices run (i) in the helix and in the table form.  (iii) verdicts and flags of FUSED = 0, 1, 2 equal
+    on the 24 states."""
+    fx = ftc.load(name)
+    rows, q = np.arange(ftc.N_STATES), ftc.tip_rows(fx)
+    bound = ftc.bounds(fx)["p"]
+    det = {}
+    for fuse, form in [(1, "helix"), (1, "table"), (0, "helix"), (2, "helix")]:
+        if form == "table" and name not in UNIFORM_HELIX:
+            continue
+        env = dict(TENDON_HIP_FUSED=fuse, **({"TENDON_HIP_ROUTING": "table"} if form == "table" else {}))
+        with ftc.with_env(**env):
+            chk = irt.VoxelBackboneValidityChecker(ftc.robot_from_fixture(irt, fx), irt.VoxelEnvironment(), _grid(irt, 64))
+        d = det[fuse, form] = chk.is_valid_detail(fx["states"])
+        vox = chk.engine.voxelize_batch(fx["states"]) if fuse < 2 else None
+        chk.engine.close()
+        assert (d["flags"] & 1).all()
+        if fuse == 2:
+            continue
+        assert np.array_equal(vox["shape_valid"], np.asarray(d["valid"], bool))      # an empty grid: the shape test is the verdict
+        for what, tips in (("is_valid_detail", d["tips"]), ("voxelize_batch", vox["tips"])):
+            err = ftc.err_vs_truth(tips, fx["p_hi"][rows, q], fx["p_lo"][rows, q]).max(axis=1)
+            print("%s: FUSED=%d%s %s tips, max error / bound %.3f" % (name, fuse, " (table form)" if form == "table" else "", what,
+                                                                       (err / bound).max()))
+            assert (err <= bound).all(), (fuse, form, what, np.flatnonzero(err > bound), (err / bound).max())
+    for key in ((0, "helix"), (2, "helix")):
+        assert np.array_equal(det[key]["flags"], det[1, "helix"]["flags"]), key
+        assert np.array_equal(det[key]["valid"], det[1, "helix"]["valid"]), key
+
+
+@pytest.mark.parametrize("name", ["n5", "n6", "helix5", "helix6"])
+def test_fallback_pass_on_curled_states(irt, orc, helpers, name):
+    """fk_sweep_fused_list<5>, <6> in both routing forms: 64 tightly curled states (fk_truth_common.curled_states) through
+    fk_verdict and, for every state whose milestones do not settle the self-collision test, the fallback pass, whose workspace
+    TENDON_HIP_FB_CAP=64 makes exactly one wave wide.  Flags and verdicts equal the oracle's tests (collides_self,
+    is_within_length_limits) on the device's own stored points.  No fallback counter leaves the library; but fk_verdict never
+    clears the self-collision bit of a converged state within its limits itself (verdict_kernel.hpp: verdict_decide sets it where the
+    milestones resolve, and hands every other state over), so a state with bits 1 and 2 set and bit 4 clear was decided by the
+    fallback pass: at least 8 of them (tests/test_fk_truth.py counts them with the oracle alone)."""
+    fx = ftc.load(name)
+    st = ftc.curled_states(fx)
+    robot = ftc.curled_robot(irt, fx)
+    with ftc.with_env(TENDON_HIP_FB_CAP=64):
+        chk = irt.VoxelBackboneValidityChecker(robot, irt.VoxelEnvironment(), _grid(irt, 128))
+    got = chk.is_valid_detail(st)
+    fk = chk.engine.fk_batch(st)
+    home = chk.engine.home_lengths()
+    chk.engine.close()
+    orb = helpers.oracle_robot(orc, robot)
+    conv = fk["converged"].astype(bool)
+    within = np.array([bool(conv[i]) and orb.is_within_length_limits(home, fk["L_i"][i]) for i in range(len(st))])
+    hits = np.array([bool(conv[i]) and orb.collides_self(fk["p"][i]) for i in range(len(st))])
+    want = conv.astype(np.uint8) | ((conv & within).astype(np.uint8) << 1) | ((conv & within & ~hits).astype(np.uint8) << 2)
+    fallback = ((got["flags"] & 7) == 3) & ((got["flags"] & 16) == 0)
+    print("%s: %d converged, %d decided as self-colliding by the fallback pass, %d free" % (name, conv.sum(), fallback.sum(), ((got["flags"] & 4) != 0).sum()))
+    assert np.array_equal(got["flags"] & 7, want), np.flatnonzero((got["flags"] & 7) != want)
+    assert not (got["flags"] & 16).any()                                 # every point inside the grid: nothing else decides
+    assert np.array_equal(np.asarray(got["valid"], bool), conv & within & ~hits)
+    assert fallback.sum() >= 8 and ((got["flags"] & 4) != 0).sum() >= 8
 
 
 # ---- retraction: the stored-point kernel with its home lengths, the verdict form, the verdict kernels' tips ---------------------
@@ -264,7 +348,7 @@ def test_retraction_verdict_kernel_length_test_as_comparator(irt, name, spheres)
 
 @pytest.mark.parametrize("name", ftc.FIXTURES)
 def test_verdict_kernels_tips_against_truth(irt, name):
-    """The tips fk_verdict<1, 3, 4, 8> and fk_verdict_retract report (is_valid_detail: no stored point behind them) lie within the
+    """The tips fk_verdict<1 .. 8> (both routing forms' instantiations at 2, 5, 6) and fk_verdict_retract report (is_valid_detail: no stored point behind them) lie within the
     point bound of the truth's last point, for every state the kernel reports converged -- all of them."""
     fx = ftc.load(name)
     rows, q = np.arange(ftc.N_STATES), ftc.tip_rows(fx)
@@ -297,7 +381,7 @@ def _signature_rows(vox, pts, width):
     return out.view(np.int32)
 
 
-@pytest.mark.parametrize("name", ["config3_rot", "n1", "n8", "config2"])
+@pytest.mark.parametrize("name", ["config3_rot", "n1", "n8", "config2", "n5", "n6", "helix5", "helix6"])
 def test_edge_queue_length_test_as_comparator(irt, name):
     """fk_edge_queue integrates every interior sample of an edge and nothing else does when the vertices come with their signature
     rows (tr_validate_edges_indexed_sig_dev takes every vertex as valid).  Edge i turns state i about the z axis, from theta - 0.125
@@ -305,7 +389,7 @@ def test_edge_queue_length_test_as_comparator(irt, name):
     depend on the angle.  An edge nothing subdivides (n_fk == 2: a straight backbone does not move) is valid whatever the limit;
     an edge with interior samples is valid exactly when its state's truth passes the limit.  Probes as in
     test_verdict_kernel_length_test_as_comparator, among the states whose edge has interior samples.  Empty 256^3 grid on
-    +- 0.3 m; 128^3 for n1 and n8, whose dL = 4 mm the backbone checker refuses on 2.3 mm voxels (VoxelBackboneValidityChecker.h:
+    +- 0.3 m; 128^3 for n1, n8, n5, n6, helix5 and helix6, whose dL = 4 mm the backbone checker refuses on 2.3 mm voxels (VoxelBackboneValidityChecker.h:
     37-45) while the sphere checker, which has no such check, hands no signature rows over.  config2: the fixture's states with
     rotation switched on."""
     import torch

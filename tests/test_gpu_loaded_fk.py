@@ -20,7 +20,7 @@ import loaded_fk_reference as ref                                    # noqa: E40
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("config1", "n1", "n8", "config3_rot")
+NAMES = ("config1", "n1", "n8", "config3_rot", "n5", "n6")          # n5, n6: fk_loaded_uniform<5>, <6>, the widest at two waves
 CASES = ("A", "B", "C")
 KEYS = ("p", "L", "L_i", "vu0", "vuL", "residual", "iters", "num_fk_calls", "converged")
 

@@ -33,7 +33,12 @@ PROBLEMS = {"config1_B": ("config1", "B", "base", 3.0, 0.0),
             "config1_C": ("config1", "C", "base", 3.0, 0.0),
             "n1_B": ("n1", "B", "world", 1.5, 0.3),
             "config3_rot_base": ("config3_rot", "B", "base", 0.5, 0.1),
-            "config3_rot_world": ("config3_rot", "B", "world", 0.5, 0.1)}
+            "config3_rot_world": ("config3_rot", "B", "world", 0.5, 0.1),
+            # S = 6, 7, 9: fk_loaded_lin<5>, <6>, <8> and ikl_lm_step<6>, <7>, <9> (from <5> on the forms that need AGPRs)
+            "n5_world": ("n5", "B", "world") + ikr.WIDE_SIGMA,
+            "n6_world": ("n6", "B", "world") + ikr.WIDE_SIGMA,
+            "n8_world": ("n8", "B", "world") + ikr.WIDE_SIGMA}
+WIDE = ("n5_world", "n6_world", "n8_world")                             # solved with max_iters = 25, as the numpy scheme was
 
 
 @pytest.fixture(scope="module")
@@ -95,7 +100,7 @@ def solved(world):
                 wrench = wrench[0] if wrench.any() else None
             if (dist == dist[0]).all():
                 dist = dist[0]
-        out = ik(eng, starts, goals, wrench, dist, frame)
+        out = ik(eng, starts, goals, wrench, dist, frame, **(dict(max_iters=ikr.WIDE_MAX_ITERS) if key in WIDE else {}))
         w, d = ikr.load_rows(rob, out["state"], wrench, dist, frame)
         with np.errstate(all="ignore"):
             cold = ref.shoot(rob, out["state"], F_e=w[:, :3], L_e=w[:, 3:], f_e=d[:, :3], l_e=d[:, 3:])
@@ -134,8 +139,11 @@ def test_it_is_a_solution(world, solved, key):
     assert np.abs(out["error"] - np.linalg.norm(goals - out["tip"], axis=1)).max() <= 1e-12
 
 
-@pytest.mark.parametrize("key", ["config3_rot_base", "config3_rot_world"])
+@pytest.mark.parametrize("key", ["config3_rot_base", "config3_rot_world"] + list(WIDE))
 def test_rotation_in_both_frames(solved, key):
+    """WIDE: the reach count is not 21 by decree.  The numpy scheme reaches 24, 22, 21 of 24 in 25 outer iterations
+    (tests/test_loaded_ik_reference.py); the device, with the same max_iters, must reach at 1e-4 m every problem that scheme ends
+    at 0.5e-4 m or less (loaded_ik_reference.WIDE_HALF_TOL_ROWS)."""
     s = solved(key)
     out, goals, bound = s["out"], s["goals"], s["bound"]
     reached = out["error"] <= TOL
@@ -143,7 +151,12 @@ def test_rotation_in_both_frames(solved, key):
     print("%s: reached %d of 24, iters <= %d, integrations %.1f per problem; reported error off the cold numpy solve's by <= %.3g of bound"
           % (key, reached.sum(), out["iters"].max(), out["num_fk_calls"].mean(), (np.abs(miss_cold - out["error"]) / bound).max()))
     assert out["equilibrium"].all() and s["cold"]["converged"].all()
-    assert reached.sum() >= 21
+    if key in WIDE:
+        must = list(ikr.WIDE_HALF_TOL_ROWS[PROBLEMS[key][0]])
+        assert reached[must].all(), (must, out["error"][must])
+        assert (out["iters"] <= ikr.WIDE_MAX_ITERS).all()
+    else:
+        assert reached.sum() >= 21
     assert (np.abs(miss_cold - out["error"]) <= bound).all()
     th = out["state"][:, -1]
     assert ((th >= -np.pi) & (th < np.pi)).all()

@@ -91,7 +91,7 @@ def test_small_tip_force_deflects_like_a_timoshenko_cantilever(rob40):
     assert out["converged"][0] and abs(rel) <= 1e-6
 
 
-@pytest.mark.parametrize("name", ["config1", "n1", "n8", "config3_rot"])
+@pytest.mark.parametrize("name", ["config1", "n1", "n8", "config3_rot", "n5", "n6"])
 def test_generator_reproduces_its_fixture(gen, name):
     """two states per fixture, every case; 1e-12 m / 1e-9 relative: the same arithmetic on, perhaps, another LAPACK"""
     fx = np.load(gen.path(name))

@@ -62,6 +62,22 @@ def test_it_reaches_the_loaded_tips(gen, name, case, sigma_tension, sigma_rotati
     assert np.abs(x - out["tip"]).max() <= 1e-9
 
 
+@pytest.mark.parametrize("name", ["n5", "n6", "n8"])
+def test_it_reaches_the_loaded_tips_at_wider_state_sizes(gen, name):
+    """S = 6, 7, 9 under gravity in the world frame at 25 outer iterations: at least 21 of 24 reached (measured: 24, 22, 21; rows
+    20 - 22 start and end on the tension box), and the rows this scheme ends at half the stop threshold are the recorded ones."""
+    rob, st, fx, goals = _case(gen, name, "B")
+    starts = ikr.offset_starts(rob, st, *ikr.WIDE_SIGMA)
+    out = ikr.inverse_kinematics_loaded_batch(rob, starts, goals, max_iters=ikr.WIDE_MAX_ITERS, dist=GRAVITY, frame="world")
+    reached = out["error"] <= 1e-4
+    print("%s: reached %d of 24 (not: %s), outer iterations <= %d" % (name, reached.sum(), np.flatnonzero(~reached).tolist(), out["iters"].max()))
+    assert out["equilibrium"].all()
+    assert reached.sum() >= 21
+    assert tuple(np.flatnonzero(out["error"] <= 0.5e-4)) == ikr.WIDE_HALF_TOL_ROWS[name]
+    lo, hi = ikr.bounds(rob)
+    assert ((out["state"] >= lo) & (out["state"] <= hi)).all()
+
+
 def test_the_reduced_jacobian_is_the_derivative_of_the_loaded_tip(gen):
     rob, st, fx, _ = _case(gen, "config1", "B")
     dist = fx["dist_B"][0]
