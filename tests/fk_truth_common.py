@@ -20,6 +20,21 @@ Retraction fixtures (consts[9] = 1) also hold
                                                        first interval (route_tendon, fk_retract_kernel.hpp); added to E_design
   home_hi (24, N) f64, home_lo f32                     truth of home_shape(s_start).L_i: the rule orc_home_shape follows, in mpmath
   Eref_home (24, N)                                    distance of the oracle's home lengths from it
+
+Loaded fixtures, loaded_fk_truth_<name>.npz (tests/golden/make_loaded_fk_truth.py; the robots of make_loaded_fk.NAMES, none with
+retraction; one integration of the loaded rod from given base strains, no shooting):
+  states, C, D, consts, max_tension   as above
+  steps (K, 2), step_row (K,)         the RK4 step sequence (t, h) and the backbone point a step ends in: one for all states
+  n_points (), pt_idx (Q,)            P, the point count of every state, and the backbone points that are stored (all up to P = 64)
+and per load case X of LOADED_CASES (A, C, D of make_loaded_fk.py), loads in the base frame before the state's rotation:
+  wrench_X, dist_X, vu0_X (24, 6)     (F_e, L_e), (f_e, l_e) and the start strains (v0, u0): loaded_fk_<name>.npz's, the truth's input
+  p_hi_X (24, Q, 3) f64, p_lo_X f32   truth of the stored points; R_hi_X (24, 9), R_lo_X the tip frame, column-major
+  L_hi_X (24,), L_lo_X; Li_hi_X (24, N), Li_lo_X
+  vu_hi_X (24, 6), vu_lo_X            the tip strains (v, u)
+  e_hi_X (24, 6), e_lo_X              the tip residual (n - F_t - F_e, m - L_t - L_e)
+  e_terms_X (24, 6)                   per residual component the largest magnitude among the terms summed into it
+  Eref_<k>_X, Edes_<k>_X              k = p, R, L (24,), Li (24, N), vu, e (24, 6): distance of loaded_fk_reference.evaluate from the
+                                      truth, largest shift under the one-Newton-step perturbation model
 """
 import contextlib
 import os
@@ -171,6 +186,57 @@ def bounds(fx):
     if "home_hi" in fx:
         out["home"] = np.maximum(4.0 * fx["Eref_home"], (fx["n_points"][:, None] + 2) * np.spacing(np.abs(fx["home_hi"])))
     return out
+
+
+LOADED_CASES = ("A", "C", "D")
+LOADED_KEYS = ("p", "R", "L", "Li", "vu", "e")
+
+
+def loaded_path(name):
+    return os.path.join(GOLD, "loaded_fk_truth_%s.npz" % name)
+
+
+def load_loaded(name):
+    with np.load(loaded_path(name)) as d:
+        return {k: d[k] for k in d.files}
+
+
+def loaded_bounds(fx, case):
+    """The bounds of a loaded fixture's case, beside bounds(): 4 (E_ref + E_design), at least 4 ulp of the output's magnitude -- per
+    state; points: the largest coordinate of the backbone; R: 1; L, every L_i and every tip strain: themselves.  For a component
+    of the tip residual e the magnitude is the largest term summed into it (e_terms): e is a difference of forces of up to tens of
+    newtons that is ~1e-11 N at a solution, and its rounding error has the size of those terms, not of e.  `enorm`, the bound on
+    |e|, is the sum of the six component bounds: | |a| - |b| | <= |a - b|_2 <= |a - b|_1."""
+    k = lambda key: fx["%s_%s" % (key, case)]
+    f = lambda key, mag: np.maximum(4.0 * (k("Eref_" + key) + k("Edes_" + key)), 4.0 * np.spacing(np.abs(mag)))
+    out = dict(p=f("p", np.abs(k("p_hi")).max(axis=(1, 2))), R=f("R", np.ones(N_STATES)), L=f("L", k("L_hi")), L_i=f("Li", k("Li_hi")),
+               vu=f("vu", k("vu_hi")), e=f("e", k("e_terms")))
+    out["enorm"] = out["e"].sum(axis=1)
+    return out
+
+
+def loaded_e_norm(fx, case):
+    """(24,) |e| of the truth, in fp64 from the six hi + lo components (relative error ~1e-16: far inside the enorm bound)."""
+    return np.linalg.norm(fx["e_hi_" + case] + fx["e_lo_" + case].astype(np.float64), axis=1)
+
+
+def loaded_errors(fx, case, p, R_tip, L, L_i, vuL=None, e=None):
+    """Per-state errors of an fp64 result against a loaded case's truth, in loaded_bounds' keys (vu and e only where given).
+    p: (24, P, 3); R_tip: (24, 9) column-major; e: (24, 6) residual components."""
+    k = lambda key: (fx["%s_hi_%s" % (key, case)], fx["%s_lo_%s" % (key, case)])
+    out = dict(p=err_vs_truth(np.asarray(p)[:, fx["pt_idx"]], *k("p")).max(axis=(1, 2)), R=err_vs_truth(R_tip, *k("R")).max(axis=1), L=err_vs_truth(L, *k("L")),
+               L_i=err_vs_truth(L_i, *k("Li")))
+    if vuL is not None:
+        out["vu"] = err_vs_truth(vuL, *k("vu"))
+    if e is not None:
+        out["e"] = err_vs_truth(e, *k("e"))
+    return out
+
+
+def loaded_ratios(fx, case, errs):
+    """{key: (24,) error / bound} of loaded_errors' result."""
+    b = loaded_bounds(fx, case)
+    return {key: (v / b[key]).reshape(N_STATES, -1).max(axis=1) for key, v in errs.items()}
 
 
 def length_change(fx, home=None):

@@ -172,8 +172,10 @@ def stiffness(ro, ri, E, nu):
     return [G * Ar, G * Ar, E * Ar], [E * I, E * I, 2 * I * G]
 
 
-def deriv(rt, Kse, Kbt, tau, x, signs=None):
-    """np_deriv (tests/test_oracle.py) in mpmath.  x = dict(p, R (3x3), v, u); returns the rates and (|v|, [|p_dot_i|])."""
+def deriv(rt, Kse, Kbt, tau, x, signs=None, f_e=None, l_e=None):
+    """np_deriv (tests/test_oracle.py) in mpmath.  x = dict(p, R (3x3), v, u); returns the rates and (|v|, [|p_dot_i|]).
+    f_e, l_e: the distributed force and moment per unit length, three mpf each in the base frame; they enter as rhs() of
+    tests/loaded_fk_reference.py has them, c -= R^T l_e and d -= R^T f_e with R the frame of x.  None: the unloaded arithmetic."""
     R, v, u = x["R"], x["v"], x["u"]
     A = [[ZERO] * 3 for _ in range(3)]; B = [[ZERO] * 3 for _ in range(3)]
     G = [[ZERO] * 3 for _ in range(3)]; H = [[ZERO] * 3 for _ in range(3)]
@@ -202,6 +204,10 @@ def deriv(rt, Kse, Kbt, tau, x, signs=None):
     Ku = [Kbt[i] * u[i] for i in range(3)]
     c = [-x1 - x2 - x3 for x1, x2, x3 in zip(_cross(u, Ku), _cross(v, Kv), b)]
     d = [-x1 - x2 for x1, x2 in zip(_cross(u, Kv), a)]
+    if l_e is not None:
+        c = [y - (R[0][i] * l_e[0] + R[1][i] * l_e[1] + R[2][i] * l_e[2]) for i, y in enumerate(c)]
+    if f_e is not None:
+        d = [y - (R[0][i] * f_e[0] + R[1][i] * f_e[1] + R[2][i] * f_e[2]) for i, y in enumerate(d)]
     M = mp.matrix(6, 6)
     for i in range(3):
         for j in range(3):
@@ -240,14 +246,54 @@ def step_list(t_pts, dL):
     return out
 
 
-def model(fx_consts, C, D, state, v0, u0, steps, pattern=None):
-    """Truth of one state: dict(p [points][3], R (column-major 9, tip), L, Li) in mpmath.  steps: [(t, h, row)]."""
+def tip_balance(C, D, L, Kse, Kbt, tau, x, F_e, L_e):
+    """(e [6], terms [6]): the tip residual e = (n - F_t - F_e, m - L_t - L_e) by the rule of tip_residual()
+    (tests/loaded_fk_reference.py) in mpmath, from the integrated state x at s = L: n = R K_se (v - e3), m = R K_bt u,
+    F_t = sum -tau_i unit(R p_dot_i), L_t = sum (R r_i) x F_t,i.  The tendon directions are normalised AFTER the rotation into the
+    base frame, and R is the integrated frame, not re-orthonormalised -- as the reference and fk_loaded_uniform have it.
+    terms[k]: the largest magnitude among the terms summed into component k (the products of the two matrix-vector rows, every
+    tendon's force component or the two products of its moment, the wrench component): the floor of that component's bound.
+    No Newton-step site: the kernel forms the balance with IEEE sqrt and division and with contraction off."""
+    R, v, u = x["R"], x["v"], x["u"]
+    Kv = [Kse[0] * v[0], Kse[1] * v[1], Kse[2] * (v[2] - 1)]
+    Ku = [Kbt[i] * u[i] for i in range(3)]
+    e, terms = [], []
+    for r in range(3):
+        prods = [R[r][q] * Kv[q] for q in range(3)]
+        e.append(prods[0] + prods[1] + prods[2] - F_e[r])
+        terms.append(max([abs(y) for y in prods] + [abs(F_e[r])]))
+    for r in range(3):
+        prods = [R[r][q] * Ku[q] for q in range(3)]
+        e.append(prods[0] + prods[1] + prods[2] - L_e[r])
+        terms.append(max([abs(y) for y in prods] + [abs(L_e[r])]))
+    for (rr, rd, _), ta in zip(routing(C, D, L), tau):
+        pd = _mv(R, _add(_add(_cross(u, rr), rd), v))
+        nrm = mp.sqrt(pd[0] * pd[0] + pd[1] * pd[1] + pd[2] * pd[2])
+        Ft = [-ta * y / nrm for y in pd]
+        rw = _mv(R, rr)
+        for r in range(3):
+            a, b = rw[(r + 1) % 3] * Ft[(r + 2) % 3], rw[(r + 2) % 3] * Ft[(r + 1) % 3]
+            e[r] -= Ft[r]
+            e[3 + r] -= a - b
+            terms[r] = max(terms[r], abs(Ft[r]))
+            terms[3 + r] = max(terms[3 + r], abs(a), abs(b))
+    return e, terms
+
+
+def model(fx_consts, C, D, state, v0, u0, steps, pattern=None, f_e=None, l_e=None, wrench=None):
+    """Truth of one state: dict(p [points][3], R (column-major 9, tip), L, Li, v, u) in mpmath.  steps: [(t, h, row)].
+    v, u: the tip strains (body frame: the rotation does not touch them).  f_e, l_e: the distributed load, three numbers each,
+    constant over the rod, in the base frame before the state's rotation (deriv); None: the unloaded arithmetic, unchanged.
+    wrench: (F_e, L_e), six numbers in the same frame; given, the result also holds e [6] and e_terms [6] (tip_balance), formed
+    before the rotation like v and u."""
     Lr, dL, ro, ri, E, nu, r, res, rot, ret = (float(x) for x in fx_consts)
     N = len(C)
     trig = TrigSigns(pattern) if pattern is not None and pattern[0].startswith("trig") else None
     signs = Signs(pattern) if pattern is not None and trig is None else None
     Kse, Kbt = stiffness(ro, ri, E, nu)
     tau = [mp.mpf(float(s)) for s in state[:N]]
+    f_e = None if f_e is None else [mp.mpf(float(y)) for y in f_e]
+    l_e = None if l_e is None else [mp.mpf(float(y)) for y in l_e]
     x = dict(p=[ZERO] * 3, R=[[ONE, ZERO, ZERO], [ZERO, ONE, ZERO], [ZERO, ZERO, ONE]], v=[mp.mpf(float(s)) for s in v0],
              u=[mp.mpf(float(s)) for s in u0], L=ZERO, Li=[ZERO] * N)
     pts = [list(x["p"])]
@@ -270,21 +316,26 @@ def model(fx_consts, C, D, state, v0, u0, steps, pattern=None):
         else:
             rt = rt_plain
         own = own and row < 0
-        k1 = deriv(rt(t), Kse, Kbt, tau, x, signs)
-        k2 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k1), signs)
-        k3 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k2), signs)
-        k4 = deriv(rt(te), Kse, Kbt, tau, _axpy(x, hm, k3), signs)
+        k1 = deriv(rt(t), Kse, Kbt, tau, x, signs, f_e, l_e)
+        k2 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k1), signs, f_e, l_e)
+        k3 = deriv(rt(tm), Kse, Kbt, tau, _axpy(x, hm / 2, k2), signs, f_e, l_e)
+        k4 = deriv(rt(te), Kse, Kbt, tau, _axpy(x, hm, k3), signs, f_e, l_e)
         x = _axpy(_axpy(_axpy(_axpy(x, hm / 6, k1), hm / 3, k2), hm / 3, k3), hm / 6, k4)
         if row >= 0:
             assert row == len(pts)
             pts.append(list(x["p"]))
     Rm = x["R"]
+    out = dict(v=list(x["v"]), u=list(x["u"]))
+    if wrench is not None:
+        w = [mp.mpf(float(y)) for y in wrench]
+        out["e"], out["e_terms"] = tip_balance(C, D, Lr, Kse, Kbt, tau, x, w[:3], w[3:])
     if rot:
         th = mp.mpf(float(state[N]))
         Rz = [[mp.cos(th), -mp.sin(th), ZERO], [mp.sin(th), mp.cos(th), ZERO], [ZERO, ZERO, ONE]]
         pts = [_mv(Rz, q) for q in pts]
         Rm = _mm(Rz, Rm)
-    return dict(p=pts, R=[Rm[rr][cc] for cc in range(3) for rr in range(3)], L=x["L"], Li=x["Li"])
+    out.update(p=pts, R=[Rm[rr][cc] for cc in range(3) for rr in range(3)], L=x["L"], Li=x["Li"])
+    return out
 
 
 def home_truth(fx_consts, C, D, s_start, t_pts):

@@ -1,10 +1,14 @@
 """Writes tests/golden/loaded_fk_<name>.npz: loaded shapes of the fixture robots by the numpy reference (tests/loaded_fk_reference.py).
 
-Robots and their 24 states are make_fk_truth's (fixture_robot / fixture_states).  Three load cases per fixture, loads in the robot's
+Robots and their 24 states are make_fk_truth's (fixture_robot / fixture_states).  Four load cases per fixture, loads in the robot's
 base frame before the state's rotation:
   A  one wrench for all: F_e = (0.05, -0.03, 0.02) N, L_e = (1e-3, -2e-3, 5e-4) N m
   B  gravity per state: f_e = Rz(-theta) (0, -2.4525, 0) N/m (a 50 g robot of 0.2 m), no wrench
   C  B plus a seeded wrench per state, |F| <= 0.1 N, |L| <= 2e-3 N m
+  D  C plus a seeded distributed load of its own per state: a force of any direction with 0.3 <= |f| <= 1.0 N/m added to the gravity
+     row, and a distributed moment l_e of any direction with 0.003 <= |l| <= 0.01 N (a generator of its own, seeded by the robot's
+     position in NAMES).  The only case with a moment per unit length and with a z component in f_e: all twelve numbers of a row are
+     non-zero, and the lower limits keep every state's moment large enough to see (tests/test_loaded_fk_truth.py)
 Per state and case: the loads, the reference's (v0, u0), points, tip frame, L, L_i, |e_ref|, and
   C_i     the largest 2-norm over the backbone points of dp/d(v0, u0) J^-1 in m/N (from the last Jacobian's integrations)
   bound_i 1e-9 m + 1.5 C_i (residual_threshold + |e_ref,i|): the first-order displacement of a solution whose wrench misses by the
@@ -31,7 +35,7 @@ import loaded_fk_reference as ref                                    # noqa: E40
 import make_fk_truth as mft                                          # noqa: E402
 
 NAMES = ("config1", "n1", "n8", "config3_rot", "n5", "n6")          # new names go last: case C is seeded by position
-CASES = ("A", "B", "C")
+CASES = ("A", "B", "C", "D")
 WRENCH_A = np.array([0.05, -0.03, 0.02, 1e-3, -2e-3, 5e-4])
 GRAVITY = np.array([0.0, -2.4525, 0.0])
 GRID_N, GRID_HALF, SPHERE_VOXELS, CLEAR_VOXELS = 256, 0.3, 3, 2
@@ -59,11 +63,16 @@ def loads(name, robot, st, case):
     c, s = np.cos(-theta), np.sin(-theta)
     dist[:, 0] = c * GRAVITY[0] - s * GRAVITY[1]
     dist[:, 1] = s * GRAVITY[0] + c * GRAVITY[1]
-    if case == "C":
+    if case in ("C", "D"):
         rng = np.random.default_rng(9000 + NAMES.index(name))
         for col, cap in ((0, 0.1), (3, 2e-3)):
             d = rng.normal(size=(n, 3))
             wrench[:, col:col + 3] = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.0, cap, (n, 1))
+    if case == "D":
+        rng = np.random.default_rng(9500 + NAMES.index(name))
+        for col, lo, hi in ((0, 0.3, 1.0), (3, 0.003, 0.01)):
+            d = rng.normal(size=(n, 3))
+            dist[:, col:col + 3] += d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(lo, hi, (n, 1))
     return wrench, dist
 
 

@@ -4,6 +4,10 @@ import numpy as np
 
 WRENCH = np.array([0.05, -0.03, 0.02, 0.0, 0.0, 0.0])
 DIST = np.array([0.0, -2.4525, 0.0, 0.0, 0.0, 0.0])
+# all twelve numbers non-zero: case A's wrench (make_loaded_fk.py) and a row of case D's size -- gravity plus a force of 0.76 N/m with a
+# z component, and a distributed moment of 7.8e-3 N
+WRENCH_FULL = np.array([0.05, -0.03, 0.02, 1e-3, -2e-3, 5e-4])
+DIST_FULL = np.array([0.45, -2.1025, 0.5, 4e-3, -6e-3, 3e-3])
 HALF = 0.3
 #        edges, seed of the edges, tension cap of the start states, seed and count of the spheres, their radius
 FIXTURES = {"config1": (32, 3, 12.0, 5, 40, 0.03), "config3_rot": (32, 3, 18.0, 7, 24, 0.02), "n8": (8, 4, 4.0, 9, 40, 0.03)}

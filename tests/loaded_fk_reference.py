@@ -225,7 +225,7 @@ def shoot(rob, states, F_e=None, L_e=None, f_e=None, l_e=None, guess=None, tol=1
 
 
 def evaluate(rob, states, vu0, F_e=None, L_e=None, f_e=None, l_e=None):
-    """One integration per state from given base strains: dict(p, R after rotate_z, L, L_i, e (n, 6))."""
+    """One integration per state from given base strains: dict(p, R after rotate_z, L, L_i, e (n, 6), vuL (n, 6) the tip strains)."""
     st = np.atleast_2d(np.asarray(states, float))
     n, N = st.shape[0], rob.n_tendons
     tau = np.ascontiguousarray(st[:, :N])
@@ -235,4 +235,4 @@ def evaluate(rob, states, vu0, F_e=None, L_e=None, f_e=None, l_e=None):
     sh = integrate(rob, tau, np.asarray(vu0, float).reshape(n, 6), rows(f_e), rows(l_e), routing)
     e = tip_residual(rob, tau, sh, rows(F_e), rows(L_e), routing)
     p, R = rotate_z(sh["p"], sh["R"], theta)
-    return dict(p=p, R=R, L=sh["L"], L_i=sh["L_i"], e=e)
+    return dict(p=p, R=R, L=sh["L"], L_i=sh["L_i"], e=e, vuL=np.concatenate([sh["v"], sh["u"]], axis=1))

@@ -62,6 +62,22 @@ def offset_starts(rob, states, sigma_tension, sigma_rotation=0.0, seed=5):
     return np.clip(st + off, lo, hi)
 
 
+# One distributed row with all six numbers non-zero (tests/loaded_edges_common.py: DIST_FULL, gravity plus a force of case D's size
+# with a z component, and a distributed moment) on config1, sigma = 3 N: the set `config1_full` of tests/test_gpu_loaded_ik.py -- the
+# one that runs fk_loaded_lin's load.l.  No fixture holds shapes under that row, so the goals are the numpy shooting's tips under it
+# (loaded_tips), as the other sets' goals are the fixtures' tips under their loads.  This scheme reaches 24 of 24 in at most 6 outer
+# iterations (measured when the set was added; tests/test_loaded_ik_reference.py holds it to that).
+FULL_REACHED = 24
+
+
+def loaded_tips(rob, states, wrench=None, dist=None):
+    """(n, 3) tips of the loaded shapes of `states` under one BASE-frame load set, by the numpy shooting from the unloaded start."""
+    w, d = (np.zeros(6) if a is None else np.asarray(a, float) for a in (wrench, dist))
+    sol = ref.shoot(rob, states, F_e=w[:3], L_e=w[3:], f_e=d[:3], l_e=d[3:])
+    assert sol["converged"].all()
+    return np.ascontiguousarray(sol["p"][:, -1])
+
+
 def load_rows(rob, states, wrench=None, dist=None, frame="base"):
     """(n, 6) wrench and distributed-load rows of the states, in the frame before the state's rotation."""
     st = np.atleast_2d(np.asarray(states, float))

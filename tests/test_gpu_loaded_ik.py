@@ -1,7 +1,8 @@
 """Tip IK on loaded shapes on the device (tr_ik_loaded_batch*, csrc/loaded_ik_host.inc) against the numpy restatements
 (tests/loaded_ik_reference.py, tests/loaded_fk_reference.py) and the loaded-FK fixtures (tests/golden/loaded_fk_<name>.npz).
 
-Goals are the fixtures' loaded tips, starts the fixture states plus seeded normal offsets (loaded_ik_reference.offset_starts, seed 5).
+Goals are the fixtures' loaded tips (config1_full: the numpy shooting's tips under its own row, which no fixture holds), starts the
+fixture states plus seeded normal offsets (loaded_ik_reference.offset_starts, seed 5).
 The ABI takes one load set per call: cases whose rows differ per state (case C's wrenches, config3_rot's rows in the BASE frame) are
 solved one problem per call.
 
@@ -22,6 +23,7 @@ for _p in (HERE, os.path.join(HERE, "golden")):
 
 import loaded_fk_reference as ref                                    # noqa: E402
 import loaded_ik_reference as ikr                                    # noqa: E402
+from loaded_edges_common import DIST_FULL                            # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +34,9 @@ KEYS = ("state", "tip", "error", "iters", "num_fk_calls", "vu0", "equilibrium")
 PROBLEMS = {"config1_B": ("config1", "B", "base", 3.0, 0.0),
             "config1_C": ("config1", "C", "base", 3.0, 0.0),
             "n1_B": ("n1", "B", "world", 1.5, 0.3),
+            # one distributed row with a z component and a moment per unit length (loaded_edges_common.DIST_FULL): load.l of
+            # fk_loaded_lin; goals are the numpy shooting's tips under that row (loaded_ik_reference.loaded_tips)
+            "config1_full": ("config1", "full", "base", 3.0, 0.0),
             "config3_rot_base": ("config3_rot", "B", "base", 0.5, 0.1),
             "config3_rot_world": ("config3_rot", "B", "world", 0.5, 0.1),
             # S = 6, 7, 9: fk_loaded_lin<5>, <6>, <8> and ikl_lm_step<6>, <7>, <9> (from <5> on the forms that need AGPRs)
@@ -91,8 +96,10 @@ def solved(world):
         name, case, frame, s_tau, s_rot = PROBLEMS[key]
         robot, rob, fx, eng = world(name)
         starts = ikr.offset_starts(rob, fx["states"], s_tau, s_rot)
-        goals = np.ascontiguousarray(fx["p_" + case][:, -1])
-        if frame == "world":
+        goals = ikr.loaded_tips(rob, fx["states"], dist=DIST_FULL) if case == "full" else np.ascontiguousarray(fx["p_" + case][:, -1])
+        if case == "full":
+            wrench, dist = None, DIST_FULL
+        elif frame == "world":
             wrench, dist = None, GRAVITY
         else:
             wrench, dist = fx["wrench_" + case], fx["dist_" + case]
@@ -116,7 +123,7 @@ def _same(a, b, rows_a=slice(None), rows_b=slice(None)):
         assert np.array_equal(a[k][rows_a], b[k][rows_b], equal_nan=True), k
 
 
-@pytest.mark.parametrize("key", ["config1_B", "config1_C", "n1_B"])
+@pytest.mark.parametrize("key", ["config1_B", "config1_C", "n1_B", "config1_full"])
 def test_it_is_a_solution(world, solved, key):
     robot, rob, fx, eng = world(PROBLEMS[key][0])
     s = solved(key)

@@ -62,6 +62,29 @@ def test_it_reaches_the_loaded_tips(gen, name, case, sigma_tension, sigma_rotati
     assert np.abs(x - out["tip"]).max() <= 1e-9
 
 
+def test_it_reaches_the_tips_under_a_full_distributed_row(gen):
+    """config1 under one distributed row with a z component and a moment per unit length (the set config1_full of
+    tests/test_gpu_loaded_ik.py): goals are the numpy shooting's tips under that row, and the scheme reaches FULL_REACHED = 24 of 24,
+    every row an equilibrium whose tip is the returned one."""
+    from loaded_edges_common import DIST_FULL
+    rob, st, fx, _ = _case(gen, "config1", "B")
+    assert DIST_FULL.all()
+    goals = ikr.loaded_tips(rob, st, dist=DIST_FULL)
+    moved = np.linalg.norm(goals - fx["p_B"][:, -1], axis=1)
+    starts = ikr.offset_starts(rob, st, 3.0, 0.0)
+    out = ikr.inverse_kinematics_loaded_batch(rob, starts, goals, max_iters=10, dist=DIST_FULL)
+    reached = out["error"] <= 1e-4
+    print("config1 under the full row: reached %d of 24, outer iterations <= %d; the row moves the tips of case B by %.3g .. %.3g m"
+          % (reached.sum(), out["iters"].max(), moved.min(), moved.max()))
+    assert out["equilibrium"].all()
+    assert reached.sum() == ikr.FULL_REACHED == 24
+    assert moved.min() > 10 * 1e-4                                       # the row matters at the stop threshold
+    w, d = ikr.load_rows(rob, out["state"], None, DIST_FULL)
+    x, e = ikr.tips_and_residuals(rob, out["state"], out["vu0"], w, d)
+    assert (np.linalg.norm(e, axis=1) <= rob.c.residual_threshold).all()
+    assert np.abs(x - out["tip"]).max() <= 1e-9
+
+
 @pytest.mark.parametrize("name", ["n5", "n6", "n8"])
 def test_it_reaches_the_loaded_tips_at_wider_state_sizes(gen, name):
     """S = 6, 7, 9 under gravity in the world frame at 25 outer iterations: at least 21 of 24 reached (measured: 24, 22, 21; rows
