@@ -515,6 +515,41 @@ int tr_ik_loaded_batch_dev(tr_ctx *ctx, const tr_ik_params *params, const tr_sho
                            int32_t *d_iters_out, int32_t *d_fk_calls_out, double *d_vu0_out, uint8_t *d_equilibrium_out,
                            int64_t *rounds_out, void *stream);
 
+/* ---- tip Jacobian and tip compliance of loaded shapes ------------------------------------- */
+
+/* tr_tip_jacobian for LOADED shapes: the linearisation the loaded IK forms in every round of its loop, for n states in one call.
+ * It replaces differencing tr_fk_loaded_batch through 2 S + 1 shooting solves per state (each with its own stopping noise) by one
+ * solve and 13 + 2 S integrations.  Every state is equilibrated by tr_fk_loaded_batch's shooting (`shoot`, NULL: its defaults;
+ * `guess`: optional n x 6 start strains, NULL: the unloaded solution) under ONE load set per call (`loads`, tr_edge_loads' meaning
+ * of BASE and WORLD; NULL: no load; warm_start is not read).  With max_iters = 0 and a guess the state is linearised exactly at
+ * the guess: one integration, equilibrium = (residual <= residual_threshold) as tr_fk_loaded_batch defines it.
+ * At base strains y with e_w(y, p) = balance(y, p) - w = 0 and the blocks J_y = de_w/dy, J_p = de_w/dp, X_y = dx/dy, X_p = dx/dp
+ * (central differences; the state's steps are levmar's max(|1e-4 p_k|, delta), the strains' the shooting's
+ * finite_difference_delta itself):
+ *   W = J_y^-1 J_p                  n x 6 x S   (-W = dy/dp: the loaded IK's strain predictor)
+ *   J = X_p - X_y W                 n x 3 x S   dx/dp, the tip Jacobian of the loaded shape -- bit for bit the loaded IK's
+ *   compliance = X_y J_y^-1 T       n x 3 x 6   dx/dw: tip displacement per unit tip force and moment, with respect to the wrench AS
+ *                                               GIVEN: T = I (BASE), blockdiag(Rz(-theta), Rz(-theta)) (WORLD on a robot with rotation)
+ *   vu0 = y - J_y^-1 e_w            n x 6       the strains after one Newton step (the shooting stops at the threshold)
+ *   tips = x - X_y J_y^-1 e_w       n x 3       the tip there
+ *   equilibrium                     n           the shooting converged (and J_y has no zero pivot)
+ *   blocks                          n x (69 + 9 S), row-major each: y(6), x(3), e_w(6), J_y(36), J_p(6 S), X_y(18), X_p(3 S) --
+ *                                               what the results above were reduced from
+ *   n_integrations                  n           the shooting's integrations and the 13 + 2 S lanes
+ *   rounds_out                      one int64: shooting rounds (one host synchronisation each)
+ * All outputs are optional.  A state whose shooting does not converge has equilibrium = 0 and NaN in every double output: never
+ * an error of the call.  A zero pivot of J_y leaves inf / NaN in what is solved with it.
+ * Robots with retraction: TR_ERR_UNSUPPORTED; a bad frame, delta <= 0 or null states: TR_ERR_INVALID_ARG; n == 0: TR_OK.  A
+ * problem's result does not depend on the batch size, the order, the chunking (TENDON_HIP_SHOOT_CHUNK) or the other problems. */
+int tr_tip_jacobian_loaded(tr_ctx *ctx, const tr_shoot_params *shoot, const tr_edge_loads *loads, const double *states, int64_t n,
+                           double delta, const double *guess, double *tips, double *J, double *compliance, double *W, double *vu0,
+                           uint8_t *equilibrium, double *blocks, int64_t *n_integrations, int64_t *rounds_out);
+/* ... with device arrays (rounds_out stays a host pointer); the run is ordered on `stream` and ends synchronised. */
+int tr_tip_jacobian_loaded_dev(tr_ctx *ctx, const tr_shoot_params *shoot, const tr_edge_loads *loads, const double *d_states,
+                               int64_t n, double delta, const double *d_guess, double *d_tips, double *d_J, double *d_compliance,
+                               double *d_W, double *d_vu0, uint8_t *d_equilibrium, double *d_blocks, int64_t *d_n_integrations,
+                               int64_t *rounds_out, void *stream);
+
 /* ---- cached voxel sets vs obstacles: VoxelOctree::collides on roadmap caches ------------ */
 
 /* Batched `obstacles.collides(*cached_voxels)` for roadmap vertices / edges

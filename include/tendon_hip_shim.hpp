@@ -73,6 +73,21 @@ struct ShootOptions {
   double mu_init = 0.1, stop_threshold_JT_err_inf = 1e-9, stop_threshold_Dp = 1e-4, finite_difference_delta = 1e-6;
 };
 
+/// What tip_jacobian_loaded_batch returns: J n x 3 x S (d tip / d state), tips n x 3 and vu0 n x 6 (the tip and base strains
+/// one Newton step past the shooting's stop), compliance n x 3 x 6 (d tip / d (F_e, L_e), the wrench as given), equilibrium n,
+/// n_integrations n.  A state without an equilibrium has equilibrium = 0 and NaN in its rows.
+struct LoadedTipJacobian {
+  std::vector<double> J, tips, vu0, compliance;
+  std::vector<uint8_t> equilibrium;
+  std::vector<int64_t> n_integrations;
+};
+/// Arguments of tip_jacobian_loaded_batch after the loads: the shooting's, the state's difference step, the load's frame
+struct LoadedJacobianOptions {
+  ShootOptions shoot{};
+  double delta = 1e-6;
+  bool world = false;             // the load is fixed in the frame after the state's rotation (gravity), else before it
+};
+
 class TendonRobot {                 // tendon/TendonRobot.h:52-355
  public:
   double r = 0.015;
@@ -215,6 +230,34 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
         res.v_f[k] = vuL[6 * i + k]; res.u_f[k] = vuL[6 * i + 3 + k];
       }
     }
+    return out;
+  }
+
+  /// tip_jacobian_batch on the shapes of generalShapeBatch (tr_tip_jacobian_loaded): one shooting solve and 13 + 2 S integrations
+  /// per state.  `wrench` holds (F_e, L_e), `dist` (f_e, l_e) per unit length, 6 values each or empty (zero), ONE set per call;
+  /// `guess` holds n rows (v, u) or is empty.  rounds (optional): shooting rounds.
+  LoadedTipJacobian tip_jacobian_loaded_batch(const std::vector<double> &states, size_t n, const std::vector<double> &wrench,
+                                              const std::vector<double> &dist = {},
+                                              const LoadedJacobianOptions &opt = LoadedJacobianOptions(),
+                                              const std::vector<double> &guess = {}, int64_t *rounds = nullptr) const {
+    const size_t S = state_size();
+    if (states.size() != n * S) throw std::invalid_argument("State is not the right size");
+    if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6)) throw std::invalid_argument("loads: 6 values or none");
+    if (!guess.empty() && guess.size() != 6 * n) throw std::invalid_argument("guess: empty, or 6 per state");
+    tr_ctx *c = context();
+    const tr_shoot_params prm{opt.shoot.max_iters, opt.shoot.mu_init, opt.shoot.stop_threshold_JT_err_inf, opt.shoot.stop_threshold_Dp,
+                              opt.shoot.finite_difference_delta};
+    tr_edge_loads ld{};
+    for (size_t q = 0; q < wrench.size(); q++) ld.wrench[q] = wrench[q];
+    for (size_t q = 0; q < dist.size(); q++) ld.dist[q] = dist[q];
+    ld.frame = opt.world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
+    LoadedTipJacobian out;
+    out.J.resize(n * 3 * S); out.tips.resize(n * 3); out.vu0.resize(n * 6); out.compliance.resize(n * 18);
+    out.equilibrium.resize(n); out.n_integrations.resize(n);
+    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error)
+    check(c, tr_tip_jacobian_loaded(c, &prm, (wrench.empty() && dist.empty()) ? nullptr : &ld, states.data(), (int64_t)n, opt.delta,
+                                    guess.empty() ? nullptr : guess.data(), out.tips.data(), out.J.data(), out.compliance.data(), nullptr,
+                                    out.vu0.data(), out.equilibrium.data(), nullptr, out.n_integrations.data(), rounds));
     return out;
   }
 
@@ -403,6 +446,53 @@ inline LoadedIKResult inverseKinematicsLoaded(const tendon::TendonRobot &robot, 
                                               const std::vector<double> &dist, const LoadedIKOptions &opt = LoadedIKOptions()) {
   if (initial_state.size() != robot.state_size()) throw std::invalid_argument("State is not the right size");
   return inverseKinematicsLoadedBatch(robot, initial_state, 1, {des}, wrench, dist, opt)[0];
+}
+
+/// tip_control::damped_resolved_rate_update (tip_control.cpp:418-483) without the FKFunc: the next state for the tip displacement
+/// v_times_dt.  The reference runs ONE Levenberg-Marquardt iteration towards fk(q) + v_times_dt with mu_init = lambda, all three
+/// stop thresholds at 1e-9 and Bounds::from_robot centred on q; here that is the tip through tip_control's wrapper followed by
+/// tr_ik_batch with max_iters = 1.  A step that LM rejects leaves the state where it is.  `verbose` is accepted and ignored.
+inline std::vector<double> damped_resolved_rate_update(const tendon::TendonRobot &robot, const std::vector<double> &current_state,
+                                                       const std::array<double, 3> &v_times_dt, double lambda = 0.1,
+                                                       double finite_difference_delta = 1e-6, bool verbose = false) {
+  (void)verbose;
+  const size_t S = robot.state_size();
+  if (current_state.size() != S) throw std::invalid_argument("State is not the right size");
+  tr_ctx *c = robot.context();
+  std::array<double, 3> tip{};
+  if (robot.enable_retraction && current_state[S - 1] > robot.specs.L) {
+    tip = {0.0, 0.0, robot.specs.L - current_state[S - 1]};           // tip_control.cpp:96-104
+  } else {
+    check(c, tr_fk_tips(c, current_state.data(), 1, tip.data(), nullptr));
+  }
+  const std::array<double, 3> des{tip[0] + v_times_dt[0], tip[1] + v_times_dt[1], tip[2] + v_times_dt[2]};
+  return inverse_kinematics_batch(robot, current_state, 1, {des}, 1, lambda, 1e-9, 1e-9, 1e-9, finite_difference_delta)[0].state;
+}
+
+/// ... on the LOADED shape: the loaded tip and its strains from tr_tip_jacobian_loaded (one shooting solve), then tr_ik_loaded_batch
+/// with max_iters = 1 from those strains.  opt.max_iters, mu_init and the stop thresholds are not read; opt.world is.
+inline std::vector<double> damped_resolved_rate_updateLoaded(const tendon::TendonRobot &robot, const std::vector<double> &current_state,
+                                                             const std::array<double, 3> &v_times_dt, const std::vector<double> &wrench,
+                                                             const std::vector<double> &dist, double lambda = 0.1,
+                                                             double finite_difference_delta = 1e-6,
+                                                             const LoadedIKOptions &opt = LoadedIKOptions()) {
+  const size_t S = robot.state_size();
+  if (current_state.size() != S) throw std::invalid_argument("State is not the right size");
+  tendon::LoadedJacobianOptions jo;
+  jo.delta = finite_difference_delta; jo.world = opt.world;
+  const auto at = robot.tip_jacobian_loaded_batch(current_state, 1, wrench, dist, jo);
+  if (!at.equilibrium[0]) return current_state;
+  tr_ctx *c = robot.context();
+  const tr_ik_params prm{1, lambda, 1e-9, 1e-9, 1e-9, finite_difference_delta};
+  tr_edge_loads ld{};
+  for (size_t q = 0; q < wrench.size(); q++) ld.wrench[q] = wrench[q];
+  for (size_t q = 0; q < dist.size(); q++) ld.dist[q] = dist[q];
+  ld.frame = opt.world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
+  const double des[3] = {at.tips[0] + v_times_dt[0], at.tips[1] + v_times_dt[1], at.tips[2] + v_times_dt[2]};
+  std::vector<double> next(S);
+  check(c, tr_ik_loaded_batch(c, &prm, nullptr, (wrench.empty() && dist.empty()) ? nullptr : &ld, current_state.data(), 1, des, 0, nullptr,
+                              nullptr, at.vu0.data(), next.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  return next;
 }
 
 }  // namespace tip_control

@@ -44,6 +44,7 @@ ABI_SYMBOLS = (
     "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
     "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
     "tr_ik_loaded_batch", "tr_ik_loaded_batch_dev",
+    "tr_tip_jacobian_loaded", "tr_tip_jacobian_loaded_dev",
 )
 
 
@@ -371,6 +372,8 @@ def lib():
     L.tr_connect_edges_loaded_indexed.argtypes = L.tr_voxelize_edges_loaded_indexed.argtypes
     L.tr_ik_loaded_batch.argtypes = [vp, P(TrIkParams), shp, elp, dp, i64, dp, i64, dp, dp, dp, dp, dp, dp, i32p, i32p, dp, P(C.c_uint8), P(i64)]
     L.tr_ik_loaded_batch_dev.argtypes = [vp, P(TrIkParams), shp, elp, vp, i64, vp, i64, dp, dp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
+    L.tr_tip_jacobian_loaded.argtypes = [vp, shp, elp, dp, i64, C.c_double, dp, dp, dp, dp, dp, dp, P(C.c_uint8), dp, P(i64), P(i64)]
+    L.tr_tip_jacobian_loaded_dev.argtypes = [vp, shp, elp, vp, i64, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     tqp = P(TrTipQueryParams)
     L.tr_roadmap_set_tips.argtypes = [vp, dp, P(u64)]
     L.tr_roadmap_nearest_tips.argtypes = [vp, dp, i64, C.c_int32, i32p, dp]

@@ -14,7 +14,8 @@ int64_t ikl_chunk(const tr_ctx *c) { return std::min<int64_t>(shoot_chunk_size(c
 void ikl_release(tr_ctx *c) {
   tr_ctx::IklDev &k = c->ikl;
   void *p[] = {k.lin, k.p, k.pn, k.y, k.W, k.J, k.f, k.des, k.err2, k.mu, k.nu, k.iters, k.calls, k.list[0], k.list[1], k.eq, k.row_s, k.row_w,
-               k.row_d, k.row_g, k.row_vu, k.row_conv, k.row_calls, k.d_count, k.io_s, k.io_3, k.io_g, k.io_e, k.io_vu, k.io_i, k.io_c, k.io_eq};
+               k.row_d, k.row_g, k.row_vu, k.row_conv, k.row_calls, k.d_count, k.io_s, k.io_3, k.io_g, k.io_e, k.io_vu, k.io_i, k.io_c, k.io_eq,
+               k.sens_c, k.sens_b, k.sens_n};
   for (void *q : p) if (q) (void)hipFree(q);
   if (k.h_count) (void)hipHostFree(k.h_count);
   k = tr_ctx::IklDev{};

@@ -47,6 +47,7 @@
 #include "loaded_edge_kernel.hpp"
 #include "loaded_roadmap_kernel.hpp"
 #include "loaded_ik_kernel.hpp"
+#include "loaded_sens_kernel.hpp"
 
 void tr_dev_cache_trim();          // roadmap.hip: frees the idle device buffers of the query objects' cache
 struct tr_ctx;
@@ -303,6 +304,11 @@ struct tr_ctx {
     double *io_s = nullptr, *io_3 = nullptr, *io_g = nullptr, *io_e = nullptr, *io_vu = nullptr;
     int32_t *io_i = nullptr, *io_c = nullptr;
     uint8_t *io_eq = nullptr;
+    // staging of tr_tip_jacobian_loaded's host-array form (loaded_jacobian_host.inc): compliance [sens_probs][18], blocks
+    // [sens_probs][69 + 9 S], integrations [sens_probs]
+    int64_t sens_probs = 0;
+    double *sens_c = nullptr, *sens_b = nullptr;
+    int64_t *sens_n = nullptr;
   } ikl;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
@@ -2273,3 +2279,4 @@ int tr_profile_end(tr_ctx *c) {
 #include "loaded_edges_host.inc"
 #include "loaded_roadmap_host.inc"
 #include "loaded_ik_host.inc"
+#include "loaded_jacobian_host.inc"

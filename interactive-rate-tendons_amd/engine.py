@@ -596,6 +596,84 @@ class Engine:
             opt(d_equilibrium_out, torch.uint8, n, "d_equilibrium_out"), rounds, self._stream_ptr(stream)))
         return int(rounds[0]), int(rounds[1])
 
+    # ---- tip Jacobian and tip compliance of loaded shapes (tr_tip_jacobian_loaded*, include/tendon_hip.h) -------------------------
+    _SENS_WANT = ("J", "tips", "vu0", "compliance", "W", "blocks")
+
+    def _sens_args(self, wrench, dist, frame, want, shoot):
+        if frame not in ("base", "world"):
+            raise L.InvalidArgument("frame must be 'base' or 'world'")
+        bad = set(want) - set(self._SENS_WANT)
+        if bad:
+            raise TypeError("unknown output(s): %s" % ", ".join(sorted(bad)))
+        bad = set(shoot) - set(self._SHOOT_DEFAULTS)
+        if bad:
+            raise TypeError("unknown shooting parameter(s): %s" % ", ".join(sorted(bad)))
+        ld = None if wrench is None and dist is None else self._edge_loads(wrench, dist, frame, False)
+        return ld, self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+
+    @staticmethod
+    def split_blocks(blocks, S):
+        """The named arrays of tr_tip_jacobian_loaded's `blocks` rows (n, 69 + 9 S): dict(y, x, e, J_y, J_p, X_y, X_p)."""
+        b = np.asarray(blocks)
+        n = b.shape[0]
+        cut = np.cumsum([0, 6, 3, 6, 36, 6 * S, 18, 3 * S])
+        part = lambda i, *shape: b[:, cut[i]:cut[i + 1]].reshape((n,) + shape)
+        return dict(y=part(0, 6), x=part(1, 3), e=part(2, 6), J_y=part(3, 6, 6), J_p=part(4, 6, S), X_y=part(5, 3, 6), X_p=part(6, 3, S))
+
+    def tip_jacobian_loaded(self, states, wrench=None, dist=None, frame="base", guess=None, delta=1e-6, want=("J",), **shoot):
+        """tip_jacobian for LOADED shapes (tr_tip_jacobian_loaded): every state is equilibrated under one load set, wrench =
+        (F_e, L_e) and dist = (f_e, l_e) of (6,) each (None: zero), frame 'base' or 'world' as in ik_loaded_batch, and linearised
+        there.  guess: optional (n, 6) start strains; **shoot: fk_loaded_batch's solver arguments (max_iters=0 with a guess:
+        linearise exactly at the guess).  Returns dict(J (n, 3, S) = dx/dp, tips, vu0, equilibrium, n_integrations (n,), rounds) and,
+        when named in `want`: compliance (n, 3, 6) = dx/dw, W (n, 6, S) = J_y^-1 J_p, blocks = dict(y, x, e, J_y, J_p, X_y, X_p).
+        A state without an equilibrium has equilibrium False and NaN in every array."""
+        st = self._states(states)
+        n, S = st.shape
+        g = None
+        if guess is not None:
+            g = _f64(guess)
+            if g.shape != (n, 6):
+                raise L.InvalidArgument("guess must be (n, 6)")
+        ld, sprm = self._sens_args(wrench, dist, frame, want, shoot)
+        J, tips, vu0 = np.empty((n, 3, S)), np.empty((n, 3)), np.empty((n, 6))
+        Cm = np.empty((n, 3, 6)) if "compliance" in want else None
+        W = np.empty((n, 6, S)) if "W" in want else None
+        blk = np.empty((n, 69 + 9 * S)) if "blocks" in want else None
+        eq, nint = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.int64)
+        rounds = C.c_int64(0)
+        opt = lambda a: _dp(a) if a is not None else None
+        L.check(self._ctx, self.lib.tr_tip_jacobian_loaded(
+            self._ctx, C.byref(sprm), C.byref(ld) if ld is not None else None, _dp(st), n, float(delta), opt(g), _dp(tips), _dp(J),
+            opt(Cm), opt(W), _dp(vu0), eq.ctypes.data_as(C.POINTER(C.c_uint8)), opt(blk), nint.ctypes.data_as(C.POINTER(C.c_int64)),
+            C.byref(rounds)))
+        out = dict(J=J, tips=tips, vu0=vu0, equilibrium=eq.astype(bool), n_integrations=nint, rounds=int(rounds.value))
+        if Cm is not None:
+            out["compliance"] = Cm
+        if W is not None:
+            out["W"] = W
+        if blk is not None:
+            out["blocks"] = self.split_blocks(blk, S)
+        return out
+
+    def tip_jacobian_loaded_dev(self, d_states, n, d_J=None, d_tips=None, d_compliance=None, d_W=None, d_vu0=None, d_equilibrium=None,
+                                d_blocks=None, d_n_integrations=None, d_guess=None, wrench=None, dist=None, frame="base", delta=1e-6,
+                                stream=None, **shoot):
+        """tr_tip_jacobian_loaded_dev: device tensors in and out, every output optional (d_n_integrations: int64); returns the
+        shooting rounds."""
+        torch = _torch()
+        S = self.state_size
+        f64 = torch.float64
+        opt = lambda t, dt, m, nm: self._check_dev(t, dt, m, nm) if t is not None else None
+        ld, sprm = self._sens_args(wrench, dist, frame, (), shoot)
+        rounds = C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_tip_jacobian_loaded_dev(
+            self._ctx, C.byref(sprm), C.byref(ld) if ld is not None else None, self._check_dev(d_states, f64, n * S, "d_states"), int(n),
+            float(delta), opt(d_guess, f64, 6 * n, "d_guess"), opt(d_tips, f64, 3 * n, "d_tips"), opt(d_J, f64, 3 * S * n, "d_J"),
+            opt(d_compliance, f64, 18 * n, "d_compliance"), opt(d_W, f64, 6 * S * n, "d_W"), opt(d_vu0, f64, 6 * n, "d_vu0"),
+            opt(d_equilibrium, torch.uint8, n, "d_equilibrium"), opt(d_blocks, f64, (69 + 9 * S) * n, "d_blocks"),
+            opt(d_n_integrations, torch.int64, n, "d_n_integrations"), C.byref(rounds), self._stream_ptr(stream)))
+        return int(rounds.value)
+
     # ---- the roadmap build on loaded shapes (tr_sample_valid_vertices_loaded .. tr_connect_edges_loaded_indexed, include/tendon_hip.h) ----
     _SHOOT_DEFAULTS = dict(max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6)
 

@@ -194,6 +194,23 @@ class TendonRobot:
 
         return self.engine(device).fk_loaded_batch(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), guess=guess, want_R=want_R, **shoot)
 
+    def tip_jacobian_loaded_batch(self, states, f_e=None, l_e=None, F_e=None, L_e=None, frame="base", guess=None, delta=1e-6,
+                                  want=("J",), device=0, **shoot):
+        """tip_jacobian_batch on the shapes of general_shape_batch: d tip / d state (n, 3, S) of the LOADED tips and, on request,
+        the tip compliance d tip / d (F_e, L_e) (n, 3, 6), from one shooting solve and 13 + 2 S integrations per state.  Loads
+        in general_shape_batch's order, (3,) each: one set per call (frame='world': fixed behind the state's rotation).  Returns
+        Engine.tip_jacobian_loaded's dict."""
+        st = np.atleast_2d(np.asarray(states, dtype=np.float64))
+
+        def pair(a, b):
+            if a is None and b is None:
+                return None
+            z = np.zeros(3)
+            return np.concatenate([np.asarray(z if a is None else a, float).reshape(3), np.asarray(z if b is None else b, float).reshape(3)])
+
+        return self.engine(device).tip_jacobian_loaded(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), frame=frame, guess=guess,
+                                                       delta=delta, want=want, **shoot)
+
     def _stiffness(self):
         s = self.specs
         I = 0.25 * np.pi * (s.ro ** 4 - s.ri ** 4)

@@ -227,6 +227,47 @@ def inverse_kinematics_loaded_device(robot, initial_state, des, wrench=None, dis
     return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
 
 
+def tip_compliance_loaded(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, **shoot):
+    """How far the loaded tip gives way under a push: d tip / d (F_e, L_e) (n, 3, 6) in m/N and m/(N m) at the equilibria of
+    `states` under the load, with respect to the wrench as given (frame 'world': a wrench fixed behind rotate_z)
+    (tr_tip_jacobian_loaded).  Returns dict(compliance, tips, vu0, equilibrium); a state without an equilibrium has NaN rows."""
+    r = robot.engine(device).tip_jacobian_loaded(states, wrench=wrench, dist=dist, frame=frame, guess=guess, want=("compliance",), **shoot)
+    return dict(compliance=r["compliance"], tips=r["tips"], vu0=r["vu0"], equilibrium=r["equilibrium"])
+
+
+def damped_resolved_rate_update_batch_device(robot, states, v_times_dt, lam=0.1, finite_difference_delta=1e-6, wrench=None, dist=None,
+                                             frame="base", device=0):
+    """tip_control::damped_resolved_rate_update (tip_control.cpp:418-483) for a batch: the next state of every row of `states` for
+    the tip displacement v_times_dt ((3,) or one row per state).  The reference runs ONE Levenberg-Marquardt iteration towards
+    fk(q) + v_times_dt with mu_init = lambda, all three stop thresholds at 1e-9 and Bounds.from_robot centred on q; here that is
+    the tips (through tip_control's FK wrapper) followed by ik_batch with max_iters = 1 -- with wrench / dist given, fk_loaded_batch's tips followed by
+    ik_loaded_batch with max_iters = 1 (one load set per call).  A step that LM rejects leaves the state where it is."""
+    p = np.asarray(states, dtype=np.float64)
+    if p.ndim == 1:
+        p = p.reshape(1, -1)
+    if p.shape[1] != robot.state_size():
+        raise L.InvalidArgument("State is not the right size")
+    p = np.ascontiguousarray(p)
+    v = np.broadcast_to(np.asarray(v_times_dt, dtype=np.float64), (p.shape[0], 3))
+    lm = dict(max_iters=1, mu_init=lam, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-9, stop_threshold_err=1e-9,
+              finite_difference_delta=finite_difference_delta)
+    eng = robot.engine(device)
+    if wrench is None and dist is None:
+        tips = _tips(robot, p, device)
+        return eng.ik_batch(p, np.ascontiguousarray(tips + v), **lm)["state"]
+    w, d = eng.sample_loads(p, wrench, dist, frame)                      # every state's rows (a world-frame set: turned by its rotation)
+    out = eng.fk_loaded_batch(p, wrench=w, dist=d)
+    tips = out["p"][np.arange(len(p)), out["n_points"] - 1]
+    return eng.ik_loaded_batch(p, np.ascontiguousarray(tips + v), wrench=wrench, dist=dist, frame=frame, guess=out["vu0"], **lm)["state"]
+
+
+def damped_resolved_rate_update_device(robot, state, v_times_dt, lam=0.1, finite_difference_delta=1e-6, wrench=None, dist=None,
+                                       frame="base", device=0):
+    """damped_resolved_rate_update_batch_device for one state: the next state (S,)."""
+    return damped_resolved_rate_update_batch_device(robot, np.asarray(state, float).reshape(1, -1), v_times_dt, lam,
+                                                    finite_difference_delta, wrench, dist, frame, device)[0]
+
+
 def roadmap_ik(robot, goal_tip, vertex_states, vertex_tips, k=10, tolerance=1e-4, **lm):
     """The IK leg of VoxelCachedLazyPRM::roadmapIk (:3164-3205): start from the k roadmap vertices whose tips are
     nearest to the goal, all k solves in the same launches; returns the batch result sorted by error plus the
