@@ -13,10 +13,7 @@ int64_t ik_chunk(const tr_ctx *c) { return kIkLanes / (2 * c->K.state_size + 1);
 
 void ik_release(tr_ctx *c) {
   tr_ctx::IkDev &k = c->ik;
-  void *p[] = {k.xs, k.tips, k.p, k.pn, k.f, k.J, k.des, k.err2, k.mu, k.nu, k.iters, k.calls, k.list[0], k.list[1], k.d_count,
-               k.io_s, k.io_3, k.io_e, k.io_i, k.io_c};
-  for (void *q : p) if (q) (void)hipFree(q);
-  if (k.h_count) (void)hipHostFree(k.h_count);
+  k.chunk.release(); k.once.release(); k.count.release();
   k = tr_ctx::IkDev{};
 }
 
@@ -26,33 +23,49 @@ int ik_reserve(tr_ctx *c, int64_t n) {
   const int64_t S = c->K.state_size, Q = 2 * S + 1;
   const int64_t probs = round_up(std::max<int64_t>(1, std::min(n, ik_chunk(c))), 64), lanes = round_up(probs * Q, 64);
   int rc;
-  if (!k.d_count) {
-    if ((rc = dev_alloc(c, &k.d_count, 2))) return rc;
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_count, sizeof(uint32_t), hipHostMallocDefault));
-  }
+  if ((rc = k.count.reserve(c, k.once))) return rc;
   if (k.probs >= probs) return TR_OK;
   HIP_TRY(c, hipDeviceSynchronize());
-  if ((rc = dev_alloc(c, &k.xs, (size_t)(lanes * S)))) return rc;
-  if ((rc = dev_alloc(c, &k.tips, (size_t)(lanes * 3)))) return rc;
-  if ((rc = dev_alloc(c, &k.p, (size_t)(probs * S)))) return rc;
-  if ((rc = dev_alloc(c, &k.pn, (size_t)(probs * S)))) return rc;
-  if ((rc = dev_alloc(c, &k.f, (size_t)(probs * 3)))) return rc;
-  if ((rc = dev_alloc(c, &k.J, (size_t)(probs * 3 * S)))) return rc;
-  if ((rc = dev_alloc(c, &k.des, (size_t)(probs * 3)))) return rc;
-  if ((rc = dev_alloc(c, &k.err2, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.mu, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.nu, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.iters, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.calls, (size_t)probs))) return rc;
-  for (int q = 0; q < 2; q++) if ((rc = dev_alloc(c, &k.list[q], (size_t)probs))) return rc;
-  // staging of the host-array forms
-  if ((rc = dev_alloc(c, &k.io_s, (size_t)(probs * S)))) return rc;
-  if ((rc = dev_alloc(c, &k.io_3, (size_t)(probs * 3)))) return rc;
-  if ((rc = dev_alloc(c, &k.io_e, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.io_i, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.io_c, (size_t)probs))) return rc;
+  DevOwner &o = k.chunk;
+  o.release();
+  k.probs = k.lanes = 0;                       // (no buffer is usable until all of them exist again)
+  if ((rc = o.alloc(c, &k.xs, (size_t)(lanes * S))) || (rc = o.alloc(c, &k.tips, (size_t)(lanes * 3)))) return rc;
+  // per problem, by shape (io_*: the staging of the host-array forms)
+  if ((rc = o.alloc_all(c, {&k.p, &k.pn, &k.io_s}, (size_t)(probs * S)))) return rc;
+  if ((rc = o.alloc_all(c, {&k.f, &k.des, &k.io_3}, (size_t)(probs * 3)))) return rc;
+  if ((rc = o.alloc(c, &k.J, (size_t)(probs * 3 * S)))) return rc;
+  if ((rc = o.alloc_all(c, {&k.err2, &k.mu, &k.nu, &k.io_e}, (size_t)probs))) return rc;
+  if ((rc = o.alloc_all(c, {&k.iters, &k.calls, &k.list[0], &k.list[1], &k.io_i, &k.io_c}, (size_t)probs))) return rc;
   k.probs = probs;
   k.lanes = lanes;
+  return TR_OK;
+}
+
+// ---- what the host-array forms of this file and the loaded_*_host.inc files share: a host-array entry point stages chunks of its
+// arrays around the body its _dev twin runs (the same body, on the staging pointers and the null stream) --------------------------
+
+// the chunk's first row of an optional array of row width w (null stays null)
+template <typename T>
+T *rows_at(T *p, int64_t row, int64_t w = 1) { return p ? p + row * w : nullptr; }
+
+// rows [off, off + m) of a host array of row stride ld, packed to width w and uploaded (ld == 0: the one row there is)
+int upload_rows(tr_ctx *c, double *d_dst, const double *src, int64_t ld, int64_t off, int64_t m, int64_t w) {
+  const int64_t rows = ld == 0 ? 1 : m;
+  const double *from = src + off * ld;
+  std::vector<double> packed;
+  if (ld != w && rows > 1) {
+    packed.resize((size_t)(rows * w));
+    for (int64_t i = 0; i < rows; i++) for (int64_t q = 0; q < w; q++) packed[(size_t)(i * w + q)] = from[i * ld + q];
+    from = packed.data();
+  }
+  HIP_TRY(c, hipMemcpy(d_dst, from, (size_t)(rows * w) * sizeof(double), hipMemcpyHostToDevice));
+  return TR_OK;
+}
+
+// if the caller wants the array: m staged rows of width w down to its rows [off, off + m)
+template <typename T>
+int download_rows(tr_ctx *c, T *dst, const T *d_src, int64_t off, int64_t m, int64_t w = 1) {
+  if (dst) HIP_TRY(c, hipMemcpy(dst + off * w, d_src, (size_t)(m * w) * sizeof(T), hipMemcpyDeviceToHost));
   return TR_OK;
 }
 
@@ -65,7 +78,8 @@ unsigned ik_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / blo
 
 // K1 over `lanes` expanded states: tips only
 int ik_fk(tr_ctx *c, int64_t lanes, hipStream_t s) {
-  const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->ik.tips, nullptr, nullptr, nullptr};
+  trk::FkOut out = kFkOutNone;
+  out.tips = c->ik.tips;
   return launch_fk(c, c->ik.xs, lanes, round_up(lanes, 64), out, s);
 }
 
@@ -119,31 +133,56 @@ int ik_chunk_solve(tr_ctx *c, const trk::IkParams &prm, const double *d_init, in
   hipLaunchKernelGGL(trk::ik_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st);
   HIP_TRY(c, hipGetLastError());
   int64_t active = m;
-  int cur = 0;
+  int cur = 0, rc;
   for (bool init = true; active > 0; init = false) {
     const int nxt = cur ^ 1;
     const int32_t *list = init ? nullptr : k.list[cur];
-    HIP_TRY(c, hipMemsetAsync(k.d_count + nxt, 0, sizeof(uint32_t), s));
+    if ((rc = k.count.zero(nxt, s))) return rc;
     hipLaunchKernelGGL(trk::ik_expand, dim3(ik_grid(active * Q, 256)), dim3(256), 0, s, (const double *)k.pn, list, active, S, prm.delta, k.xs);
     HIP_TRY(c, hipGetLastError());
-    int rc;
     if ((rc = ik_fk(c, active * Q, s))) return rc;
     switch (S) {
 #define TRK_CASE(SS) case SS: hipLaunchKernelGGL((trk::ik_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, st, list, active, \
-                                                 (const double *)k.tips, (int)init, k.list[nxt], k.d_count + nxt); break;
+                                                 (const double *)k.tips, (int)init, k.list[nxt], k.count.d + nxt); break;
       TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8) TRK_CASE(9) TRK_CASE(10)
 #undef TRK_CASE
       default: return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(k.h_count, k.d_count + nxt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    active = (int64_t)*k.h_count;
+    if ((rc = k.count.read(nxt, s, active))) return rc;
     cur = nxt;
     rounds++;
   }
   hipLaunchKernelGGL(trk::ik_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_states, d_tips, d_err, d_iters, d_calls);
   HIP_TRY(c, hipGetLastError());
+  return TR_OK;
+}
+
+// tr_tip_jacobian*'s body: n device rows in chunks (d_tips may be null)
+int jacobian_run(tr_ctx *c, const double *d_states, int64_t n, double delta, double *d_tips, double *d_J, hipStream_t s) {
+  const int S = c->K.state_size;
+  int rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  const int64_t chunk = ik_chunk(c);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    if ((rc = jacobian_chunk(c, d_states + off * S, m, delta, rows_at(d_tips, off, 3), d_J + off * 3 * S, s))) return rc;
+  }
+  return TR_OK;
+}
+
+// tr_ik_batch*'s body: n device problems in chunks, each to the end (outputs may be null); adds its rounds to `rounds`
+int ik_run(tr_ctx *c, const trk::IkParams &prm, const double *d_init, int64_t n, const double *d_des, int64_t des_ld, double *d_states,
+           double *d_tips, double *d_err, int32_t *d_iters, int32_t *d_calls, hipStream_t s, int64_t &rounds) {
+  const int S = prm.S;
+  int rc;
+  if ((rc = ik_reserve(c, n))) return rc;
+  const int64_t chunk = ik_chunk(c);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    if ((rc = ik_chunk_solve(c, prm, d_init + off * S, m, d_des + off * des_ld, des_ld, rows_at(d_states, off, S), rows_at(d_tips, off, 3),
+                             rows_at(d_err, off), rows_at(d_iters, off), rows_at(d_calls, off), s, rounds))) return rc;
+  }
   return TR_OK;
 }
 
@@ -197,15 +236,9 @@ int tr_tip_jacobian_dev(tr_ctx *c, const double *d_states, int64_t n, double del
   if (!d_states || !d_J) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t s = (hipStream_t)stream;
-  const int S = c->K.state_size;
   int rc;
   if ((rc = begin_dev_work(c, s))) return rc;
-  if ((rc = ik_reserve(c, n))) return rc;
-  const int64_t chunk = ik_chunk(c);
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t m = std::min(chunk, n - off);
-    if ((rc = jacobian_chunk(c, d_states + off * S, m, delta, d_tips ? d_tips + off * 3 : nullptr, d_J + off * 3 * S, s))) return rc;
-  }
+  if ((rc = jacobian_run(c, d_states, n, delta, d_tips, d_J, s))) return rc;
   return note_dev_work(c, s);
 }
 
@@ -223,10 +256,9 @@ int tr_tip_jacobian(tr_ctx *c, const double *states, int64_t n, double delta, do
   const int64_t chunk = ik_chunk(c);
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
-    HIP_TRY(c, hipMemcpy(k.io_s, states + off * S, (size_t)(m * S) * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = jacobian_chunk(c, k.io_s, m, delta, tips ? k.io_3 : nullptr, k.J, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpy(J + off * 3 * S, k.J, (size_t)(m * 3 * S) * sizeof(double), hipMemcpyDeviceToHost));
-    if (tips) HIP_TRY(c, hipMemcpy(tips + off * 3, k.io_3, (size_t)(m * 3) * sizeof(double), hipMemcpyDeviceToHost));
+    if ((rc = upload_rows(c, k.io_s, states, S, off, m, S))) return rc;
+    if ((rc = jacobian_run(c, k.io_s, m, delta, tips ? k.io_3 : nullptr, k.J, nullptr))) return rc;
+    if ((rc = download_rows(c, J, k.J, off, m, 3 * S)) || (rc = download_rows(c, tips, k.io_3, off, m, 3))) return rc;
   }
   return TR_OK;
 }
@@ -242,21 +274,13 @@ int tr_ik_batch_dev(tr_ctx *c, const tr_ik_params *params, const double *d_initi
   if (!d_initial_states || !d_des) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t s = (hipStream_t)stream;
-  const int S = c->K.state_size;
   trk::IkParams prm;
   int rc;
   if ((rc = ik_params(c, params, lo, hi, prm))) return rc;
   if ((rc = begin_dev_work(c, s))) return rc;
-  if ((rc = ik_reserve(c, n))) return rc;
-  const int64_t chunk = ik_chunk(c);
   int64_t rounds = 0;
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t m = std::min(chunk, n - off);
-    if ((rc = ik_chunk_solve(c, prm, d_initial_states + off * S, m, d_des + off * des_ld, des_ld,
-                             d_states_out ? d_states_out + off * S : nullptr, d_tips_out ? d_tips_out + off * 3 : nullptr,
-                             d_error_out ? d_error_out + off : nullptr, d_iters_out ? d_iters_out + off : nullptr,
-                             d_fk_calls_out ? d_fk_calls_out + off : nullptr, s, rounds))) return rc;
-  }
+  if ((rc = ik_run(c, prm, d_initial_states, n, d_des, des_ld, d_states_out, d_tips_out, d_error_out, d_iters_out, d_fk_calls_out, s,
+                   rounds))) return rc;
   if (rounds_out) *rounds_out = rounds;
   return note_dev_work(c, s);
 }
@@ -279,25 +303,15 @@ int tr_ik_batch(tr_ctx *c, const tr_ik_params *params, const double *initial_sta
   if ((rc = ik_reserve(c, n))) return rc;
   tr_ctx::IkDev &k = c->ik;
   const int64_t chunk = ik_chunk(c);
-  std::vector<double> dbuf;
   int64_t rounds = 0;
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
-    HIP_TRY(c, hipMemcpy(k.io_s, initial_states + off * S, (size_t)(m * S) * sizeof(double), hipMemcpyHostToDevice));
-    if (des_ld == 0) {
-      HIP_TRY(c, hipMemcpy(k.io_3, des, 3 * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-      dbuf.resize((size_t)(m * 3));
-      for (int64_t i = 0; i < m; i++) for (int q = 0; q < 3; q++) dbuf[(size_t)(i * 3 + q)] = des[(off + i) * des_ld + q];
-      HIP_TRY(c, hipMemcpy(k.io_3, dbuf.data(), (size_t)(m * 3) * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_rows(c, k.io_s, initial_states, S, off, m, S)) || (rc = upload_rows(c, k.io_3, des, des_ld, off, m, 3))) return rc;
     // (io_s / io_3 are read by ik_init before ik_finish overwrites them with the results)
-    if ((rc = ik_chunk_solve(c, prm, k.io_s, m, k.io_3, des_ld ? 3 : 0, k.io_s, k.io_3, k.io_e, k.io_i, k.io_c, nullptr, rounds))) return rc;
-    if (states_out) HIP_TRY(c, hipMemcpy(states_out + off * S, k.io_s, (size_t)(m * S) * sizeof(double), hipMemcpyDeviceToHost));
-    if (tips_out) HIP_TRY(c, hipMemcpy(tips_out + off * 3, k.io_3, (size_t)(m * 3) * sizeof(double), hipMemcpyDeviceToHost));
-    if (error_out) HIP_TRY(c, hipMemcpy(error_out + off, k.io_e, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
-    if (iters_out) HIP_TRY(c, hipMemcpy(iters_out + off, k.io_i, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (fk_calls_out) HIP_TRY(c, hipMemcpy(fk_calls_out + off, k.io_c, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if ((rc = ik_run(c, prm, k.io_s, m, k.io_3, des_ld ? 3 : 0, k.io_s, k.io_3, k.io_e, k.io_i, k.io_c, nullptr, rounds))) return rc;
+    if ((rc = download_rows(c, states_out, k.io_s, off, m, S)) || (rc = download_rows(c, tips_out, k.io_3, off, m, 3)) ||
+        (rc = download_rows(c, error_out, k.io_e, off, m)) || (rc = download_rows(c, iters_out, k.io_i, off, m)) ||
+        (rc = download_rows(c, fk_calls_out, k.io_c, off, m))) return rc;
   }
   if (rounds_out) *rounds_out = rounds;
   return TR_OK;

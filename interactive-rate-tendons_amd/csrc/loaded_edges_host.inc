@@ -31,12 +31,15 @@ struct LoadedEdges {
   int reserve(int64_t cap) {
     tr_ctx::LoadedEdgeDev &le = c->ledge;
     int rc;
-    if (!le.tally && (rc = dev_alloc(c, &le.tally, 2))) return rc;
+    if (!le.tally && (rc = le.once.alloc(c, &le.tally, 2))) return rc;
     if (le.cap < cap) {
       HIP_TRY(c, hipDeviceSynchronize());
-      if ((rc = dev_alloc(c, &le.vu_pool, (size_t)cap * 6)) || (rc = dev_alloc(c, &le.w, (size_t)cap * 6)) ||
-          (rc = dev_alloc(c, &le.d, (size_t)cap * 6)) || (rc = dev_alloc(c, &le.g, (size_t)cap * 6)) ||
-          (rc = dev_alloc(c, &le.calls, (size_t)cap))) return rc;
+      DevOwner &o = le.pool;
+      o.release();
+      le.cap = 0;
+      if ((rc = o.alloc(c, &le.vu_pool, (size_t)cap * 6)) || (rc = o.alloc(c, &le.w, (size_t)cap * 6)) ||
+          (rc = o.alloc(c, &le.d, (size_t)cap * 6)) || (rc = o.alloc(c, &le.g, (size_t)cap * 6)) ||
+          (rc = o.alloc(c, &le.calls, (size_t)cap))) return rc;
       le.cap = cap;
     }
     return shoot_reserve(c, cap);
@@ -144,14 +147,8 @@ int loaded_edges_begin(tr_ctx *c, const tr_space_params *sp, const tr_shoot_para
   empty = false;
   int rc;
   le.c = c;
-  le.loads = trk::EdgeLoadsK{};
-  le.warm = false;
-  if (loads) {
-    if (loads->frame != TR_LOAD_FRAME_BASE && loads->frame != TR_LOAD_FRAME_WORLD) return fail(c, TR_ERR_INVALID_ARG, "bad argument (frame: TR_LOAD_FRAME_BASE or TR_LOAD_FRAME_WORLD)");
-    for (int q = 0; q < 6; q++) { le.loads.wrench[q] = loads->wrench[q]; le.loads.dist[q] = loads->dist[q]; }
-    le.loads.world = loads->frame == TR_LOAD_FRAME_WORLD;
-    le.warm = loads->warm_start != 0;
-  }
+  if ((rc = parse_loads(c, loads, le.loads))) return rc;
+  le.warm = loads && loads->warm_start != 0;
   if ((rc = shoot_check(c, n_edges, 0, 0))) return rc;
   if ((rc = shoot_params(c, shoot, le.prm))) return rc;
   if (n_edges == 0) { empty = true; return TR_OK; }

@@ -12,11 +12,7 @@ int64_t shoot_io_chunk(const tr_ctx *c) { return std::min<int64_t>(shoot_chunk_s
 
 void shoot_release(tr_ctx *c) {
   tr_ctx::ShootDev &k = c->shoot;
-  void *p[] = {k.xs, k.res, k.p, k.pn, k.e, k.J, k.err2, k.mu, k.nu, k.iters, k.calls, k.list[0], k.list[1], k.d_count, k.tip_route, k.zero6,
-               k.io_states, k.io_w, k.io_d, k.io_g, k.io_px, k.io_py, k.io_pz, k.io_R, k.io_L, k.io_Li, k.io_vu, k.io_vuL, k.io_e, k.io_np, k.io_it,
-               k.io_fc, k.io_conv};
-  for (void *q : p) if (q) (void)hipFree(q);
-  if (k.h_count) (void)hipHostFree(k.h_count);
+  k.chunk.release(); k.once.release(); k.io.release(); k.io_frames.release(); k.count.release();
   k = tr_ctx::ShootDev{};
 }
 
@@ -25,31 +21,27 @@ int shoot_reserve(tr_ctx *c, int64_t n) {
   tr_ctx::ShootDev &k = c->shoot;
   const int64_t probs = round_up(std::max<int64_t>(1, std::min(n, shoot_chunk_size(c))), 64), lanes = round_up(probs * trk::kShootQ, 64);
   int rc;
-  if (!k.d_count) {
-    if ((rc = dev_alloc(c, &k.d_count, 2))) return rc;
-    HIP_TRY(c, hipHostMalloc((void **)&k.h_count, sizeof(uint32_t), hipHostMallocDefault));
+  if (!k.zero6) {
+    if ((rc = k.count.reserve(c, k.once))) return rc;
     const int N = c->K.n_tendons;
     std::vector<double> route((size_t)N * 6);
     routing_at(c, c->K.L, route.data());
-    if ((rc = dev_alloc(c, &k.tip_route, route.size()))) return rc;
+    if ((rc = k.once.alloc(c, &k.tip_route, route.size()))) return rc;
     HIP_TRY(c, hipMemcpy(k.tip_route, route.data(), route.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(c, &k.zero6, 6))) return rc;
+    if ((rc = k.once.alloc(c, &k.zero6, 6))) return rc;
     HIP_TRY(c, hipMemset(k.zero6, 0, 6 * sizeof(double)));
   }
   if (k.probs >= probs) return TR_OK;
   HIP_TRY(c, hipDeviceSynchronize());
-  if ((rc = dev_alloc(c, &k.xs, (size_t)(lanes * 6)))) return rc;
-  if ((rc = dev_alloc(c, &k.res, (size_t)(lanes * 6)))) return rc;
-  if ((rc = dev_alloc(c, &k.p, (size_t)(probs * 6)))) return rc;
-  if ((rc = dev_alloc(c, &k.pn, (size_t)(probs * 6)))) return rc;
-  if ((rc = dev_alloc(c, &k.e, (size_t)(probs * 6)))) return rc;
-  if ((rc = dev_alloc(c, &k.J, (size_t)(probs * 36)))) return rc;
-  if ((rc = dev_alloc(c, &k.err2, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.mu, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.nu, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.iters, (size_t)probs))) return rc;
-  if ((rc = dev_alloc(c, &k.calls, (size_t)probs))) return rc;
-  for (int q = 0; q < 2; q++) if ((rc = dev_alloc(c, &k.list[q], (size_t)probs))) return rc;
+  DevOwner &o = k.chunk;
+  o.release();
+  k.probs = k.lanes = 0;                       // (no buffer is usable until all of them exist again)
+  if ((rc = o.alloc_all(c, {&k.xs, &k.res}, (size_t)(lanes * 6)))) return rc;
+  // per problem, by shape
+  if ((rc = o.alloc_all(c, {&k.p, &k.pn, &k.e}, (size_t)(probs * 6)))) return rc;
+  if ((rc = o.alloc(c, &k.J, (size_t)(probs * 36)))) return rc;
+  if ((rc = o.alloc_all(c, {&k.err2, &k.mu, &k.nu}, (size_t)probs))) return rc;
+  if ((rc = o.alloc_all(c, {&k.iters, &k.calls, &k.list[0], &k.list[1]}, (size_t)probs))) return rc;
   k.probs = probs;
   k.lanes = lanes;
   return TR_OK;
@@ -63,27 +55,23 @@ int shoot_reserve_io(tr_ctx *c, int64_t n, bool want_R) {
   int rc;
   if (k.io_probs < probs) {
     HIP_TRY(c, hipDeviceSynchronize());
-    if ((rc = dev_alloc(c, &k.io_states, (size_t)probs * S))) return rc;
-    if ((rc = dev_alloc(c, &k.io_w, (size_t)probs * 6))) return rc;
-    if ((rc = dev_alloc(c, &k.io_d, (size_t)probs * 6))) return rc;
-    if ((rc = dev_alloc(c, &k.io_g, (size_t)probs * 6))) return rc;
-    if ((rc = dev_alloc(c, &k.io_px, P * (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_py, P * (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_pz, P * (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_L, (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_Li, N * (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_vu, (size_t)probs * 6))) return rc;
-    if ((rc = dev_alloc(c, &k.io_vuL, (size_t)probs * 6))) return rc;
-    if ((rc = dev_alloc(c, &k.io_e, (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_np, (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_it, (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_fc, (size_t)probs))) return rc;
-    if ((rc = dev_alloc(c, &k.io_conv, (size_t)probs))) return rc;
+    DevOwner &o = k.io;
+    o.release();
+    k.io_probs = 0;
+    if ((rc = o.alloc(c, &k.io_states, (size_t)probs * S))) return rc;
+    if ((rc = o.alloc_all(c, {&k.io_w, &k.io_d, &k.io_g, &k.io_vu, &k.io_vuL}, (size_t)probs * 6))) return rc;
+    if ((rc = o.alloc_all(c, {&k.io_px, &k.io_py, &k.io_pz}, P * (size_t)probs))) return rc;
+    if ((rc = o.alloc(c, &k.io_Li, N * (size_t)probs))) return rc;
+    if ((rc = o.alloc_all(c, {&k.io_L, &k.io_e}, (size_t)probs))) return rc;
+    if ((rc = o.alloc_all(c, {&k.io_np, &k.io_it, &k.io_fc}, (size_t)probs))) return rc;
+    if ((rc = o.alloc(c, &k.io_conv, (size_t)probs))) return rc;
     k.io_probs = probs;
   }
   if (want_R && k.io_R_probs < probs) {
     HIP_TRY(c, hipDeviceSynchronize());
-    if ((rc = dev_alloc(c, &k.io_R, 9 * P * (size_t)probs))) return rc;
+    k.io_frames.release();
+    k.io_R_probs = 0;
+    if ((rc = k.io_frames.alloc(c, &k.io_R, 9 * P * (size_t)probs))) return rc;
     k.io_R_probs = probs;
   }
   return TR_OK;
@@ -113,17 +101,24 @@ int shoot_check(tr_ctx *c, int64_t n, int64_t wrench_ld, int64_t dist_ld) {
   return TR_OK;
 }
 
+// The one load set of a call (the edge, roadmap, IK and Jacobian calls on loaded shapes) in the form its kernels take: Loads is
+// trk::EdgeLoadsK or trk::IklLoads, kernel parameter types with the same three members.  loads == NULL: no load.
+template <typename Loads>
+int parse_loads(tr_ctx *c, const tr_edge_loads *loads, Loads &dst) {
+  dst = Loads{};
+  if (!loads) return TR_OK;
+  if (loads->frame != TR_LOAD_FRAME_BASE && loads->frame != TR_LOAD_FRAME_WORLD)
+    return fail(c, TR_ERR_INVALID_ARG, "bad argument (frame: TR_LOAD_FRAME_BASE or TR_LOAD_FRAME_WORLD)");
+  for (int q = 0; q < 6; q++) { dst.wrench[q] = loads->wrench[q]; dst.dist[q] = loads->dist[q]; }
+  dst.world = loads->frame == TR_LOAD_FRAME_WORLD;
+  return TR_OK;
+}
+
 // `lanes` integrations: lane t is problem list[t / Q] (list null: t / Q) of d_states from strains vu[t]
 int shoot_fk(tr_ctx *c, const double *d_states, int64_t lanes, int64_t ld, const trk::FkOut &out, trk::LoadedIn in, hipStream_t s) {
   in.tip_route = c->shoot.tip_route;
-  const trk::FkLaunch a{d_states, lanes, ld, c->K, (bool)c->K.enable_rotation, out.R != nullptr, c->d_tab, c->d_steps,
-                        (int)c->steps.size(), c->d_poly, c->k_first, c->d_tgrid, c->d_hl, out, s};
-  switch (c->K.n_tendons) {
-#define TRK_CASE(N) case N: trk::launch_fk_loaded<N>(a, in); break;
-    TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-    default: return fail(c, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-  }
+  const trk::FkLaunch a = fk_launch_args(c, d_states, lanes, ld, out, out.R != nullptr, s);
+  TRK_FOR_TENDONS(c, trk::launch_fk_loaded<N>(a, in));
   HIP_TRY(c, hipGetLastError());
   return TR_OK;
 }
@@ -137,53 +132,41 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
   tr_ctx::ShootDev &k = c->shoot;
   constexpr int Q = trk::kShootQ;
   const trk::ShootState st{k.p, k.pn, k.e, k.J, k.err2, k.mu, k.nu, k.iters, k.calls};
-  const trk::FkOut none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const trk::LoadedIn base{d_wrench, wrench_ld, d_dist, dist_ld, nullptr, nullptr, 1, nullptr, k.res, k.lanes, nullptr};
   int rc;
   {
-    const trk::FkLaunch a{d_states, m, ld, c->K, (bool)c->K.enable_rotation, false, c->d_tab, c->d_steps, (int)c->steps.size(),
-                          c->d_poly, c->k_first, c->d_tgrid, c->d_hl, none, s};
-    switch (c->K.n_tendons) {
-#define TRK_CASE(N) case N: trk::launch_shoot_start<N>(a, d_guess, k.pn); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-      default: return fail(c, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-    }
+    const trk::FkLaunch a = fk_launch_args(c, d_states, m, ld, kFkOutNone, false, s);
+    TRK_FOR_TENDONS(c, trk::launch_shoot_start<N>(a, d_guess, k.pn));
     HIP_TRY(c, hipGetLastError());
   }
-  auto read_count = [&](int slot, int64_t &active) -> int {
-    HIP_TRY(c, hipMemcpyAsync(k.h_count, k.d_count + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    active = (int64_t)*k.h_count;
-    rounds++;
-    return TR_OK;
-  };
   // the start of every problem: one lane each
   int cur = 0;
   int64_t active = 0;
-  HIP_TRY(c, hipMemsetAsync(k.d_count + cur, 0, sizeof(uint32_t), s));
+  if ((rc = k.count.zero(cur, s))) return rc;
   {
     trk::LoadedIn in = base;
     in.vu = k.pn;
-    if ((rc = shoot_fk(c, d_states, m, ld, none, in, s))) return rc;
+    if ((rc = shoot_fk(c, d_states, m, ld, kFkOutNone, in, s))) return rc;
   }
   hipLaunchKernelGGL(trk::shoot_begin, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, (const double *)k.res, k.lanes, k.list[cur],
-                     k.d_count + cur);
+                     k.count.d + cur);
   HIP_TRY(c, hipGetLastError());
-  if ((rc = read_count(cur, active))) return rc;
+  if ((rc = k.count.read(cur, s, active))) return rc;
+  rounds++;
   while (active > 0) {
     const int nxt = cur ^ 1;
-    HIP_TRY(c, hipMemsetAsync(k.d_count + nxt, 0, sizeof(uint32_t), s));
+    if ((rc = k.count.zero(nxt, s))) return rc;
     hipLaunchKernelGGL(trk::ik_expand, dim3(ik_grid(active * Q, 256)), dim3(256), 0, s, (const double *)k.pn, (const int32_t *)k.list[cur],
                        active, 6, prm.delta, k.xs);
     HIP_TRY(c, hipGetLastError());
     trk::LoadedIn in = base;
     in.vu = k.xs; in.list = k.list[cur]; in.Q = Q;
-    if ((rc = shoot_fk(c, d_states, active * Q, ld, none, in, s))) return rc;
+    if ((rc = shoot_fk(c, d_states, active * Q, ld, kFkOutNone, in, s))) return rc;
     hipLaunchKernelGGL(trk::shoot_lm_step, dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, st, (const int32_t *)k.list[cur], active,
-                       (const double *)k.res, k.lanes, k.list[nxt], k.d_count + nxt);
+                       (const double *)k.res, k.lanes, k.list[nxt], k.count.d + nxt);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = read_count(nxt, active))) return rc;
+    if ((rc = k.count.read(nxt, s, active))) return rc;
+    rounds++;
     cur = nxt;
   }
   // the outputs: every problem once more at its final strains (final_launch false: the caller wants the strains and flags only)
@@ -194,6 +177,27 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
   }
   hipLaunchKernelGGL(trk::shoot_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_vu0, d_res, d_iters, d_calls, d_conv);
   HIP_TRY(c, hipGetLastError());
+  return TR_OK;
+}
+
+// tr_fk_loaded_batch*'s body: n device problems in chunks, each to the end.  d_wrench null: no tip wrench; `out`: K1's outputs with
+// column 0 = problem 0 (planes of leading dimension ld); every output may be null.  Adds its rounds to `rounds`.
+int shoot_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, int64_t n, int64_t ld, const double *d_wrench,
+              int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess, const trk::FkOut &out, uint8_t *d_conv,
+              double *d_vu0, double *d_vuL, double *d_res, int32_t *d_iters, int32_t *d_calls, hipStream_t s, int64_t &rounds) {
+  const int S = c->K.state_size;
+  int rc;
+  if ((rc = shoot_reserve(c, n))) return rc;
+  const int64_t chunk = shoot_chunk_size(c);
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    const trk::FkOut o{rows_at(out.px, off), rows_at(out.py, off), rows_at(out.pz, off), rows_at(out.R, off), rows_at(out.L, off),
+                       rows_at(out.Li, off), nullptr, nullptr, rows_at(out.n_points, off), nullptr};
+    if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, m, ld, d_wrench ? d_wrench + off * wrench_ld : c->shoot.zero6,
+                                d_wrench ? wrench_ld : 0, rows_at(d_dist, off, dist_ld), dist_ld, rows_at(d_guess, off, 6), o,
+                                rows_at(d_conv, off), rows_at(d_vu0, off, 6), rows_at(d_vuL, off, 6), rows_at(d_res, off),
+                                rows_at(d_iters, off), rows_at(d_calls, off), s, rounds))) return rc;
+  }
   return TR_OK;
 }
 
@@ -218,26 +222,13 @@ int tr_fk_loaded_batch_dev(tr_ctx *c, const tr_shoot_params *params, const doubl
   if (d_R && !d_px) return fail(c, TR_ERR_INVALID_ARG, "d_R needs the point planes");
   HIP_TRY(c, hipSetDevice(c->device));
   const hipStream_t s = (hipStream_t)stream;
-  const int S = c->K.state_size;
   trk::ShootParams prm;
   if ((rc = shoot_params(c, params, prm))) return rc;
   if ((rc = begin_dev_work(c, s))) return rc;
-  if ((rc = shoot_reserve(c, n))) return rc;
-  const int64_t chunk = shoot_chunk_size(c);
+  const trk::FkOut out{d_px, d_py, d_pz, d_R, d_L, d_Li, nullptr, nullptr, d_n_points, nullptr};
   int64_t rounds = 0;
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t m = std::min(chunk, n - off);
-    const trk::FkOut out{d_px ? d_px + off : nullptr, d_py ? d_py + off : nullptr, d_pz ? d_pz + off : nullptr, d_R ? d_R + off : nullptr,
-                         d_L ? d_L + off : nullptr, d_Li ? d_Li + off : nullptr, nullptr, nullptr, d_n_points ? d_n_points + off : nullptr,
-                         nullptr};
-    if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, m, ld, d_wrench ? d_wrench + off * wrench_ld : c->shoot.zero6,
-                                d_wrench ? wrench_ld : 0, d_dist ? d_dist + off * dist_ld : nullptr, dist_ld,
-                                d_guess ? d_guess + off * 6 : nullptr, out, d_converged ? d_converged + off : nullptr,
-                                d_vu0_out ? d_vu0_out + off * 6 : nullptr, d_vuL_out ? d_vuL_out + off * 6 : nullptr,
-                                d_residual_out ? d_residual_out + off : nullptr,
-                                d_iters_out ? d_iters_out + off : nullptr, d_fk_calls_out ? d_fk_calls_out + off : nullptr, s, rounds)))
-      return rc;
-  }
+  if ((rc = shoot_run(c, prm, d_states, n, ld, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, out, d_converged, d_vu0_out, d_vuL_out,
+                      d_residual_out, d_iters_out, d_fk_calls_out, s, rounds))) return rc;
   if (rounds_out) *rounds_out = rounds;
   return note_dev_work(c, s);
 }
@@ -258,32 +249,21 @@ int tr_fk_loaded_batch(tr_ctx *c, const tr_shoot_params *params, const double *s
   const int S = c->K.state_size, P = c->K.n_points, N = c->K.n_tendons;
   trk::ShootParams prm;
   if ((rc = shoot_params(c, params, prm))) return rc;
-  const int64_t chunk = shoot_io_chunk(c);
-  if ((rc = shoot_reserve(c, std::min(n, chunk)))) return rc;
+  const int64_t chunk = shoot_io_chunk(c);      // (no more than one chunk of the body's: its loop runs once per staging chunk)
   if ((rc = shoot_reserve_io(c, n, R != nullptr))) return rc;
   tr_ctx::ShootDev &k = c->shoot;
-  // rows of a strided host array, packed to 6 doubles each (ld == 0: the one row)
-  std::vector<double> rows;
-  auto upload_rows = [&](double *d_dst, const double *src, int64_t src_ld, int64_t off, int64_t m) -> int {
-    if (src_ld == 0) { HIP_TRY(c, hipMemcpy(d_dst, src, 6 * sizeof(double), hipMemcpyHostToDevice)); return TR_OK; }
-    rows.resize((size_t)(m * 6));
-    for (int64_t i = 0; i < m; i++) for (int q = 0; q < 6; q++) rows[(size_t)(i * 6 + q)] = src[(off + i) * src_ld + q];
-    HIP_TRY(c, hipMemcpy(d_dst, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    return TR_OK;
-  };
   std::vector<double> hx, hy, hz, hR, hLi;
   int64_t rounds = 0;
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off), ld = round_up(m, 64);
-    HIP_TRY(c, hipMemcpy(k.io_states, states + off * S, (size_t)m * S * sizeof(double), hipMemcpyHostToDevice));
-    if (wrench && (rc = upload_rows(k.io_w, wrench, wrench_ld, off, m))) return rc;
-    if (dist && (rc = upload_rows(k.io_d, dist, dist_ld, off, m))) return rc;
-    if (guess) HIP_TRY(c, hipMemcpy(k.io_g, guess + off * 6, (size_t)m * 6 * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = upload_rows(c, k.io_states, states, S, off, m, S))) return rc;
+    if (wrench && (rc = upload_rows(c, k.io_w, wrench, wrench_ld, off, m, 6))) return rc;
+    if (dist && (rc = upload_rows(c, k.io_d, dist, dist_ld, off, m, 6))) return rc;
+    if (guess && (rc = upload_rows(c, k.io_g, guess, 6, off, m, 6))) return rc;
     const trk::FkOut out{p || R ? k.io_px : nullptr, p || R ? k.io_py : nullptr, p || R ? k.io_pz : nullptr, R ? k.io_R : nullptr, k.io_L, k.io_Li,
                          nullptr, nullptr, k.io_np, nullptr};
-    if ((rc = shoot_chunk_solve(c, prm, k.io_states, m, ld, wrench ? k.io_w : k.zero6, wrench && wrench_ld ? 6 : 0, dist ? k.io_d : nullptr,
-                                dist_ld ? 6 : 0, guess ? k.io_g : nullptr, out, k.io_conv, k.io_vu, k.io_vuL, k.io_e, k.io_it, k.io_fc, nullptr, rounds)))
-      return rc;
+    if ((rc = shoot_run(c, prm, k.io_states, m, ld, wrench ? k.io_w : nullptr, wrench_ld ? 6 : 0, dist ? k.io_d : nullptr, dist_ld ? 6 : 0,
+                        guess ? k.io_g : nullptr, out, k.io_conv, k.io_vu, k.io_vuL, k.io_e, k.io_it, k.io_fc, nullptr, rounds))) return rc;
     HIP_TRY(c, hipDeviceSynchronize());
     // device planes are [P][ld]; only the first m columns are copied (2-D copies, host pitch m)
     if (p) {
@@ -304,19 +284,16 @@ int tr_fk_loaded_batch(tr_ctx *c, const tr_shoot_params *params, const double *s
         for (int j = 0; j < P; j++)
           for (int q = 0; q < 9; q++) R[((size_t)(off + i) * P + j) * 9 + q] = hR[((size_t)q * P + j) * m + i];
     }
-    if (L) HIP_TRY(c, hipMemcpy(L + off, k.io_L, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
+    if ((rc = download_rows(c, L, k.io_L, off, m))) return rc;
     if (L_i) {
       hLi.resize((size_t)N * m);
       HIP_TRY(c, hipMemcpy2D(hLi.data(), (size_t)m * 8, k.io_Li, (size_t)ld * 8, (size_t)m * 8, (size_t)N, hipMemcpyDeviceToHost));
       for (int64_t i = 0; i < m; i++) for (int j = 0; j < N; j++) L_i[(size_t)(off + i) * N + j] = hLi[(size_t)j * m + i];
     }
-    if (converged) HIP_TRY(c, hipMemcpy(converged + off, k.io_conv, (size_t)m, hipMemcpyDeviceToHost));
-    if (n_points) HIP_TRY(c, hipMemcpy(n_points + off, k.io_np, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (vu0_out) HIP_TRY(c, hipMemcpy(vu0_out + off * 6, k.io_vu, (size_t)m * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    if (vuL_out) HIP_TRY(c, hipMemcpy(vuL_out + off * 6, k.io_vuL, (size_t)m * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    if (residual_out) HIP_TRY(c, hipMemcpy(residual_out + off, k.io_e, (size_t)m * sizeof(double), hipMemcpyDeviceToHost));
-    if (iters_out) HIP_TRY(c, hipMemcpy(iters_out + off, k.io_it, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (fk_calls_out) HIP_TRY(c, hipMemcpy(fk_calls_out + off, k.io_fc, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if ((rc = download_rows(c, converged, k.io_conv, off, m)) || (rc = download_rows(c, n_points, k.io_np, off, m)) ||
+        (rc = download_rows(c, vu0_out, k.io_vu, off, m, 6)) || (rc = download_rows(c, vuL_out, k.io_vuL, off, m, 6)) ||
+        (rc = download_rows(c, residual_out, k.io_e, off, m)) || (rc = download_rows(c, iters_out, k.io_it, off, m)) ||
+        (rc = download_rows(c, fk_calls_out, k.io_fc, off, m))) return rc;
   }
   if (rounds_out) *rounds_out = rounds;
   return TR_OK;

@@ -19,13 +19,8 @@ int loaded_states_begin(tr_ctx *c, const tr_shoot_params *shoot, const tr_edge_l
   empty = false;
   int rc;
   le.c = c;
-  le.loads = trk::EdgeLoadsK{};
-  le.warm = false;
-  if (loads) {
-    if (loads->frame != TR_LOAD_FRAME_BASE && loads->frame != TR_LOAD_FRAME_WORLD) return fail(c, TR_ERR_INVALID_ARG, "bad argument (frame: TR_LOAD_FRAME_BASE or TR_LOAD_FRAME_WORLD)");
-    for (int q = 0; q < 6; q++) { le.loads.wrench[q] = loads->wrench[q]; le.loads.dist[q] = loads->dist[q]; }
-    le.loads.world = loads->frame == TR_LOAD_FRAME_WORLD;
-  }
+  if ((rc = parse_loads(c, loads, le.loads))) return rc;
+  le.warm = false;                             // every vertex is solved cold
   if ((rc = shoot_check(c, n, 0, 0))) return rc;
   if ((rc = shoot_params(c, shoot, le.prm))) return rc;
   if (n == 0) { empty = true; return TR_OK; }
@@ -66,10 +61,12 @@ int sample_valid_loaded_impl(tr_ctx *c, const tr_shoot_params *shoot, const tr_e
   tr_ctx::LoadedEdgeDev &ld = c->ledge;
   const bool own = d_states_out == nullptr;
   if (ld.out_cap < n_want) {
-    if ((rc = dev_alloc(c, &ld.out_vu, (size_t)n_want * 6)) || (rc = dev_alloc(c, &ld.out_index, (size_t)n_want))) return rc;
+    ld.out.release();
+    ld.out_cap = 0;
+    if ((rc = ld.out.alloc(c, &ld.out_vu, (size_t)n_want * 6)) || (rc = ld.out.alloc(c, &ld.out_index, (size_t)n_want))) return rc;
     ld.out_cap = n_want;
   }
-  if (!ld.vtally && (rc = dev_alloc(c, &ld.vtally, 2))) return rc;
+  if (!ld.vtally && (rc = ld.once.alloc(c, &ld.vtally, 2))) return rc;
   // a batch lives in the point workspace: what is still missing over the acceptance rate seen so far, 3 % + 512 on top, whole waves
   const int64_t kMaxBatch = c->loaded_vertex_batch > 0 ? c->loaded_vertex_batch : (int64_t)1 << 16;
   double rate = ld.rate_seen > 0.0 ? ld.rate_seen : 1.0;

@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <chrono>
 #include <thread>
 #include <ctime>
@@ -108,6 +109,35 @@ struct EdgeDev {
   // indexed forms: the roadmap's vertex states and the edges' index pairs (grow-only)
   double *ix_states = nullptr; int64_t ix_states_cap = 0;
   int32_t *ix_idx = nullptr; int64_t ix_idx_cap = 0;
+};
+
+// The device buffers of one group that grows together (the workspaces of the IK and loaded paths).  alloc hands a buffer out
+// through dev_alloc and remembers it; release frees all it handed out.  A reserve that grows releases its owner and allocates again,
+// so no second list of the group's pointers exists anywhere.
+struct DevOwner {
+  std::vector<void *> held;
+  template <typename T>
+  int alloc(tr_ctx *c, T **field, size_t count);             // (defined below dev_alloc)
+  template <typename T>
+  int alloc_all(tr_ctx *c, std::initializer_list<T **> fields, size_t count) {      // buffers of one shape
+    for (T **f : fields) if (const int rc = alloc(c, f, count)) return rc;
+    return 0;
+  }
+  void release() {
+    for (void *q : held) (void)hipFree(q);
+    held.clear();
+  }
+};
+
+// The active count of a solver's rounds: two device slots (a round's kernels count into the one the previous round did not use) and
+// the pinned word the host reads a slot through
+struct RoundCount {
+  tr_ctx *c = nullptr;
+  uint32_t *d = nullptr, *h = nullptr;
+  int reserve(tr_ctx *ctx, DevOwner &own);                   // (defined below dev_alloc; a no-op once reserved)
+  int zero(int slot, hipStream_t s);
+  int read(int slot, hipStream_t s, int64_t &active);        // synchronises s
+  void release() { if (h) (void)hipHostFree(h); d = h = nullptr; }   // (d is its owner's)
 };
 
 }  // namespace
@@ -254,9 +284,10 @@ struct tr_ctx {
     double *p = nullptr, *pn = nullptr, *f = nullptr, *J = nullptr, *des = nullptr;   // [probs][S | 3 | 3 S | 3]
     double *err2 = nullptr, *mu = nullptr, *nu = nullptr;
     int32_t *iters = nullptr, *calls = nullptr, *list[2] = {nullptr, nullptr};
-    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    RoundCount count;
     double *io_s = nullptr, *io_3 = nullptr, *io_e = nullptr;       // staging of the host-array forms
     int32_t *io_i = nullptr, *io_c = nullptr;
+    DevOwner chunk, once;                                           // everything sized by probs; the counter
   } ik;
   // loaded FK (loaded_host.inc): the lanes of one round and the per-problem state of one chunk of problems, grow-only; io_*: the
   // staging of the host-array form (its own, smaller chunk)
@@ -266,7 +297,7 @@ struct tr_ctx {
     double *p = nullptr, *pn = nullptr, *e = nullptr, *J = nullptr; // [probs][6 | 6 | 6 | 36]
     double *err2 = nullptr, *mu = nullptr, *nu = nullptr;
     int32_t *iters = nullptr, *calls = nullptr, *list[2] = {nullptr, nullptr};
-    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    RoundCount count;
     double *tip_route = nullptr, *zero6 = nullptr;                  // [N][6] routing at s = L; a zero wrench
     int64_t io_probs = 0, io_R_probs = 0;
     double *io_states = nullptr, *io_w = nullptr, *io_d = nullptr, *io_g = nullptr;
@@ -274,6 +305,7 @@ struct tr_ctx {
     double *io_vu = nullptr, *io_vuL = nullptr, *io_e = nullptr;
     int32_t *io_np = nullptr, *io_it = nullptr, *io_fc = nullptr;
     uint8_t *io_conv = nullptr;
+    DevOwner chunk, once, io, io_frames;                            // sized by probs; counter, tip_route, zero6; by io_probs; io_R
   } shoot;
   // loaded edges (loaded_edges_host.inc): per pool sample the accepted base strains [cap][6]; per level sample the load rows, the
   // start strains [cap][6] each and the integrations [cap]; the run's tally (unconverged samples, integrations)
@@ -288,6 +320,7 @@ struct tr_ctx {
     double *out_vu = nullptr; int64_t *out_index = nullptr; int64_t out_cap = 0;
     unsigned long long *vtally = nullptr;
     double rate_seen = 0.0;
+    DevOwner pool, out, once;                                       // sized by cap; by out_cap; the two tallies
   } ledge;
   // tip IK on loaded shapes (loaded_ik_host.inc): the per-problem state of one chunk of problems, the rows of one round in list
   // order, the [9][lanes] planes of the linearisation launch and the staging of the host-array form, grow-only
@@ -300,7 +333,7 @@ struct tr_ctx {
     uint8_t *eq = nullptr;
     double *row_s = nullptr, *row_w = nullptr, *row_d = nullptr, *row_g = nullptr, *row_vu = nullptr;   // [probs][S | 6 | 6 | 6 | 6]
     uint8_t *row_conv = nullptr; int32_t *row_calls = nullptr;
-    uint32_t *d_count = nullptr, *h_count = nullptr;                // active counts of the next round [2] and their pinned image
+    RoundCount count;
     double *io_s = nullptr, *io_3 = nullptr, *io_g = nullptr, *io_e = nullptr, *io_vu = nullptr;
     int32_t *io_i = nullptr, *io_c = nullptr;
     uint8_t *io_eq = nullptr;
@@ -309,6 +342,7 @@ struct tr_ctx {
     int64_t sens_probs = 0;
     double *sens_c = nullptr, *sens_b = nullptr;
     int64_t *sens_n = nullptr;
+    DevOwner chunk, once, sens;                                     // sized by probs; the counter; by sens_probs
   } ikl;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
@@ -414,6 +448,32 @@ int dev_alloc(tr_ctx *ctx, T **p, size_t count) {
     e = hipMalloc((void **)p, count * sizeof(T));
   }
   HIP_TRY(ctx, e);
+  return TR_OK;
+}
+
+template <typename T>
+int DevOwner::alloc(tr_ctx *c, T **field, size_t count) {
+  *field = nullptr;                      // (what it pointed to, if anything, went with the last release)
+  if (const int rc = dev_alloc(c, field, count)) return rc;
+  held.push_back(*field);
+  return TR_OK;
+}
+
+int RoundCount::reserve(tr_ctx *ctx, DevOwner &own) {
+  if (d) return TR_OK;
+  c = ctx;
+  if (const int rc = own.alloc(c, &d, 2)) return rc;
+  HIP_TRY(c, hipHostMalloc((void **)&h, sizeof(uint32_t), hipHostMallocDefault));
+  return TR_OK;
+}
+int RoundCount::zero(int slot, hipStream_t s) {
+  HIP_TRY(c, hipMemsetAsync(d + slot, 0, sizeof(uint32_t), s));
+  return TR_OK;
+}
+int RoundCount::read(int slot, hipStream_t s, int64_t &active) {
+  HIP_TRY(c, hipMemcpyAsync(h, d + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  active = (int64_t)*h;
   return TR_OK;
 }
 
@@ -603,12 +663,31 @@ trk::SweepIn ws_sweep_in(const tr_ctx *ctx, int64_t col) {
 }
 
 // ---- K1 launch (instantiations live in fk_inst.hip objects) ------------------------------------
+// this context's launch arguments of a K1-family kernel over n states (the verdict, fused and edge-queue launches set further fields)
+trk::FkLaunch fk_launch_args(const tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, bool write_R,
+                             hipStream_t s) {
+  return trk::FkLaunch{d_states, n, ld, ctx->K, (bool)ctx->K.enable_rotation, write_R, ctx->d_tab, ctx->d_steps,
+                       (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, out, s};
+}
+
+// a launch that stores nothing through FkOut
+const trk::FkOut kFkOutNone{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+
+// The statement(s) given, once per tendon count with N a constant expression: the dispatch to the kernels' instantiations.
+// Returns from the enclosing function when the context's count has none.
+#define TRK_TENDONS_CASE(COUNT, ...) case COUNT: { constexpr int N = COUNT; __VA_ARGS__; } break;
+#define TRK_FOR_TENDONS(ctx, ...)                                                                                          \
+  switch ((ctx)->K.n_tendons) {                                                                                            \
+    TRK_TENDONS_CASE(1, __VA_ARGS__) TRK_TENDONS_CASE(2, __VA_ARGS__) TRK_TENDONS_CASE(3, __VA_ARGS__) TRK_TENDONS_CASE(4, __VA_ARGS__) \
+    TRK_TENDONS_CASE(5, __VA_ARGS__) TRK_TENDONS_CASE(6, __VA_ARGS__) TRK_TENDONS_CASE(7, __VA_ARGS__) TRK_TENDONS_CASE(8, __VA_ARGS__) \
+    default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");                                              \
+  }
+
 int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, hipStream_t s, int lane = 0) {
   if (n <= 0) return TR_OK;
   ProfScope ps(ctx, 0, s);
   const bool ret = ctx->K.enable_retraction;
-  trk::FkLaunch a{d_states, n, ld, ctx->K, (bool)ctx->K.enable_rotation, out.R != nullptr, ctx->d_tab, ctx->d_steps,
-                  (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, out, s};
+  trk::FkLaunch a = fk_launch_args(ctx, d_states, n, ld, out, out.R != nullptr, s);
   if (ret && ctx->retract_sort_min > 0 && n >= ctx->retract_sort_min) {
     // A large batch of a retraction robot is integrated in the order of its backbone lengths, as the verdict-only kernels do
     // (a wave runs from its LONGEST backbone's base to the tip, the shorter ones idle: in arrival order half of the lane-steps
@@ -622,12 +701,7 @@ int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const 
     a.d_perm = perm;
     a.d_wave_k_begin = ctx->retract_wave_start ? ro.kbegin : nullptr;
   }
-  switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: if (ret) trk::launch_fk_retract<N>(a); else trk::launch_fk_uniform<N>(a); break;
-    TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-    default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-  }
+  TRK_FOR_TENDONS(ctx, if (ret) trk::launch_fk_retract<N>(a); else trk::launch_fk_uniform<N>(a));
   HIP_TRY(ctx, hipGetLastError());
   return TR_OK;
 }
@@ -1164,11 +1238,7 @@ void tr_destroy(tr_ctx *c) {
   ik_release(c);
   shoot_release(c);
   ikl_release(c);
-  {
-    tr_ctx::LoadedEdgeDev &le = c->ledge;
-    void *lp[] = {le.vu_pool, le.w, le.d, le.g, le.calls, le.tally, le.out_vu, le.out_index, le.vtally};
-    for (void *q : lp) if (q) (void)hipFree(q);
-  }
+  c->ledge.pool.release(); c->ledge.out.release(); c->ledge.once.release();
   delete c;
 }
 

@@ -52,7 +52,20 @@ def main():
             assert np.array_equal(big["status"][:1], out["status"][:1]) and (big["status"][0] != 0 or big["cost"][0] == out["cost"][0])
             if it % 8 == 0:
                 assert prm.release_search_state() > 0
-        sig = (int(v.sum()), int(ev.sum()), int(lv.sum()), float(lt.sum()), int(len(e_ok)), int((out["status"] == 0).sum()), float(np.nansum(out["cost"][out["status"] == 0])))
+        # the tip and loaded families, one call each on 4 096 states: their workspaces (tens of MiB per context) are the context's own,
+        # so one that is not freed with it crosses the bound below within the run
+        eng = robot.engine(0)
+        q = W.random_states(robot, 4096, seed=9, tau_max=10.0)
+        gravity = np.array([0.0, -2.4525, 0.0, 0.0, 0.0, 0.0])
+        J, tips = eng.tip_jacobian(q, want_tips=True)
+        goals = np.ascontiguousarray(np.roll(tips, 1, axis=0))
+        ik = eng.ik_batch(q, goals, max_iters=4)
+        lfk = eng.fk_loaded_batch(q, dist=gravity)
+        lik = eng.ik_loaded_batch(q, goals, dist=gravity, max_iters=2)
+        lj = eng.tip_jacobian_loaded(q, dist=gravity, want=("compliance", "W", "blocks"))
+        tip_sig = (float(np.nansum(J)), float(np.nansum(ik["error"])), int(ik["rounds"]), int(lfk["converged"].sum()), int(lfk["rounds"]),
+                   float(np.nansum(lik["error"])), int(lik["equilibrium"].sum()), float(np.nansum(lj["J"])), float(np.nansum(lj["compliance"])))
+        sig = (int(v.sum()), int(ev.sum()), int(lv.sum()), float(lt.sum()), int(len(e_ok)), int((out["status"] == 0).sum()), float(np.nansum(out["cost"][out["status"] == 0]))) + tip_sig
         key = (it % 2, it % 3 == 0, it % 5 == 0)
         if ref is None:
             ref = {}
@@ -61,7 +74,7 @@ def main():
         else:
             ref[key] = sig
         prm.close()
-        del prm, rb, mv, chk, vc, ec, full_vc
+        del prm, rb, mv, chk, vc, ec, full_vc, eng
         robot.close() if hasattr(robot, "close") else None
         gc.collect()
         torch.cuda.synchronize()
