@@ -746,8 +746,19 @@ int tr_roadmap_search_state_bytes(tr_roadmap *rm, int64_t *bytes);
  *      followed by the goal state (`controls`); cost = roadmap cost + state-space distance from the connection vertex to it.
  * The result joins the roadmap through that ONE validated edge, as an RMAP_IK_AUTO_ADD result without ACCURATE does in the reference
  * (:3242-3244, :3276-3287).  Deliberate difference: in the CLOSEST case the reference also connects the new vertex lazily to its
- * connection-strategy neighbours (:3534), so its cost may be smaller.  RMAP_IK_ACCURATE, RMAP_IK_LAZY_ADD and persistent insertion
- * into the graph are not offered; the graph is never edited. */
+ * connection-strategy neighbours (:3534), so its cost may be smaller.  RMAP_IK_LAZY_ADD and persistent insertion into the graph
+ * are not offered; the graph is never edited.
+ * RMAP_IK_ACCURATE (the *_connect entry points with k_connect > 0; :3237-3244, :3344-3352, :3471-3478): the vertex IK started from
+ * is nearest in TIP space; the straight state-space segment from it to the IK answer is often the one that collides while a
+ * state-space neighbour of the answer reaches it.  Rules 1, 2 and 6 stay; with N_q[i] the slot's IK vertex:
+ *   3'. C_i = tr_roadmap_nearest_states(x_i, k_connect, max_distance), then N_q[i] as the LAST source when C_i does not hold it
+ *       (:3238-3241): at most k_connect + 1 sources per slot.  (ok_ij, t_ij) = checkMotion(states[C_i[j]], x_i, last_valid) for every
+ *       source j in that order: all live pairs of the call in ONE tr_validate_edges_last_valid.
+ *   4'. TR_TIPQ_REACHED: the first (i, j) in lexicographic order with err_i < tolerance and ok_ij -> controls x_i, tip_i, err_i,
+ *       connection vertex C_i[j], t = 1.
+ *   5'. TR_TIPQ_CLOSEST: otherwise g_ij = interpolate(states[C_i[j]], x_i, t_ij), its tip from tr_fk_tips, e_ij = |tip(g_ij) - r_q|;
+ *       the smallest e_ij, the first in (i, j) order winning a tie (:3452-3521) -> controls g_ij, its tip, e_ij, C_i[j], t_ij.
+ * neighbor_vertex is the connection vertex (what rule 6 solves to); ik_vertex is N_q[i] of the chosen slot. */
 /* Replaces vertexTipPositionProperty_ (filled by voxelizeVertex :2803-2837 or read from the file): tips n_vertices x 3 (NULL: computed
  * once with tr_fk_tips_dev from the roadmap's states); present_bits (optional): a 0 bit = the vertex has no tip and is never a
  * neighbour.  Uploads the tips and a copy of the states. */
@@ -781,6 +792,35 @@ int tr_roadmap_solve_tips(tr_roadmap *rm, const tr_space_params *sp, const tr_ti
  * (validity + tip_knn + gather), out[1] IK, out[2] edges, out[3] select (interpolation, FK, choice, results), out[4] solve;
  * out[5] = rounds of the IK batch. */
 int tr_roadmap_tip_query_profile(tr_roadmap *rm, double out[6]);
+/* The k nearest roadmap vertices of ARBITRARY states (tr_knn answers only for rows of its own array) -- connectionStrategy_(vertex)
+ * for a state that is not in the roadmap: queries n x state_size; per query the first k vertices in the order (dist, vertex index)
+ * among the vertices valid in the current grid (validity learned and kept as rule 1 does; having a tip is not required); vertices
+ * n x k (-1 padded), dist (optional) n x k (+inf where padded).  Entries farther than max_distance are dropped (INFINITY: no bound).
+ * dist = CompoundStateSpace::distance in tr_knn's arithmetic, fp64 without contraction: s2 = 0, s2 += t t over the tension
+ * differences left to right, sqrt(s2), + w_rot arc (arc = |dtheta|, 2 pi - |dtheta| beyond pi), + w_ret sqrt(ds ds)
+ * (tr_space_weights); candidates whose distances round equal stay in index order.  k: 1 .. 64; needs tr_roadmap_set_tips (it uploads
+ * the states).  Exact, brute force over the vertex array (state_knn).  The _dev form takes device pointers on the context's GPU and
+ * synchronises as tr_roadmap_nearest_tips_dev does: the device before, the null stream after. */
+int tr_roadmap_nearest_states(tr_roadmap *rm, const double *queries, int64_t n, int32_t k, double max_distance, int32_t *vertices, double *dist);
+int tr_roadmap_nearest_states_dev(tr_roadmap *rm, const double *d_queries, int64_t n, int32_t k, double max_distance, int32_t *d_vertices,
+                                  double *d_dist);
+/* The accurate rule (3' - 5' above).  k_connect: 0 .. 64; 0, or a NULL tr_tip_connect_params*, is the one-edge rule with its bits and
+ * ik_vertex = neighbor_vertex.  n k (k_connect + 1) <= 2^28.  max_distance bounds the source search (INFINITY: none). */
+typedef struct {
+  int32_t k_connect;
+  double max_distance;
+} tr_tip_connect_params;
+int tr_roadmap_ik_batch_connect(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                const double *requests, int64_t n, double *controls, double *tips, double *error, int32_t *neighbor_vertex,
+                                int32_t *ik_vertex, int32_t *outcome, double *last_valid_t);
+int tr_roadmap_solve_tips_connect(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                  const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls, double *tips,
+                                  double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
+                                  int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats);
+/* Of the last *_connect call on this roadmap: out[0] pairs checked, out[1] requests REACHED, out[2] requests whose connection vertex
+ * differs from their ik_vertex, out[3] requests REACHED that the one-edge rule, restricted to the pairs (i, N_q[i]), does not reach.
+ * The source search counts into `nearest` of tr_roadmap_tip_query_profile. */
+int tr_roadmap_tip_connect_stats(tr_roadmap *rm, int64_t out[4]);
 
 /* The connection loop itself (motion-planning/VoxelCachedLazyPRM.cpp:1491-1502: for every vertex v and every neighbour n
  * of connectionStrategy_(v), `if (!getEdge(v, n)) connectVertices(v, n)`): the undirected edge set of the k-nearest

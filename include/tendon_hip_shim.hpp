@@ -1345,6 +1345,74 @@ class VoxelCachedLazyPRM {
     return s;
   }
 
+  // ---- RMAP_IK_ACCURATE for a batch (tr_roadmap_nearest_states / tr_roadmap_ik_batch_connect / tr_roadmap_solve_tips_connect) ----
+  struct NearestStates {
+    std::vector<int32_t> vertices;         // n x k, -1 padded
+    std::vector<double> distance;          // n x k, +inf where padded
+  };
+  /// connectionStrategy_ for states that are not in the roadmap: per query (n x state size, flat) the k nearest vertices in state
+  /// space among those not known invalid, in the order (distance, vertex index), none farther than max_distance.
+  NearestStates nearestStates(const std::vector<double> &queries, size_t k, double max_distance = std::numeric_limits<double>::infinity()) {
+    if (queries.size() % S_ != 0) throw std::invalid_argument("nearestStates: queries must be n x state size");
+    sync_tips();
+    const size_t n = queries.size() / S_;
+    NearestStates r;
+    r.vertices.assign(n * k, -1); r.distance.assign(n * k, std::numeric_limits<double>::infinity());
+    rcheck(tr_roadmap_nearest_states(rm_, queries.data(), (int64_t)n, (int32_t)k, max_distance, r.vertices.data(), r.distance.data()));
+    return r;
+  }
+  struct AccurateTipResults : TipResults {   // neighbor_vertex: the connection vertex, a state-space neighbour of the goal state
+    std::vector<int32_t> ik_vertex;          // the vertex IK started from
+    std::array<int64_t, 4> connect_stats{};  // pairs checked, reached, connection vertex != ik_vertex, reached only by this rule
+  };
+  struct AccurateTipSolution { AccurateTipResults ik; Solution roadmap; };
+  /// roadmapIkBatch under RMAP_IK_ACCURATE (rules 3' - 5' in include/tendon_hip.h): every IK answer is tried from its k_connect
+  /// state-space neighbours and then from the vertex IK started from; nothing is added to the graph.
+  AccurateTipResults roadmapIkBatchAccurate(const std::vector<std::array<double, 3>> &requests, double tolerance = 1e-4, size_t k = 5,
+                                            size_t k_connect = 10, double max_distance = std::numeric_limits<double>::infinity()) {
+    need_validators("roadmapIkBatchAccurate");
+    refuse_loaded("roadmapIkBatchAccurate");
+    sync_tips();
+    const size_t n = requests.size();
+    AccurateTipResults r;
+    static_cast<TipResults &>(r) = tip_results(n);
+    r.ik_vertex.resize(n);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    const tr_tip_connect_params cp{(int32_t)k_connect, max_distance};
+    rcheck(tr_roadmap_ik_batch_connect(rm_, &mv_->space, &prm, &cp, n ? requests[0].data() : nullptr, (int64_t)n, r.controls.data(),
+                                       r.tip_positions.data(), r.error.data(), r.neighbor_vertex.data(), r.ik_vertex.data(), r.outcome.data(),
+                                       r.last_valid_t.data()));
+    rcheck(tr_roadmap_tip_connect_stats(rm_, r.connect_stats.data()));
+    return r;
+  }
+  /// ... followed by solveWithRoadmap from starts[q] to request q's connection vertex, as solveToTips.
+  AccurateTipSolution solveToTipsAccurate(const std::vector<int32_t> &starts, const std::vector<std::array<double, 3>> &requests,
+                                          double tolerance = 1e-4, size_t k = 5, size_t k_connect = 10, int n_threads = 0,
+                                          double max_distance = std::numeric_limits<double>::infinity()) {
+    if (starts.size() != requests.size()) throw std::invalid_argument("starts and requests differ in length");
+    need_validators("solveToTipsAccurate");
+    refuse_loaded("solveToTipsAccurate");
+    sync_tips();
+    const size_t n = requests.size();
+    AccurateTipSolution s;
+    static_cast<TipResults &>(s.ik) = tip_results(n);
+    s.ik.ik_vertex.resize(n);
+    s.roadmap.status.resize(n); s.roadmap.cost.resize(n);
+    std::vector<int64_t> off(n + 1, 0);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    const tr_tip_connect_params cp{(int32_t)k_connect, max_distance};
+    rcheck(tr_roadmap_solve_tips_connect(rm_, &mv_->space, &prm, &cp, starts.data(), n ? requests[0].data() : nullptr, (int64_t)n, n_threads,
+                                         s.ik.controls.data(), s.ik.tip_positions.data(), s.ik.error.data(), s.ik.neighbor_vertex.data(),
+                                         s.ik.ik_vertex.data(), s.ik.outcome.data(), s.ik.last_valid_t.data(), s.roadmap.status.data(),
+                                         s.roadmap.cost.data(), off.data(), &s.roadmap.stats));
+    rcheck(tr_roadmap_tip_connect_stats(rm_, s.ik.connect_stats.data()));
+    std::vector<int32_t> pv((size_t)off[n]);
+    rcheck(tr_roadmap_fetch_paths(rm_, pv.data(), (int64_t)pv.size()));
+    s.roadmap.paths.resize(n);
+    for (size_t q = 0; q < n; q++) s.roadmap.paths[q].assign(pv.begin() + off[q], pv.begin() + off[q + 1]);
+    return s;
+  }
+
   int64_t releaseSearchState() { int64_t b = 0; if (rm_) rcheck(tr_roadmap_release_search_state(rm_, &b)); return b; }
   /// CompoundStateSpace::distance with the weights of Problem.cpp:112-152 (the edge cost connectVertices stores, :2857-2861)
   double distance(const double *a, const double *b) const {

@@ -39,6 +39,8 @@ ABI_SYMBOLS = (
     "tr_fk_tips", "tr_fk_tips_dev", "tr_tip_jacobian", "tr_tip_jacobian_dev", "tr_ik_batch", "tr_ik_batch_dev",
     "tr_roadmap_set_tips", "tr_roadmap_nearest_tips", "tr_roadmap_nearest_tips_dev", "tr_roadmap_ik_batch", "tr_roadmap_solve_tips",
     "tr_roadmap_tip_query_profile",
+    "tr_roadmap_nearest_states", "tr_roadmap_nearest_states_dev", "tr_roadmap_ik_batch_connect", "tr_roadmap_solve_tips_connect",
+    "tr_roadmap_tip_connect_stats",
     "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev",
     "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
     "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
@@ -86,6 +88,10 @@ class TrEdgeLoads(C.Structure):
 
 class TrTipQueryParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("tolerance", C.c_double), ("ik", TrIkParams)]
+
+
+class TrTipConnectParams(C.Structure):
+    _fields_ = [("k_connect", C.c_int32), ("max_distance", C.c_double)]
 
 
 class TrRoadmapStats(C.Structure):
@@ -144,7 +150,7 @@ def _units():
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
-                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp"]
+                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp"]
     fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
                "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
@@ -382,6 +388,13 @@ def lib():
     L.tr_roadmap_solve_tips.argtypes = [vp, P(TrSpaceParams), tqp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, dp, i32p, dp, P(i64),
                                         P(TrRoadmapStats)]
     L.tr_roadmap_tip_query_profile.argtypes = [vp, dp]
+    tcp = P(TrTipConnectParams)
+    L.tr_roadmap_nearest_states.argtypes = [vp, dp, i64, C.c_int32, C.c_double, i32p, dp]
+    L.tr_roadmap_nearest_states_dev.argtypes = [vp, vp, i64, C.c_int32, C.c_double, vp, vp]
+    L.tr_roadmap_ik_batch_connect.argtypes = [vp, P(TrSpaceParams), tqp, tcp, dp, i64, dp, dp, dp, i32p, i32p, i32p, dp]
+    L.tr_roadmap_solve_tips_connect.argtypes = [vp, P(TrSpaceParams), tqp, tcp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, i32p, dp, i32p,
+                                                dp, P(i64), P(TrRoadmapStats)]
+    L.tr_roadmap_tip_connect_stats.argtypes = [vp, P(i64)]
     L.tr_profile_begin.argtypes = [vp]
     L.tr_profile_read.argtypes = [vp, P(i64), dp]
     L.tr_profile_end.argtypes = [vp]

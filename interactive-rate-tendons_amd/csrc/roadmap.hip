@@ -52,6 +52,7 @@
 #include "../../include/tendon_hip.h"
 #include "roadmap_kernel.hpp"
 #include "tipq_kernel.hpp"
+#include "stateq_kernel.hpp"
 #include "handback_feed.hpp"
 
 namespace {
@@ -205,6 +206,7 @@ struct tr_roadmap {
   struct DevTips {
     bool set = false;
     double *d_tips = nullptr, *d_states = nullptr;
+    double *d_soa = nullptr;             // the states coordinate by coordinate ([S][V]): what state_knn streams
     uint8_t *d_vstat = nullptr;          // the image of `vstat` the kernel filters by; sent again only when `vstat` differs from `vstat_sent`
     uint64_t *d_present = nullptr;       // bit v: vertex v has a tip
     std::vector<uint8_t> vstat_sent;
@@ -213,6 +215,7 @@ struct tr_roadmap {
     size_t arena_bytes = 0;
     double phase_ms[5] = {0, 0, 0, 0, 0};   // of the last call: nearest, IK, edges, select, solve
     int64_t st_ik_rounds = 0;
+    int64_t connect_stats[4] = {0, 0, 0, 0};   // of the last *_connect call (tr_roadmap_tip_connect_stats)
   } dt;
 };
 

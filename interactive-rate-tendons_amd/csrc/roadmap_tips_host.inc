@@ -5,12 +5,14 @@
 //   checkMotion(states[N], x, last_valid) on all of them -> tipq_interp + tr_fk_tips_dev -> tipq_select -> tr_roadmap_solve
 // with the roadmap's tips, states and validity bytes resident in HBM: nothing V-sized moves per call (the validity bytes are
 // sent again only after they changed on the host).  A result joins the roadmap through exactly one edge, to the neighbour IK
-// started from (:3242-3244, :3276-3287); the graph itself is not edited.
+// started from (:3242-3244, :3276-3287); the graph itself is not edited.  The accurate rule (RMAP_IK_ACCURATE: the *_connect entry
+// points) tries an edge from every state-space neighbour of the IK answer as well (:3237-3244): state_knn on the IK answers ->
+// tipq_pair_rows -> ONE last-valid edge check of all the pairs -> tipq_interp + tr_fk_tips_dev on the pairs -> tipq_select_pairs.
 namespace {
 
 void free_tips(tr_roadmap *r) {
   auto &d = r->dt;
-  void *p[] = {d.d_tips, d.d_states, d.d_vstat, d.d_present, d.arena};
+  void *p[] = {d.d_tips, d.d_states, d.d_soa, d.d_vstat, d.d_present, d.arena};
   for (void *q : p) if (q) dev_cache().release(q);
   d = tr_roadmap::DevTips{};
 }
@@ -54,15 +56,26 @@ struct TipBuffers {
   double *req, *d2, *part_d2, *starts, *goals, *x, *xtip, *err, *t, *g, *gtip, *o_controls, *o_tip, *o_err, *o_t;
   int32_t *nbr, *part_idx, *o_nbr, *o_outcome;
   uint8_t *ok;
-  void carve(TipArena &a, int64_t n, int k, int S, int slices, bool full) {
-    const size_t m = (size_t)n * (size_t)k;
+  // the accurate rule (kc > 0): the source table C (m x kc) and its slices, and per pair (m (kc + 1) of them) the source vertex and
+  // the two end rows; t / ok / g / gtip are per pair then
+  int32_t *cidx, *c_part_idx, *src, *o_ik;
+  double *c_part_d, *pa, *pb;
+  uint8_t *o_flags;
+  void carve(TipArena &a, int64_t n, int k, int S, int slices, bool full, int kc = 0, int c_slices = 1) {
+    const size_t m = (size_t)n * (size_t)k, mp = m * (size_t)(kc > 0 ? kc + 1 : 1);
     req = a.take<double>((size_t)n * 3); nbr = a.take<int32_t>(m); d2 = a.take<double>(m);
     part_idx = a.take<int32_t>(slices > 1 ? m * (size_t)slices : 1); part_d2 = a.take<double>(slices > 1 ? m * (size_t)slices : 1);
     if (!full) return;
     starts = a.take<double>(m * S); goals = a.take<double>(m * 3); x = a.take<double>(m * S); xtip = a.take<double>(m * 3);
-    err = a.take<double>(m); t = a.take<double>(m); ok = a.take<uint8_t>(m); g = a.take<double>(m * S); gtip = a.take<double>(m * 3);
+    err = a.take<double>(m); t = a.take<double>(mp); ok = a.take<uint8_t>(mp); g = a.take<double>(mp * S); gtip = a.take<double>(mp * 3);
     o_controls = a.take<double>((size_t)n * S); o_tip = a.take<double>((size_t)n * 3); o_err = a.take<double>((size_t)n);
     o_t = a.take<double>((size_t)n); o_nbr = a.take<int32_t>((size_t)n); o_outcome = a.take<int32_t>((size_t)n);
+    if (kc <= 0) return;
+    const size_t mc = m * (size_t)kc;
+    cidx = a.take<int32_t>(mc);
+    c_part_idx = a.take<int32_t>(c_slices > 1 ? mc * (size_t)c_slices : 1); c_part_d = a.take<double>(c_slices > 1 ? mc * (size_t)c_slices : 1);
+    src = a.take<int32_t>(mp); pa = a.take<double>(mp * S); pb = a.take<double>(mp * S);
+    o_ik = a.take<int32_t>((size_t)n); o_flags = a.take<uint8_t>((size_t)n);
   }
 };
 
@@ -70,28 +83,63 @@ constexpr int kTipQ = 4, kTipG = 4;     // requests per wave, tiles in flight (t
 
 // Slices of the tip array: a batch that fills the device with request groups streams it whole; a handful of requests cuts it so
 // that ~1024 waves share the work (one wave alone would take V / 256 dependent rounds of loads).
-int tip_slices(int64_t n, int64_t V) {
-  const int64_t groups = (n + kTipQ - 1) / kTipQ, tiles = (V + 63) / 64;
-  const int64_t by_work = std::max<int64_t>(1, tiles / (2 * kTipG));
+int knn_slices(int64_t n, int64_t V, int Q, int G) {
+  const int64_t groups = (n + Q - 1) / Q, tiles = (V + 63) / 64;
+  const int64_t by_work = std::max<int64_t>(1, tiles / (2 * G));
   return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, by_work), 1024 / groups));
 }
 
-int tip_buffers(tr_roadmap *r, int64_t n, int k, bool full, TipBuffers &b, int &slices) {
+int tip_slices(int64_t n, int64_t V) { return knn_slices(n, V, kTipQ, kTipG); }
+// ... and of the vertex array for state_knn, whose Q and G follow the state size
+int state_slices(const tr_roadmap *r, int64_t n) { return knn_slices(n, r->V, trk::stateq_q(r->S), trk::stateq_g(r->S)); }
+
+// the call's arena holds at least `bytes`
+int tip_arena(tr_roadmap *r, size_t bytes) {
   auto &d = r->dt;
-  slices = tip_slices(n, r->V);
-  TipArena size;
-  TipBuffers dummy;
-  dummy.carve(size, n, k, r->S, slices, full);
-  if (size.used > d.arena_bytes) {
+  if (bytes > d.arena_bytes) {
     if (d.arena) dev_cache().release(d.arena);
     d.arena = nullptr; d.arena_bytes = 0;
-    const size_t want = size.used + size.used / 2;
+    const size_t want = bytes + bytes / 2;
     RM_HIP(r, dev_cache().alloc(tr_device(r->ctx), (void **)&d.arena, want));
     d.arena_bytes = want;
   }
+  return TR_OK;
+}
+
+int tip_buffers(tr_roadmap *r, int64_t n, int k, bool full, TipBuffers &b, int &slices, int kc = 0, int *c_slices = nullptr) {
+  slices = tip_slices(n, r->V);
+  const int cs = kc > 0 ? state_slices(r, n * k) : 1;
+  if (c_slices) *c_slices = cs;
+  TipArena size;
+  TipBuffers dummy;
+  dummy.carve(size, n, k, r->S, slices, full, kc, cs);
+  if (const int rc = tip_arena(r, size.used)) return rc;
   TipArena a;
-  a.base = d.arena;
-  b.carve(a, n, k, r->S, slices, full);
+  a.base = r->dt.arena;
+  b.carve(a, n, k, r->S, slices, full, kc, cs);
+  return TR_OK;
+}
+
+// the arrays of tr_roadmap_nearest_states, from the same arena
+struct StateBuffers {
+  double *qry, *dist, *part_d;
+  int32_t *idx, *part_idx;
+  void carve(TipArena &a, int64_t n, int k, int S, int slices) {
+    const size_t m = (size_t)n * (size_t)k;
+    qry = a.take<double>((size_t)n * S); idx = a.take<int32_t>(m); dist = a.take<double>(m);
+    part_idx = a.take<int32_t>(slices > 1 ? m * (size_t)slices : 1); part_d = a.take<double>(slices > 1 ? m * (size_t)slices : 1);
+  }
+};
+
+int state_buffers(tr_roadmap *r, int64_t n, int k, StateBuffers &b, int &slices) {
+  slices = state_slices(r, n);
+  TipArena size;
+  StateBuffers dummy;
+  dummy.carve(size, n, k, r->S, slices);
+  if (const int rc = tip_arena(r, size.used)) return rc;
+  TipArena a;
+  a.base = r->dt.arena;
+  b.carve(a, n, k, r->S, slices);
   return TR_OK;
 }
 
@@ -112,6 +160,36 @@ int launch_nearest(tr_roadmap *r, const double *d_req, int64_t n, int k, int sli
   hipLaunchKernelGGL(trk::tip_knn_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, nullptr, (const int32_t *)b.part_idx,
                      (const double *)b.part_d2, n, slices, k, d_nbr, d_d2);
   RM_HIP(r, hipGetLastError());
+  return TR_OK;
+}
+
+// state_knn (+ tip_knn_merge) on the null stream: d_qry n x S -> d_idx n x k, d_dist n x k (may be null); part_*: the slices' lists
+int launch_nearest_states(tr_roadmap *r, const double *d_qry, int64_t n, int k, double max_distance, int slices, int32_t *part_idx,
+                          double *part_d, int32_t *d_idx, double *d_dist) {
+  auto &d = r->dt;
+  const int Q = trk::stateq_q(r->S);
+  const int64_t groups = (n + Q - 1) / Q;
+  const dim3 grid((unsigned)((groups + 3) / 4), (unsigned)slices);
+  int32_t *oi = slices > 1 ? part_idx : d_idx;
+  double *od = slices > 1 ? part_d : d_dist;
+  const int variant = (r->rot ? 1 : 0) | (r->ret ? 2 : 0);
+#define TRK_SKNN(NT, R, T) do { constexpr int SS_ = NT + (R ? 1 : 0) + (T ? 1 : 0); \
+    hipLaunchKernelGGL((trk::state_knn<NT, R, T, trk::stateq_q(SS_), trk::stateq_g(SS_)>), grid, dim3(256), 0, nullptr, (const double *)d.d_soa, \
+                       (const uint8_t *)d.d_vstat, r->V, d_qry, n, k, r->w_rot, r->w_ret, max_distance, oi, od); } while (0)
+#define TRK_SCASE(NT) case NT: if (variant == 0) TRK_SKNN(NT, false, false); else if (variant == 1) TRK_SKNN(NT, true, false); \
+                               else if (variant == 2) TRK_SKNN(NT, false, true); else TRK_SKNN(NT, true, true); break;
+  switch (r->NT) {
+    TRK_SCASE(1) TRK_SCASE(2) TRK_SCASE(3) TRK_SCASE(4) TRK_SCASE(5) TRK_SCASE(6) TRK_SCASE(7) TRK_SCASE(8)
+    default: return rfail(r, TR_ERR_UNSUPPORTED, "nearest states: 1 .. 8 tendons");
+  }
+#undef TRK_SCASE
+#undef TRK_SKNN
+  RM_HIP(r, hipGetLastError());
+  if (slices > 1) {
+    hipLaunchKernelGGL(trk::tip_knn_merge, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, nullptr, (const int32_t *)part_idx, (const double *)part_d, n,
+                       slices, k, d_idx, d_dist);
+    RM_HIP(r, hipGetLastError());
+  }
   return TR_OK;
 }
 
@@ -137,9 +215,12 @@ int fk_tips_chunked(tr_roadmap *r, const double *d_states, int64_t n, double *d_
 
 unsigned tipq_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// Rules 1 - 5 behind the lock; every output may be null.
-int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const double *requests, int64_t n,
-                     double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t) {
+// Rules 1 - 5 behind the lock, for both connection rules; every output may be null.  connect null or k_connect 0: every candidate
+// slot has ONE source, the vertex IK started from (rules 3 - 5; ik_vertex = neighbor_vertex); otherwise the k_connect state-space
+// neighbours of its IK answer and that vertex (rules 3' - 5').  count_stats: this is a *_connect call, dt.connect_stats follows it.
+int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                     bool count_stats, const double *requests, int64_t n, double *controls, double *tips, double *error,
+                     int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t) {
   const tr_tip_query_params def{5, 1e-4, tr_ik_params{100, 0.1, 1e-9, 1e-4, 1e-4, 1e-6}};      // roadmapIk's defaults and what it hands to IK
   const tr_tip_query_params &p = params ? *params : def;
   const tr_space_params spd{0.02, 0.01, 0.0001};                                                // Problem.h:59-62
@@ -149,18 +230,24 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   auto &d = r->dt;
   for (double &x : d.phase_ms) x = 0;
   d.st_ik_rounds = 0;
+  if (count_stats) for (int64_t &x : d.connect_stats) x = 0;
+  const int kc = connect ? connect->k_connect : 0;
+  if (kc < 0 || kc > TRK_TIPQ_MAX_K) return rfail(r, TR_ERR_INVALID_ARG, "bad argument (k_connect: 0 .. 64)");
+  if (kc > 0 && !(connect->max_distance >= 0)) return rfail(r, TR_ERR_INVALID_ARG, "max_distance must be >= 0 (INFINITY: no bound)");
+  const int P = kc > 0 ? kc + 1 : 1;                                    // sources per candidate slot
+  if (n * (int64_t)p.k * P > ((int64_t)1 << 28)) return rfail(r, TR_ERR_INVALID_ARG, "too many pairs in one call (n k (k_connect + 1) <= 2^28)");
   if (n == 0) return TR_OK;
   if (!requests) return rfail(r, TR_ERR_INVALID_ARG, "null requests");
   if (!(p.tolerance >= 0)) return rfail(r, TR_ERR_INVALID_ARG, "tolerance must be >= 0");
   const int k = p.k, S = r->S;
-  const int64_t m = n * k;
+  const int64_t m = n * k, mp = m * P;
   auto t0 = Clock::now();
   auto lap = [&](int phase) { const auto t1 = Clock::now(); d.phase_ms[phase] += ms_between(t0, t1); t0 = t1; };
   // 1. neighbours
   if ((rc = tips_validity(r))) return rc;
   TipBuffers b;
-  int slices = 1;
-  if ((rc = tip_buffers(r, n, k, true, b, slices))) return rc;
+  int slices = 1, c_slices = 1;
+  if ((rc = tip_buffers(r, n, k, true, b, slices, kc, &c_slices))) return rc;
   RM_HIP(r, hipMemcpyAsync(b.req, requests, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, nullptr));
   if ((rc = launch_nearest(r, b.req, n, k, slices, b, b.nbr, nullptr))) return rc;
   // 2. IK from every neighbour, one batch
@@ -176,18 +263,32 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   std::vector<double> x((size_t)m * S);
   RM_HIP(r, hipMemcpy(x.data(), b.x, x.size() * sizeof(double), hipMemcpyDeviceToHost));
   lap(1);
+  // the sources of every slot (pair p = slot P + j): the slot's neighbour alone, or (rule 3') the state-space neighbours of x_i first
+  const int32_t *src = nbr.data();
+  const double *d_a = b.starts, *d_b = b.x;
+  std::vector<int32_t> pair_src;
+  if (kc > 0) {
+    if ((rc = launch_nearest_states(r, b.x, m, kc, connect->max_distance, c_slices, b.c_part_idx, b.c_part_d, b.cidx, nullptr))) return rc;
+    hipLaunchKernelGGL(trk::tipq_pair_rows, dim3(tipq_grid(mp)), dim3(256), 0, nullptr, (const double *)d.d_states, S, (const int32_t *)b.nbr,
+                       (const int32_t *)b.cidx, (const double *)b.x, m, kc, b.src, b.pa, b.pb);
+    RM_HIP(r, hipGetLastError());
+    pair_src.resize((size_t)mp);
+    RM_HIP(r, hipMemcpy(pair_src.data(), b.src, (size_t)mp * sizeof(int32_t), hipMemcpyDeviceToHost));
+    src = pair_src.data(); d_a = b.pa; d_b = b.pb;
+    lap(0);                                                              // (the source search counts as `nearest`)
+  }
   std::vector<int64_t> live;
-  live.reserve((size_t)m);
-  for (int64_t s = 0; s < m; s++) if (nbr[(size_t)s] >= 0) live.push_back(s);
+  live.reserve((size_t)mp);
+  for (int64_t s = 0; s < mp; s++) if (src[(size_t)s] >= 0) live.push_back(s);
   const int64_t ml = (int64_t)live.size();
-  std::vector<uint8_t> ok((size_t)m, 0);
-  std::vector<double> t((size_t)m, 0.0);
+  std::vector<uint8_t> ok((size_t)mp, 0);
+  std::vector<double> t((size_t)mp, 0.0);
   if (ml > 0) {
     std::vector<double> ea((size_t)ml * S), eb((size_t)ml * S), et((size_t)ml);
     std::vector<uint64_t> bits((size_t)(ml + 63) / 64, 0);
     for (int64_t i = 0; i < ml; i++) {
-      std::memcpy(&ea[(size_t)i * S], &r->states[(size_t)nbr[(size_t)live[(size_t)i]] * S], (size_t)S * sizeof(double));
-      std::memcpy(&eb[(size_t)i * S], &x[(size_t)live[(size_t)i] * S], (size_t)S * sizeof(double));
+      std::memcpy(&ea[(size_t)i * S], &r->states[(size_t)src[(size_t)live[(size_t)i]] * S], (size_t)S * sizeof(double));
+      std::memcpy(&eb[(size_t)i * S], &x[(size_t)(live[(size_t)i] / P) * S], (size_t)S * sizeof(double));
     }
     if ((rc = tr_validate_edges_last_valid(r->ctx, &space, ea.data(), eb.data(), ml, bits.data(), et.data(), nullptr))) return rfail(r, rc, tr_last_error(r->ctx));
     for (int64_t i = 0; i < ml; i++) {
@@ -195,28 +296,55 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
       t[(size_t)live[(size_t)i]] = et[(size_t)i];
     }
   }
-  RM_HIP(r, hipMemcpyAsync(b.ok, ok.data(), (size_t)m, hipMemcpyHostToDevice, nullptr));
-  RM_HIP(r, hipMemcpyAsync(b.t, t.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, nullptr));
+  RM_HIP(r, hipMemcpyAsync(b.ok, ok.data(), (size_t)mp, hipMemcpyHostToDevice, nullptr));
+  RM_HIP(r, hipMemcpyAsync(b.t, t.data(), (size_t)mp * sizeof(double), hipMemcpyHostToDevice, nullptr));
   lap(2);
-  // 4 - 5. the last valid state of every candidate, its tip, and the choice
-  hipLaunchKernelGGL(trk::tipq_interp, dim3(tipq_grid(m)), dim3(256), 0, nullptr, (const double *)b.starts, (const double *)b.x, (const double *)b.t, m, S,
-                     r->rot ? r->NT : -1, b.g);
+  // 4 - 5. the last valid state of every pair, its tip, and the choice
+  hipLaunchKernelGGL(trk::tipq_interp, dim3(tipq_grid(mp)), dim3(256), 0, nullptr, d_a, d_b, (const double *)b.t, mp, S, r->rot ? r->NT : -1, b.g);
   RM_HIP(r, hipGetLastError());
-  if ((rc = fk_tips_chunked(r, b.g, m, b.gtip))) return rc;
-  hipLaunchKernelGGL(trk::tipq_select, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, S, p.tolerance,
-                     (const double *)b.x, (const double *)b.xtip, (const double *)b.err, (const uint8_t *)b.ok, (const double *)b.t, (const double *)b.g,
-                     (const double *)b.gtip, b.o_controls, b.o_tip, b.o_err, b.o_nbr, b.o_outcome, b.o_t);
+  if ((rc = fk_tips_chunked(r, b.g, mp, b.gtip))) return rc;
+  if (kc > 0)
+    hipLaunchKernelGGL(trk::tipq_select_pairs, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, P, S,
+                       p.tolerance, (const int32_t *)b.src, (const double *)b.x, (const double *)b.xtip, (const double *)b.err, (const uint8_t *)b.ok,
+                       (const double *)b.t, (const double *)b.g, (const double *)b.gtip, b.o_controls, b.o_tip, b.o_err, b.o_nbr, b.o_ik,
+                       b.o_outcome, b.o_t, b.o_flags);
+  else
+    hipLaunchKernelGGL(trk::tipq_select, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, S, p.tolerance,
+                       (const double *)b.x, (const double *)b.xtip, (const double *)b.err, (const uint8_t *)b.ok, (const double *)b.t, (const double *)b.g,
+                       (const double *)b.gtip, b.o_controls, b.o_tip, b.o_err, b.o_nbr, b.o_outcome, b.o_t);
   RM_HIP(r, hipGetLastError());
   if (controls) RM_HIP(r, hipMemcpyAsync(controls, b.o_controls, (size_t)n * S * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (tips) RM_HIP(r, hipMemcpyAsync(tips, b.o_tip, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (error) RM_HIP(r, hipMemcpyAsync(error, b.o_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (neighbor_vertex) RM_HIP(r, hipMemcpyAsync(neighbor_vertex, b.o_nbr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (ik_vertex) RM_HIP(r, hipMemcpyAsync(ik_vertex, kc > 0 ? b.o_ik : b.o_nbr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
   if (outcome) RM_HIP(r, hipMemcpyAsync(outcome, b.o_outcome, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
   if (last_valid_t) RM_HIP(r, hipMemcpyAsync(last_valid_t, b.o_t, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   RM_HIP(r, hipStreamSynchronize(nullptr));
+  if (count_stats) {
+    // [0] pairs checked, [1] REACHED, [2] connection vertex != IK vertex, [3] REACHED where the one-edge rule is not
+    d.connect_stats[0] = ml;
+    if (kc > 0) {
+      std::vector<uint8_t> fl((size_t)n);
+      RM_HIP(r, hipMemcpy(fl.data(), b.o_flags, (size_t)n, hipMemcpyDeviceToHost));
+      for (const uint8_t f : fl) {
+        d.connect_stats[1] += (f & TRK_TIPQ_FLAG_REACHED) != 0; d.connect_stats[2] += (f & TRK_TIPQ_FLAG_MOVED) != 0;
+        d.connect_stats[3] += (f & TRK_TIPQ_FLAG_GAINED) != 0;
+      }
+    } else {
+      std::vector<int32_t> oc((size_t)n);
+      RM_HIP(r, hipMemcpy(oc.data(), b.o_outcome, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+      for (const int32_t o : oc) d.connect_stats[1] += o == TR_TIPQ_REACHED;
+    }
+  }
   lap(3);
   return TR_OK;
 }
+
+int solve_tips_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                      bool count_stats, const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls,
+                      double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
+                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats);
 
 }  // namespace
 
@@ -233,6 +361,7 @@ int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *prese
   const size_t nw = (size_t)V / 64 + 1;
   RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_tips, std::max<size_t>(1, (size_t)V * 3) * sizeof(double)));
   RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_states, std::max<size_t>(1, (size_t)V * r->S) * sizeof(double)));
+  RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_soa, std::max<size_t>(1, (size_t)V * r->S) * sizeof(double)));
   RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_vstat, std::max<size_t>(1, (size_t)V)));
   RM_HIP(r, dev_cache().alloc(dev, (void **)&d.d_present, nw * sizeof(uint64_t)));
   d.present.assign(nw, 0);
@@ -240,6 +369,11 @@ int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *prese
     if (!present_bits || ((present_bits[v >> 6] >> (v & 63)) & 1)) d.present[(size_t)v >> 6] |= (uint64_t)1 << (v & 63);
   if (V > 0) {
     RM_HIP(r, hipMemcpy(d.d_states, r->states.data(), (size_t)V * r->S * sizeof(double), hipMemcpyHostToDevice));
+    // ... and coordinate by coordinate ([S][V]): state_knn's tiles read 64 consecutive doubles per coordinate
+    std::vector<double> soa((size_t)V * r->S);
+    for (int64_t v = 0; v < V; v++)
+      for (int c = 0; c < r->S; c++) soa[(size_t)c * V + v] = r->states[(size_t)v * r->S + c];
+    RM_HIP(r, hipMemcpy(d.d_soa, soa.data(), soa.size() * sizeof(double), hipMemcpyHostToDevice));
     if (tips) {
       RM_HIP(r, hipMemcpy(d.d_tips, tips, (size_t)V * 3 * sizeof(double), hipMemcpyHostToDevice));
     } else {
@@ -290,11 +424,66 @@ int tr_roadmap_nearest_tips(tr_roadmap *r, const double *requests, int64_t n, in
   return TR_OK;
 }
 
+int tr_roadmap_nearest_states_dev(tr_roadmap *r, const double *d_queries, int64_t n, int32_t k, double max_distance, int32_t *d_vertices,
+                                  double *d_dist) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  int rc;
+  if ((rc = tips_ready(r, n, k))) return rc;
+  if (!(max_distance >= 0)) return rfail(r, TR_ERR_INVALID_ARG, "max_distance must be >= 0 (INFINITY: no bound)");
+  if (n == 0) return TR_OK;
+  if (!d_queries || !d_vertices) return rfail(r, TR_ERR_INVALID_ARG, "null device pointer");
+  RM_HIP(r, hipDeviceSynchronize());                        // (the queries may have been written on any stream)
+  if ((rc = tips_validity(r))) return rc;
+  StateBuffers b;
+  int slices = 1;
+  if ((rc = state_buffers(r, n, k, b, slices))) return rc;
+  // (the slices' lists carry their distances whether or not the caller wants them: the merge orders by them)
+  if ((rc = launch_nearest_states(r, d_queries, n, k, max_distance, slices, b.part_idx, b.part_d, d_vertices, d_dist))) return rc;
+  RM_HIP(r, hipStreamSynchronize(nullptr));
+  return TR_OK;
+}
+
+int tr_roadmap_nearest_states(tr_roadmap *r, const double *queries, int64_t n, int32_t k, double max_distance, int32_t *vertices, double *dist) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  int rc;
+  if ((rc = tips_ready(r, n, k))) return rc;
+  if (!(max_distance >= 0)) return rfail(r, TR_ERR_INVALID_ARG, "max_distance must be >= 0 (INFINITY: no bound)");
+  if (n == 0) return TR_OK;
+  if (!queries || !vertices) return rfail(r, TR_ERR_INVALID_ARG, "null argument");
+  if ((rc = tips_validity(r))) return rc;
+  StateBuffers b;
+  int slices = 1;
+  if ((rc = state_buffers(r, n, k, b, slices))) return rc;
+  RM_HIP(r, hipMemcpyAsync(b.qry, queries, (size_t)n * r->S * sizeof(double), hipMemcpyHostToDevice, nullptr));
+  if ((rc = launch_nearest_states(r, b.qry, n, k, max_distance, slices, b.part_idx, b.part_d, b.idx, b.dist))) return rc;
+  RM_HIP(r, hipMemcpyAsync(vertices, b.idx, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (dist) RM_HIP(r, hipMemcpyAsync(dist, b.dist, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+  RM_HIP(r, hipStreamSynchronize(nullptr));
+  return TR_OK;
+}
+
 int tr_roadmap_ik_batch(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const double *requests, int64_t n,
                         double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *outcome, double *last_valid_t) {
   if (!r) return TR_ERR_INVALID_ARG;
   RmLock lock_(r);
-  return tip_query_locked(r, sp, params, requests, n, controls, tips, error, neighbor_vertex, outcome, last_valid_t);
+  return tip_query_locked(r, sp, params, nullptr, false, requests, n, controls, tips, error, neighbor_vertex, nullptr, outcome, last_valid_t);
+}
+
+int tr_roadmap_ik_batch_connect(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                const double *requests, int64_t n, double *controls, double *tips, double *error, int32_t *neighbor_vertex,
+                                int32_t *ik_vertex, int32_t *outcome, double *last_valid_t) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  return tip_query_locked(r, sp, params, connect, true, requests, n, controls, tips, error, neighbor_vertex, ik_vertex, outcome, last_valid_t);
+}
+
+int tr_roadmap_tip_connect_stats(tr_roadmap *r, int64_t out[4]) {
+  if (!r || !out) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  for (int i = 0; i < 4; i++) out[i] = r->dt.connect_stats[i];
+  return TR_OK;
 }
 
 int tr_roadmap_solve_tips(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const int32_t *starts,
@@ -303,6 +492,29 @@ int tr_roadmap_solve_tips(tr_roadmap *r, const tr_space_params *sp, const tr_tip
                           int64_t *path_offsets, tr_roadmap_stats *stats) {
   if (!r) return TR_ERR_INVALID_ARG;
   RmLock lock_(r);
+  return solve_tips_locked(r, sp, params, nullptr, false, starts, requests, n, n_threads, controls, tips, error, neighbor_vertex, nullptr, outcome,
+                           last_valid_t, status, cost, path_offsets, stats);
+}
+
+int tr_roadmap_solve_tips_connect(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                  const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls, double *tips,
+                                  double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
+                                  int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  return solve_tips_locked(r, sp, params, connect, true, starts, requests, n, n_threads, controls, tips, error, neighbor_vertex, ik_vertex, outcome,
+                           last_valid_t, status, cost, path_offsets, stats);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Rules 1 - 6 behind the lock, for both connection rules
+int solve_tips_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                      bool count_stats, const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls,
+                      double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
+                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats) {
   if (n < 0 || (n > 0 && (!starts || !requests || !status || !path_offsets))) return rfail(r, TR_ERR_INVALID_ARG, "bad argument");
   reset_last_solve(r, n);
   if (path_offsets) path_offsets[0] = 0;
@@ -316,7 +528,8 @@ int tr_roadmap_solve_tips(tr_roadmap *r, const tr_space_params *sp, const tr_tip
   if (!neighbor_vertex) { own_nbr.resize((size_t)n); neighbor_vertex = own_nbr.data(); }
   if (!outcome) { own_outcome.resize((size_t)n); outcome = own_outcome.data(); }
   int rc;
-  if ((rc = tip_query_locked(r, sp, params, requests, n, controls, tips, error, neighbor_vertex, outcome, last_valid_t))) return rc;
+  if ((rc = tip_query_locked(r, sp, params, connect, count_stats, requests, n, controls, tips, error, neighbor_vertex, ik_vertex, outcome, last_valid_t)))
+    return rc;
   if (n == 0) return TR_OK;
   // rule 6: the roadmap query to the connection vertex; a request without a neighbour has no goal
   const auto t0 = Clock::now();
@@ -349,6 +562,10 @@ int tr_roadmap_solve_tips(tr_roadmap *r, const tr_space_params *sp, const tr_tip
   r->dt.phase_ms[4] = ms_between(t0, Clock::now());
   return TR_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int tr_roadmap_tip_query_profile(tr_roadmap *r, double out[6]) {
   if (!r || !out) return TR_ERR_INVALID_ARG;

@@ -597,6 +597,38 @@ class VoxelCachedLazyPRM:
         pd = eng._check_dev(d_dist2, torch.float64, n * k, "d_dist2") if d_dist2 is not None else None
         self._check(self.lib.tr_roadmap_nearest_tips_dev(self._rm, pr, int(n), int(k), pv, pd))
 
+    def nearest_states(self, queries, k, max_distance=np.inf):
+        """Per query STATE (any state, not only a vertex) the k roadmap vertices nearest in state space (CompoundStateSpace::distance,
+        Engine.knn's arithmetic) among the vertices valid in the current grid, in the order (dist, vertex index); entries farther
+        than max_distance are dropped -> (vertices (n, k) int32, -1 padded; dist (n, k), +inf where padded).  Needs set_tips."""
+        C = self._C
+        S = self.engine.state_size
+        q = np.ascontiguousarray(queries, dtype=np.float64)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != S:
+            raise self._L.InvalidArgument("queries must be (n, state_size)")
+        n = len(q)
+        idx = np.full((n, max(int(k), 0)), -1, dtype=np.int32)
+        dist = np.full((n, max(int(k), 0)), np.inf)
+        self._check(self.lib.tr_roadmap_nearest_states(self._rm, q.ctypes.data_as(C.POINTER(C.c_double)), n, int(k), float(max_distance),
+                                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_double))))
+        return idx, dist
+
+    def nearest_states_dev(self, d_queries, n, k, d_vertices, d_dist=None, max_distance=np.inf):
+        """nearest_states on device tensors of the checker's GPU (float64 (n, S) -> int32 (n, k) [, float64 (n, k)])."""
+        import torch
+        eng = self.engine
+        pq = eng._check_dev(d_queries, torch.float64, eng.state_size * n, "d_queries")
+        pv = eng._check_dev(d_vertices, torch.int32, n * k, "d_vertices")
+        pd = eng._check_dev(d_dist, torch.float64, n * k, "d_dist") if d_dist is not None else None
+        self._check(self.lib.tr_roadmap_nearest_states_dev(self._rm, pq, int(n), int(k), float(max_distance), pv, pd))
+
+    def _connect_stats(self):
+        o = (self._C.c_int64 * 4)()
+        self._check(self.lib.tr_roadmap_tip_connect_stats(self._rm, o))
+        return dict(pairs_checked=int(o[0]), reached=int(o[1]), moved=int(o[2]), gained=int(o[3]))
+
     def _refuse_loaded(self, what):
         """Tip IK under load does not exist: a roadmap whose checker has loads (set_loads) would be joined to goal states found on
         unloaded shapes."""
@@ -628,13 +660,17 @@ class VoxelCachedLazyPRM:
         self._check(self.lib.tr_roadmap_tip_query_profile(self._rm, o))
         return dict(nearest_ms=o[0], ik_ms=o[1], edges_ms=o[2], select_ms=o[3], solve_ms=o[4], ik_rounds=int(o[5]))
 
-    def roadmap_ik_batch(self, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None):
+    def roadmap_ik_batch(self, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None, connect_k=0, connect_max_distance=np.inf):
         """roadmapIk (motion-planning/VoxelCachedLazyPRM.cpp:3095-3577) for a batch of tip requests in one call: per request IK
         from the k vertices with the nearest tips, all n k problems in one device batch; the first solution in neighbour order
         within tolerance whose edge from its neighbour is valid is REACHED, otherwise the last valid state towards each solution
         whose tip is nearest the request is CLOSEST (the rule in include/tendon_hip.h).  -> dict(controls (n, S), tip (n, 3),
         error, neighbor_vertex, outcome (TR_TIPQ_*), last_valid_t).  motion_validator: its state-space resolutions (None: the
-        defaults of Problem); ik: overrides of the IK arguments."""
+        defaults of Problem); ik: overrides of the IK arguments.
+        connect_k > 0 is RMAP_IK_ACCURATE (rules 3' - 5' in include/tendon_hip.h): every IK answer is also tried from its connect_k
+        nearest vertices in state space (no farther than connect_max_distance), so neighbor_vertex -- the connection vertex --
+        need not be the vertex IK started from; the result then also carries ik_vertex (that vertex) and connect_stats
+        (pairs_checked, reached, moved: connection vertex != ik_vertex, gained: reached where the one-edge rule is not)."""
         C = self._C
         self._refuse_loaded("roadmap_ik_batch")
         r = self._requests(requests)
@@ -642,15 +678,26 @@ class VoxelCachedLazyPRM:
         prm, sp = self._tip_params(k, tolerance, ik, motion_validator)
         o = self._tip_outputs(n)
         dp, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        if connect_k != 0:
+            cp = self._L.TrTipConnectParams(int(connect_k), float(connect_max_distance))
+            o["ik_vertex"] = np.empty(n, dtype=np.int32)
+            self._check(self.lib.tr_roadmap_ik_batch_connect(
+                self._rm, C.byref(sp), C.byref(prm), C.byref(cp), r.ctypes.data_as(dp), n, o["controls"].ctypes.data_as(dp),
+                o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32),
+                o["ik_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32), o["last_valid_t"].ctypes.data_as(dp)))
+            o["connect_stats"] = self._connect_stats()
+            return o
         self._check(self.lib.tr_roadmap_ik_batch(self._rm, C.byref(sp), C.byref(prm), r.ctypes.data_as(dp), n, o["controls"].ctypes.data_as(dp),
                                                  o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32),
                                                  o["outcome"].ctypes.data_as(i32), o["last_valid_t"].ctypes.data_as(dp)))
         return o
 
-    def solve_to_tips(self, starts, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0):
+    def solve_to_tips(self, starts, requests, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0, connect_k=0,
+                      connect_max_distance=np.inf):
         """roadmap_ik_batch, then solveWithRoadmap from starts[q] to request q's connection vertex: the fields of both, with
         cost = roadmap cost + state-space distance from the connection vertex to the goal state (`controls`), which follows the
-        last vertex of paths[q].  A request without a neighbour ends TR_QUERY_INVALID_GOAL."""
+        last vertex of paths[q].  A request without a neighbour ends TR_QUERY_INVALID_GOAL.  connect_k, connect_max_distance: as
+        in roadmap_ik_batch."""
         C, L_ = self._C, self._L
         self._refuse_loaded("solve_to_tips")
         r = self._requests(requests)
@@ -663,11 +710,22 @@ class VoxelCachedLazyPRM:
         status, cost, off = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n + 1, dtype=np.int64)
         st = L_.TrRoadmapStats()
         dp, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        self._check(self.lib.tr_roadmap_solve_tips(
-            self._rm, C.byref(sp), C.byref(prm), s.ctypes.data_as(i32), r.ctypes.data_as(dp), n, int(n_threads), o["controls"].ctypes.data_as(dp),
-            o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32),
-            o["last_valid_t"].ctypes.data_as(dp), status.ctypes.data_as(i32), cost.ctypes.data_as(dp), off.ctypes.data_as(C.POINTER(C.c_int64)),
-            C.byref(st)))
+        if connect_k != 0:
+            cp = L_.TrTipConnectParams(int(connect_k), float(connect_max_distance))
+            o["ik_vertex"] = np.empty(n, dtype=np.int32)
+            self._check(self.lib.tr_roadmap_solve_tips_connect(
+                self._rm, C.byref(sp), C.byref(prm), C.byref(cp), s.ctypes.data_as(i32), r.ctypes.data_as(dp), n, int(n_threads),
+                o["controls"].ctypes.data_as(dp), o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp),
+                o["neighbor_vertex"].ctypes.data_as(i32), o["ik_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32),
+                o["last_valid_t"].ctypes.data_as(dp), status.ctypes.data_as(i32), cost.ctypes.data_as(dp),
+                off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(st)))
+            o["connect_stats"] = self._connect_stats()
+        else:
+            self._check(self.lib.tr_roadmap_solve_tips(
+                self._rm, C.byref(sp), C.byref(prm), s.ctypes.data_as(i32), r.ctypes.data_as(dp), n, int(n_threads), o["controls"].ctypes.data_as(dp),
+                o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp), o["neighbor_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32),
+                o["last_valid_t"].ctypes.data_as(dp), status.ctypes.data_as(i32), cost.ctypes.data_as(dp), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                C.byref(st)))
         pv = np.zeros(int(off[-1]), dtype=np.int32)
         self._check(self.lib.tr_roadmap_fetch_paths(self._rm, pv.ctypes.data_as(i32), len(pv)))
         self.stats = dict(rounds=st.rounds, items_checked=st.items_checked, astar_runs=st.astar_runs, expanded=st.expanded)
@@ -716,12 +774,14 @@ def interpolate_states(engine, a, b, t):
     return out
 
 
-def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0):
+def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0, connect_k=0,
+                 connect_max_distance=np.inf):
     """The loop of apps/roadmap_chained_plan.cpp:535-679 for a batch of chains: chain c starts at roadmap vertex
     start_vertex[c] and visits the tips waypoints[c, 0], waypoints[c, 1], ...; hop h of EVERY chain is one solve_to_tips call.
     A hop ends at an off-roadmap goal state joined to the roadmap by one edge, so the next hop starts at that state: it is
     prefixed with the reversed connecting edge (goal state -> its connection vertex) and that edge's distance, then follows the
-    roadmap from the connection vertex.  A chain stops at its first hop that is not solved.
+    roadmap from the connection vertex.  A chain stops at its first hop that is not solved.  connect_k, connect_max_distance: as in
+    roadmap_ik_batch (the connection vertex a hop ends at is then the accurate rule's).
     -> dict(hops: per hop the solve_to_tips result plus start_state (C, S), prefix_cost (C,), total_cost (C,), active (C,);
             cost (C,): the sum over the chain's solved hops; solved (C,): every hop solved)."""
     prm._refuse_loaded("chained_plan")
@@ -743,7 +803,8 @@ def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_valid
         idx = np.flatnonzero(active)
         res = dict(active=active.copy(), start_state=state.copy(), prefix_cost=np.zeros(C_), total_cost=np.full(C_, np.inf), chains=idx)
         if len(idx):
-            r = prm.solve_to_tips(at[idx], wp[idx, h], tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, n_threads=n_threads)
+            r = prm.solve_to_tips(at[idx], wp[idx, h], tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, n_threads=n_threads,
+                                  connect_k=connect_k, connect_max_distance=connect_max_distance)
             res.update(r)
             ok = r["status"] == L.TR_QUERY_SOLVED
             # the reversed connecting edge of the previous hop
