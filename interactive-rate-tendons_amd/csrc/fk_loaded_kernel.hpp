@@ -16,7 +16,8 @@
 //   shoot_finish       strains, |e|, counters and the converged flag of every problem
 // The distributed load is a constant vector per problem in the robot's base frame (gravity); the reference takes functions of
 // (t, p).  Robots with retraction are refused by the host (loaded_host.inc).  The LM iteration is this library's own (the scheme of
-// ik_lm_step without bounds), not levmar's code path; it is compiled without contraction.
+// ik_lm_step without bounds; the Cholesky solve and the mu / nu updates are lm_dense.hpp's, whose header lists what differs), not
+// levmar's code path; it is compiled without contraction.
 // The file has two halves: the per-problem kernels (included by tendon_hip.hip), and, under TRK_LOADED_WITH_INTEGRATOR, the kernels that
 // need the tendon count at compile time (fk_inst.hip, kind 6: one object per tendon count).
 #pragma once
@@ -154,13 +155,11 @@ __global__ __launch_bounds__(64) void shoot_lm_step(ShootParams prm, ShootState 
       jac_from_rows();
       grad();
       const double t = 2.0 * rho - 1.0;
-      const double sh = 1.0 - t * t * t;
-      mu *= (1.0 / 3.0) > sh ? (1.0 / 3.0) : sh;
+      mu *= lm_shrink(t * t * t);
       nu = 2.0;
       active = err2 > prm.eps3_sq && moving();
     } else {
-      mu *= nu;
-      nu *= 2.0;
+      lm_reject(mu, nu);
       active = shoot_finite(err2n) && shoot_finite(mu) && mu < 1e300;     // a non-finite residual ends the problem (levmar's reason 7)
     }
   }
@@ -187,37 +186,8 @@ __global__ __launch_bounds__(64) void shoot_lm_step(ShootParams prm, ShootState 
         A[a * (a + 1) / 2 + b] = s;
       }
     }
-    bool spd = true;
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-#pragma unroll
-      for (int b = 0; b <= a; b++) {
-        double s = A[a * (a + 1) / 2 + b];
-#pragma unroll
-        for (int k = 0; k < b; k++) s -= A[a * (a + 1) / 2 + k] * A[b * (b + 1) / 2 + k];
-        if (a == b) {
-          spd = spd && s > 0.0;
-          A[a * (a + 1) / 2 + a] = sqrt(s > 0.0 ? s : 1.0);
-        } else {
-          A[a * (a + 1) / 2 + b] = s / A[b * (b + 1) / 2 + b];
-        }
-      }
-    }
     double y[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      double s = g[a];
-#pragma unroll
-      for (int k = 0; k < a; k++) s -= A[a * (a + 1) / 2 + k] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
-#pragma unroll
-    for (int a = 5; a >= 0; a--) {
-      double s = y[a];
-#pragma unroll
-      for (int k = a + 1; k < 6; k++) s -= A[k * (k + 1) / 2 + a] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
+    const bool spd = chol_solve_packed<6>(A, g, y);
     double dd = 0.0, pp = 0.0;
 #pragma unroll
     for (int j = 0; j < 6; j++) { dd += y[j] * y[j]; pp += p[j] * p[j]; x[j] = p[j] + y[j]; }

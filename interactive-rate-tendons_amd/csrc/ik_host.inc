@@ -130,7 +130,7 @@ int ik_chunk_solve(tr_ctx *c, const trk::IkParams &prm, const double *d_init, in
   tr_ctx::IkDev &k = c->ik;
   const int S = prm.S, Q = 2 * S + 1;
   const trk::IkState st = ik_state(c);
-  hipLaunchKernelGGL(trk::ik_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st);
+  hipLaunchKernelGGL(trk::lm_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st.pn, st.des);
   HIP_TRY(c, hipGetLastError());
   int64_t active = m;
   int cur = 0, rc;
@@ -141,13 +141,8 @@ int ik_chunk_solve(tr_ctx *c, const trk::IkParams &prm, const double *d_init, in
     hipLaunchKernelGGL(trk::ik_expand, dim3(ik_grid(active * Q, 256)), dim3(256), 0, s, (const double *)k.pn, list, active, S, prm.delta, k.xs);
     HIP_TRY(c, hipGetLastError());
     if ((rc = ik_fk(c, active * Q, s))) return rc;
-    switch (S) {
-#define TRK_CASE(SS) case SS: hipLaunchKernelGGL((trk::ik_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, st, list, active, \
-                                                 (const double *)k.tips, (int)init, k.list[nxt], k.count.d + nxt); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8) TRK_CASE(9) TRK_CASE(10)
-#undef TRK_CASE
-      default: return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
-    }
+    TRK_FOR_STATE_SIZE(c, S, hipLaunchKernelGGL((trk::ik_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, st, list, active,
+                                                (const double *)k.tips, (int)init, k.list[nxt], k.count.d + nxt));
     HIP_TRY(c, hipGetLastError());
     if ((rc = k.count.read(nxt, s, active))) return rc;
     cur = nxt;
@@ -307,7 +302,7 @@ int tr_ik_batch(tr_ctx *c, const tr_ik_params *params, const double *initial_sta
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
     if ((rc = upload_rows(c, k.io_s, initial_states, S, off, m, S)) || (rc = upload_rows(c, k.io_3, des, des_ld, off, m, 3))) return rc;
-    // (io_s / io_3 are read by ik_init before ik_finish overwrites them with the results)
+    // (io_s / io_3 are read by lm_init before ik_finish overwrites them with the results)
     if ((rc = ik_run(c, prm, k.io_s, m, k.io_3, des_ld ? 3 : 0, k.io_s, k.io_3, k.io_e, k.io_i, k.io_c, nullptr, rounds))) return rc;
     if ((rc = download_rows(c, states_out, k.io_s, off, m, S)) || (rc = download_rows(c, tips_out, k.io_3, off, m, 3)) ||
         (rc = download_rows(c, error_out, k.io_e, off, m)) || (rc = download_rows(c, iters_out, k.io_i, off, m)) ||

@@ -11,25 +11,16 @@
 //   ik_lm_step   one lane per problem: f and J through tip_control's FK wrapper, gain ratio, accept / reject, the stop tests, the
 //                next damped step (S x S Cholesky in registers), the next trial point into the problem's row and the problem into
 //                the next active list
+// The step kernel's algebra and bookkeeping, the start kernel (lm_init) and the parameters (IkParams) are lm_dense.hpp's, shared
+// with the loaded IK.
 // The scheme is tip_control.inverse_kinematics_batch's (tip_control.py), which is the specification.  Everything here is
 // compiled without contraction, so f, J and the perturbed states are the bits numpy forms from the same tips.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#define TRK_IK_MAX_S 10      // TRK_MAX_TENDONS + rotation + retraction
+#include "lm_dense.hpp"
 
 namespace trk {
-
-struct IkParams {
-  int32_t S, max_iters;
-  int32_t rot_index;                 // state index of the rotation (-1: none); canonicalised by ik_finish
-  int32_t retraction;                // tip_control's FK wrapper applies to the last state entry
-  double L;                          // backbone length (the wrapper's threshold)
-  double delta;                      // finite_difference_delta
-  double mu_init, eps1, eps2_sq, eps3_sq;   // mu_init, |J^T e|_inf, |Dp|^2 (relative), |e|^2
-  double lo[TRK_IK_MAX_S], hi[TRK_IK_MAX_S];
-};
 
 // per-problem state, problem-indexed (one chunk of problems)
 struct IkState {
@@ -48,25 +39,11 @@ __device__ __forceinline__ double ik_step_size(double pj, double delta) {
   return a < delta ? delta : a;      // np.maximum(|1e-4 p|, delta) (a NaN stays NaN)
 }
 
-__device__ __forceinline__ double ik_clip(double x, double lo, double hi) {
-  const double v = x < lo ? lo : x;  // np.clip: minimum(maximum(x, lo), hi) (a NaN stays NaN)
-  return v > hi ? hi : v;
-}
-
 // tip_control's FK wrapper (tip_control.cpp:96-104): a retraction beyond L returns (0, 0, L - s_start)
 __device__ __forceinline__ void ik_wrap(const double *__restrict__ tip, double s, bool ret, double L, double o[3]) {
 #pragma clang fp contract(off)
   if (ret && s > L) { o[0] = 0.0; o[1] = 0.0; o[2] = L - s; }
   else { o[0] = tip[0]; o[1] = tip[1]; o[2] = tip[2]; }
-}
-
-// clipped start and goal of every problem of a chunk (des_ld = 0: one goal row for all)
-__global__ void ik_init(const double *__restrict__ init, int64_t n, const double *__restrict__ des, int64_t des_ld, IkParams prm, IkState st) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int S = prm.S;
-  for (int j = 0; j < S; j++) st.pn[i * S + j] = ik_clip(init[i * S + j], prm.lo[j], prm.hi[j]);
-  for (int k = 0; k < 3; k++) st.des[i * 3 + k] = des[i * des_ld + k];
 }
 
 // the 2S + 1 FK inputs of each of m points: rows list[r] of src (list null: row r)
@@ -142,22 +119,6 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
   double err2, mu, nu;
   int iters, calls;
   bool active, accepted;
-  // g = J^T e
-  auto grad = [&](double g[S]) {
-#pragma unroll
-    for (int j = 0; j < S; j++) g[j] = J[0 * S + j] * e[0] + J[1 * S + j] * e[1] + J[2 * S + j] * e[2];
-  };
-  // components of J^T e that can still move the state inside the box (tip_control.py: free_gradient) -> max |.| > eps1
-  auto moving = [&](const double g[S]) {
-    double mx = 0.0;
-#pragma unroll
-    for (int j = 0; j < S; j++) {
-      const bool blocked = (p[j] <= prm.lo[j] && g[j] < 0.0) || (p[j] >= prm.hi[j] && g[j] > 0.0);
-      const double a = blocked ? 0.0 : fabs(g[j]);
-      if (!(a <= mx)) mx = a;                       // a NaN wins, as in np.max
-    }
-    return mx > prm.eps1;
-  };
   double g[S];
   if (init) {
     accepted = true;
@@ -168,7 +129,7 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
 #pragma unroll
     for (int k = 0; k < 3; k++) { f[k] = fn[k]; e[k] = en[k]; }
     err2 = err2n;
-    grad(g);
+    lm_grad<S>(J, e, g);
     double dmax = 0.0;                              // mu = mu_init * max diag(J^T J), or mu_init when that is not positive
 #pragma unroll
     for (int j = 0; j < S; j++) {
@@ -180,7 +141,7 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
     nu = 2.0;
     iters = 0;
     calls = Q;
-    active = err2 > prm.eps3_sq && moving(g);
+    active = err2 > prm.eps3_sq && lm_moving<S>(p, g, prm);
   } else {
 #pragma unroll
     for (int j = 0; j < S; j++) p[j] = st.p[i * S + j];
@@ -189,12 +150,8 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
 #pragma unroll
     for (int k = 0; k < 3; k++) { f[k] = st.f[i * 3 + k]; e[k] = des[k] - f[k]; }
     err2 = st.err2[i]; mu = st.mu[i]; nu = st.nu[i]; iters = st.iters[i]; calls = st.fk_calls[i] + Q;
-    grad(g);
-    // gain ratio of the step dp = x - p against the model's predicted decrease dp . (mu dp + g)
-    double pred = 0.0;
-#pragma unroll
-    for (int j = 0; j < S; j++) { const double dp = x[j] - p[j]; pred += dp * (mu * dp + g[j]); }
-    const double rho = pred > 0.0 ? (err2 - err2n) / pred : -1.0;
+    lm_grad<S>(J, e, g);
+    const double rho = lm_gain_ratio<S>(x, p, g, mu, err2, err2n);
     accepted = rho > 0.0;
     if (accepted) {
 #pragma unroll
@@ -204,15 +161,13 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
 #pragma unroll
       for (int k = 0; k < 3; k++) { f[k] = fn[k]; e[k] = en[k]; }
       err2 = err2n;
-      grad(g);
+      lm_grad<S>(J, e, g);
       const double t = 2.0 * rho - 1.0;
-      const double sh = 1.0 - pow(t, 3.0);
-      mu *= (1.0 / 3.0) > sh ? (1.0 / 3.0) : sh;
+      mu *= lm_shrink(pow(t, 3.0));
       nu = 2.0;
-      active = err2 > prm.eps3_sq && moving(g);
+      active = err2 > prm.eps3_sq && lm_moving<S>(p, g, prm);
     } else {
-      mu *= nu;
-      nu *= 2.0;
+      lm_reject(mu, nu);
       active = isfinite(mu) && mu < 1e300;
     }
   }
@@ -234,37 +189,8 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
       for (int b = 0; b <= a; b++)
         A[a * (a + 1) / 2 + b] = J[0 * S + a] * J[0 * S + b] + J[1 * S + a] * J[1 * S + b] + J[2 * S + a] * J[2 * S + b] + (a == b ? mu : 0.0);
     }
-    bool spd = true;
-#pragma unroll
-    for (int a = 0; a < S; a++) {
-#pragma unroll
-      for (int b = 0; b <= a; b++) {
-        double s = A[a * (a + 1) / 2 + b];
-#pragma unroll
-        for (int k = 0; k < b; k++) s -= A[a * (a + 1) / 2 + k] * A[b * (b + 1) / 2 + k];
-        if (a == b) {
-          spd = spd && s > 0.0;
-          A[a * (a + 1) / 2 + a] = sqrt(s > 0.0 ? s : 1.0);
-        } else {
-          A[a * (a + 1) / 2 + b] = s / A[b * (b + 1) / 2 + b];
-        }
-      }
-    }
     double y[S];
-#pragma unroll
-    for (int a = 0; a < S; a++) {
-      double s = g[a];
-#pragma unroll
-      for (int k = 0; k < a; k++) s -= A[a * (a + 1) / 2 + k] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
-#pragma unroll
-    for (int a = S - 1; a >= 0; a--) {
-      double s = y[a];
-#pragma unroll
-      for (int k = a + 1; k < S; k++) s -= A[k * (k + 1) / 2 + a] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
+    const bool spd = chol_solve_packed<S>(A, g, y);
     // projected onto the box; the relative-step test on the step actually taken
     double dd = 0.0, pp = 0.0;
 #pragma unroll
@@ -290,24 +216,9 @@ __global__ __launch_bounds__(64) void ik_lm_step(IkParams prm, IkState st, const
 // results of a chunk: state (rotation canonical, util/angles.h:13-34), tip, error, iters, FK calls (any output may be null)
 __global__ void ik_finish(IkParams prm, IkState st, int64_t n, double *__restrict__ states, double *__restrict__ tips,
                           double *__restrict__ error, int32_t *__restrict__ iters, int32_t *__restrict__ fk_calls) {
-#pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int S = prm.S;
-  if (states) {
-    for (int j = 0; j < S; j++) {
-      double v = st.p[i * S + j];
-      if (j == prm.rot_index) {
-        const double pi = 3.141592653589793, two_pi = 2.0 * pi;
-        v = fmod(fmod(v + pi, two_pi) + two_pi, two_pi) - pi;
-      }
-      states[i * S + j] = v;
-    }
-  }
-  if (tips) for (int k = 0; k < 3; k++) tips[i * 3 + k] = st.f[i * 3 + k];
-  if (error) error[i] = sqrt(st.err2[i]);
-  if (iters) iters[i] = st.iters[i];
-  if (fk_calls) fk_calls[i] = st.fk_calls[i];
+  lm_write_result(prm, i, st.p, st.f, st.err2, st.iters, st.fk_calls, states, tips, error, iters, fk_calls);
 }
 
 }  // namespace trk

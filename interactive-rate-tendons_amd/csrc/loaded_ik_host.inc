@@ -121,7 +121,7 @@ int ikl_chunk_solve(tr_ctx *c, const IklCall &call, const double *d_init, int64_
   const int S = prm.S;
   const trk::IklState st = ikl_state(c);
   const trk::IklRows rows = ikl_rows(c);
-  hipLaunchKernelGGL(trk::ikl_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st);
+  hipLaunchKernelGGL(trk::lm_init, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_init, m, d_des, des_ld, prm, st.pn, st.des);
   HIP_TRY(c, hipGetLastError());
   int64_t active = m;
   int cur = 0, rc;
@@ -130,13 +130,8 @@ int ikl_chunk_solve(tr_ctx *c, const IklCall &call, const double *d_init, int64_
     const int32_t *list = init ? nullptr : k.list[cur];
     if ((rc = k.count.zero(nxt, s))) return rc;
     if ((rc = ikl_linearise(c, call, list, active, d_guess, s, rounds[1]))) return rc;
-    switch (S) {
-#define TRK_CASE(SS) case SS: hipLaunchKernelGGL((trk::ikl_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, call.sprm.delta, st, list, \
-                                                 active, (const double *)k.lin, k.lanes, rows, (int)init, k.list[nxt], k.count.d + nxt); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8) TRK_CASE(9) TRK_CASE(10)
-#undef TRK_CASE
-      default: return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
-    }
+    TRK_FOR_STATE_SIZE(c, S, hipLaunchKernelGGL((trk::ikl_lm_step<SS>), dim3(ik_grid(active, 64)), dim3(64), 0, s, prm, call.sprm.delta, st, list,
+                                                active, (const double *)k.lin, k.lanes, rows, (int)init, k.list[nxt], k.count.d + nxt));
     HIP_TRY(c, hipGetLastError());
     if ((rc = k.count.read(nxt, s, active))) return rc;
     cur = nxt;
@@ -217,7 +212,7 @@ int tr_ik_loaded_batch(tr_ctx *c, const tr_ik_params *params, const tr_shoot_par
     const int64_t m = std::min(chunk, n - off);
     if ((rc = upload_rows(c, k.io_s, initial_states, S, off, m, S)) || (rc = upload_rows(c, k.io_3, des, des_ld, off, m, 3))) return rc;
     if (guess && (rc = upload_rows(c, k.io_g, guess, 6, off, m, 6))) return rc;
-    // (io_s / io_3 are read by ikl_init, io_g by the first gather, before ikl_finish overwrites io_s / io_3 with the results)
+    // (io_s / io_3 are read by lm_init, io_g by the first gather, before ikl_finish overwrites io_s / io_3 with the results)
     if ((rc = ikl_run(c, call, k.io_s, m, k.io_3, des_ld ? 3 : 0, guess ? k.io_g : nullptr, k.io_s, k.io_3, k.io_e, k.io_i, k.io_c, k.io_vu,
                       k.io_eq, nullptr, rounds))) return rc;
     if ((rc = download_rows(c, states_out, k.io_s, off, m, S)) || (rc = download_rows(c, tips_out, k.io_3, off, m, 3)) ||

@@ -15,6 +15,7 @@
 //                 column over the state; ik_lm_step's stop tests and damped step, the next trial point and the next active list
 // The strain steps of J_y and X_y are the shooting's finite_difference_delta itself, not levmar's max(|1e-4 y|, delta): see
 // ikl_lm_step.
+// The LU, the Cholesky solve and the outer iteration's bookkeeping are lm_dense.hpp's, shared with ik_lm_step and loaded_tip_sens.
 // The scheme is tests/loaded_ik_reference.py's, which is the specification.  Compiled without contraction, as ik_kernel.hpp is.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,15 +49,6 @@ struct IklRows {
   uint8_t *conv;    // [m] the shooting converged
   int32_t *calls;   // [m] its integrations
 };
-
-// clipped start and goal of every problem of a chunk (des_ld = 0: one goal row for all)
-__global__ void ikl_init(const double *__restrict__ init, int64_t n, const double *__restrict__ des, int64_t des_ld, IkParams prm, IklState st) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int S = prm.S;
-  for (int j = 0; j < S; j++) st.pn[i * S + j] = ik_clip(init[i * S + j], prm.lo[j], prm.hi[j]);
-  for (int k = 0; k < 3; k++) st.des[i * 3 + k] = des[i * des_ld + k];
-}
 
 // rows of the m listed problems (list null: problems 0 .. m-1, the first round, whose guess rows are the caller's or unused)
 __global__ void ikl_gather(IkParams prm, IklState st, const int32_t *__restrict__ list, int64_t m, IklLoads ld,
@@ -121,49 +113,7 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
   // P A = L U in place (unit L below the diagonal); piv[c]: the row exchanged with row c.  A zero pivot leaves inf / NaN in what is
   // solved with it: the trial is then not accepted, or (W, J_r) make the next damped matrix indefinite, which ends the problem.
   int piv[6];
-#pragma unroll
-  for (int c = 0; c < 6; c++) {
-    int pr = c;
-    double best = fabs(A[c * 6 + c]);
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) { const double t = fabs(A[a * 6 + c]); if (t > best) { best = t; pr = a; } }
-    piv[c] = pr;
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) {
-      if (pr == a) {
-#pragma unroll
-        for (int b = 0; b < 6; b++) { const double t = A[c * 6 + b]; A[c * 6 + b] = A[a * 6 + b]; A[a * 6 + b] = t; }
-      }
-    }
-    const double d = A[c * 6 + c];
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) {
-      const double l = A[a * 6 + c] / d;
-      A[a * 6 + c] = l;
-#pragma unroll
-      for (int b = c + 1; b < 6; b++) A[a * 6 + b] -= l * A[c * 6 + b];
-    }
-  }
-  // b <- J_y^-1 b
-  auto solve = [&](double (&b)[6]) {
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-#pragma unroll
-      for (int a = c + 1; a < 6; a++)
-        if (piv[c] == a) { const double t = b[c]; b[c] = b[a]; b[a] = t; }
-    }
-#pragma unroll
-    for (int a = 1; a < 6; a++) {
-#pragma unroll
-      for (int c = 0; c < a; c++) b[a] -= A[a * 6 + c] * b[c];
-    }
-#pragma unroll
-    for (int a = 5; a >= 0; a--) {
-#pragma unroll
-      for (int c = a + 1; c < 6; c++) b[a] -= A[a * 6 + c] * b[c];
-      b[a] = b[a] / A[a * 6 + a];
-    }
-  };
+  lu6_factor(A, piv);
   // The shooting stops at |e_w| <= residual_threshold, which leaves the tip up to ~1e-5 m from the equilibrium's.  One Newton step
   // on the strains, dy = -J_y^-1 e_w, costs nothing here: the trial's strains become y + dy and its tip x + X_y dy.
   double yn[6], fn[3], en[3];
@@ -171,7 +121,7 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
     double b[6];
 #pragma unroll
     for (int a = 0; a < 6; a++) b[a] = row[a * ldr];
-    solve(b);
+    lu6_solve(A, piv, b);
 #pragma unroll
     for (int a = 0; a < 6; a++) yn[a] = rows.vu[r * 6 + a] - b[a];
 #pragma unroll
@@ -196,7 +146,7 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
       double b[6];
 #pragma unroll
       for (int a = 0; a < 6; a++) b[a] = (row[a * ldr + 14 + 2 * k] - row[a * ldr + 13 + 2 * k]) * sc;
-      solve(b);
+      lu6_solve(A, piv, b);
 #pragma unroll
       for (int a = 0; a < 6; a++) st.W[(i * 6 + a) * S + k] = b[a];
 #pragma unroll
@@ -208,22 +158,6 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
       }
     }
   };
-  // g = J^T e
-  auto grad = [&]() {
-#pragma unroll
-    for (int j = 0; j < S; j++) g[j] = J[0 * S + j] * e[0] + J[1 * S + j] * e[1] + J[2 * S + j] * e[2];
-  };
-  // components of J^T e that can still move the state inside the box (ik_lm_step) -> max |.| > eps1
-  auto moving = [&]() {
-    double mx = 0.0;
-#pragma unroll
-    for (int j = 0; j < S; j++) {
-      const bool blocked = (p[j] <= prm.lo[j] && g[j] < 0.0) || (p[j] >= prm.hi[j] && g[j] > 0.0);
-      const double a = blocked ? 0.0 : fabs(g[j]);
-      if (!(a <= mx)) mx = a;                       // a NaN wins, as in np.max
-    }
-    return mx > prm.eps1;
-  };
   auto take_trial = [&]() {
 #pragma unroll
     for (int j = 0; j < S; j++) p[j] = x[j];
@@ -231,7 +165,7 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
     for (int k = 0; k < 3; k++) { f[k] = fn[k]; e[k] = en[k]; }
     err2 = err2n;
     reduce();
-    grad();
+    lm_grad<S>(J, e, g);
   };
   if (init) {
     nu = 2.0;
@@ -259,7 +193,7 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
     }
     mu = prm.mu_init * dmax;
     if (!(mu > 0.0)) mu = prm.mu_init;
-    active = err2 > prm.eps3_sq && moving();
+    active = err2 > prm.eps3_sq && lm_moving<S>(p, g, prm);
   } else {
 #pragma unroll
     for (int j = 0; j < S; j++) p[j] = st.p[i * S + j];
@@ -268,25 +202,19 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
 #pragma unroll
     for (int k = 0; k < 3; k++) { f[k] = st.f[i * 3 + k]; e[k] = des[k] - f[k]; }
     err2 = st.err2[i]; mu = st.mu[i]; nu = st.nu[i]; iters = st.iters[i];
-    grad();
-    // gain ratio of the step dp = x - p against the model's predicted decrease dp . (mu dp + g)
-    double pred = 0.0;
-#pragma unroll
-    for (int j = 0; j < S; j++) { const double dp = x[j] - p[j]; pred += dp * (mu * dp + g[j]); }
-    const double rho = pred > 0.0 ? (err2 - err2n) / pred : -1.0;
+    lm_grad<S>(J, e, g);
+    const double rho = lm_gain_ratio<S>(x, p, g, mu, err2, err2n);
     accepted = conv && rho > 0.0;
     if (accepted) {
       take_trial();
 #pragma unroll
       for (int a = 0; a < 6; a++) st.y[i * 6 + a] = yn[a];
       const double t = 2.0 * rho - 1.0;
-      const double sh = 1.0 - t * t * t;
-      mu *= (1.0 / 3.0) > sh ? (1.0 / 3.0) : sh;
+      mu *= lm_shrink(t * t * t);
       nu = 2.0;
-      active = err2 > prm.eps3_sq && moving();
+      active = err2 > prm.eps3_sq && lm_moving<S>(p, g, prm);
     } else {
-      mu *= nu;
-      nu *= 2.0;
+      lm_reject(mu, nu);
       active = isfinite(mu) && mu < 1e300;
     }
   }
@@ -308,37 +236,8 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
       for (int b = 0; b <= a; b++)
         A[a * (a + 1) / 2 + b] = J[0 * S + a] * J[0 * S + b] + J[1 * S + a] * J[1 * S + b] + J[2 * S + a] * J[2 * S + b] + (a == b ? mu : 0.0);
     }
-    bool spd = true;
-#pragma unroll
-    for (int a = 0; a < S; a++) {
-#pragma unroll
-      for (int b = 0; b <= a; b++) {
-        double s = A[a * (a + 1) / 2 + b];
-#pragma unroll
-        for (int k = 0; k < b; k++) s -= A[a * (a + 1) / 2 + k] * A[b * (b + 1) / 2 + k];
-        if (a == b) {
-          spd = spd && s > 0.0;
-          A[a * (a + 1) / 2 + a] = sqrt(s > 0.0 ? s : 1.0);
-        } else {
-          A[a * (a + 1) / 2 + b] = s / A[b * (b + 1) / 2 + b];
-        }
-      }
-    }
     double y[S];
-#pragma unroll
-    for (int a = 0; a < S; a++) {
-      double s = g[a];
-#pragma unroll
-      for (int k = 0; k < a; k++) s -= A[a * (a + 1) / 2 + k] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
-#pragma unroll
-    for (int a = S - 1; a >= 0; a--) {
-      double s = y[a];
-#pragma unroll
-      for (int k = a + 1; k < S; k++) s -= A[k * (k + 1) / 2 + a] * y[k];
-      y[a] = s / A[a * (a + 1) / 2 + a];
-    }
+    const bool spd = chol_solve_packed<S>(A, g, y);
     // projected onto the box; the relative-step test on the step actually taken
     double dd = 0.0, pp = 0.0;
 #pragma unroll
@@ -366,24 +265,9 @@ __global__ __launch_bounds__(64) void ikl_lm_step(IkParams prm, double delta_y, 
 __global__ void ikl_finish(IkParams prm, IklState st, int64_t n, double *__restrict__ states, double *__restrict__ tips,
                            double *__restrict__ error, int32_t *__restrict__ iters, int32_t *__restrict__ calls, double *__restrict__ vu0,
                            uint8_t *__restrict__ eq) {
-#pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int S = prm.S;
-  if (states) {
-    for (int j = 0; j < S; j++) {
-      double v = st.p[i * S + j];
-      if (j == prm.rot_index) {
-        const double pi = 3.141592653589793, two_pi = 2.0 * pi;
-        v = fmod(fmod(v + pi, two_pi) + two_pi, two_pi) - pi;
-      }
-      states[i * S + j] = v;
-    }
-  }
-  if (tips) for (int k = 0; k < 3; k++) tips[i * 3 + k] = st.f[i * 3 + k];
-  if (error) error[i] = sqrt(st.err2[i]);
-  if (iters) iters[i] = st.iters[i];
-  if (calls) calls[i] = st.calls[i];
+  lm_write_result(prm, i, st.p, st.f, st.err2, st.iters, st.calls, states, tips, error, iters, calls);
   if (vu0) for (int a = 0; a < 6; a++) vu0[i * 6 + a] = st.y[i * 6 + a];
   if (eq) eq[i] = st.eq[i];
 }

@@ -45,13 +45,8 @@ int sens_chunk_solve(tr_ctx *c, const IklCall &call, const double *d_states, int
   // the states are the gather's trial points as they stand (no bounds here)
   HIP_TRY(c, hipMemcpyAsync(k.pn, d_states, (size_t)(m * S) * sizeof(double), hipMemcpyDeviceToDevice, s));
   if (const int rc = ikl_linearise(c, call, nullptr, m, d_guess, s, rounds)) return rc;
-  switch (S) {
-#define TRK_CASE(SS) case SS: hipLaunchKernelGGL((trk::loaded_tip_sens<SS>), dim3(ik_grid(m, 64)), dim3(64), 0, s, prm.delta, call.sprm.delta, \
-                                                 (int)prm.rot_index, (int)call.loads.world, m, (const double *)k.lin, k.lanes, rows, out); break;
-    TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8) TRK_CASE(9) TRK_CASE(10)
-#undef TRK_CASE
-    default: return fail(c, TR_ERR_OUT_OF_RANGE, "state size out of range");
-  }
+  TRK_FOR_STATE_SIZE(c, S, hipLaunchKernelGGL((trk::loaded_tip_sens<SS>), dim3(ik_grid(m, 64)), dim3(64), 0, s, prm.delta, call.sprm.delta,
+                                              (int)prm.rot_index, (int)call.loads.world, m, (const double *)k.lin, k.lanes, rows, out));
   HIP_TRY(c, hipGetLastError());
   return TR_OK;
 }

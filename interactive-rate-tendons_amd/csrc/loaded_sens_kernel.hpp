@@ -11,9 +11,10 @@
 // with respect to the wrench as the caller gave it.  The shooting stops at the threshold, not at the equilibrium: one Newton step
 // with J_y gives the strains y_c = y - J_y^-1 e_w and the tip x_c = x - X_y J_y^-1 e_w that are returned.
 //
-// The differences, the LU of J_y with partial pivoting in registers, the solves and the reduction are ikl_lm_step's, operation by
-// operation: W and J are the bits the loaded IK uses from the same planes.  The specification is
-// tests/loaded_jacobian_reference.py.  Compiled without contraction.
+// The LU of J_y with partial pivoting in registers and the solves are the functions ikl_lm_step calls (lm_dense.hpp: lu6_factor,
+// lu6_solve); the differences, the Newton step and the reduction around them are ikl_lm_step's text, operation by operation (the
+// header says why they are not functions too): W and J are the bits the loaded IK uses from the same planes.  The specification
+// is tests/loaded_jacobian_reference.py.  Compiled without contraction.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,60 +74,15 @@ __global__ __launch_bounds__(64) void loaded_tip_sens(double delta_p, double del
 #pragma unroll
     for (int q = 0; q < 18; q++) put(blk + 51 + 6 * S + q, Xy[q]);
   }
-  // P A = L U in place (unit L below the diagonal); piv[c]: the row exchanged with row c.  A zero pivot leaves inf / NaN in what is
-  // solved with it, and clears the problem's flag.
+  // the LU factors of J_y; a zero pivot clears the problem's flag
   int piv[6];
-  bool singular = false;
-#pragma unroll
-  for (int c = 0; c < 6; c++) {
-    int pr = c;
-    double best = fabs(A[c * 6 + c]);
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) { const double t = fabs(A[a * 6 + c]); if (t > best) { best = t; pr = a; } }
-    piv[c] = pr;
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) {
-      if (pr == a) {
-#pragma unroll
-        for (int b = 0; b < 6; b++) { const double t = A[c * 6 + b]; A[c * 6 + b] = A[a * 6 + b]; A[a * 6 + b] = t; }
-      }
-    }
-    const double d = A[c * 6 + c];
-    singular = singular || d == 0.0;
-#pragma unroll
-    for (int a = c + 1; a < 6; a++) {
-      const double l = A[a * 6 + c] / d;
-      A[a * 6 + c] = l;
-#pragma unroll
-      for (int b = c + 1; b < 6; b++) A[a * 6 + b] -= l * A[c * 6 + b];
-    }
-  }
-  // b <- J_y^-1 b
-  auto solve = [&](double (&b)[6]) {
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-#pragma unroll
-      for (int a = c + 1; a < 6; a++)
-        if (piv[c] == a) { const double t = b[c]; b[c] = b[a]; b[a] = t; }
-    }
-#pragma unroll
-    for (int a = 1; a < 6; a++) {
-#pragma unroll
-      for (int c = 0; c < a; c++) b[a] -= A[a * 6 + c] * b[c];
-    }
-#pragma unroll
-    for (int a = 5; a >= 0; a--) {
-#pragma unroll
-      for (int c = a + 1; c < 6; c++) b[a] -= A[a * 6 + c] * b[c];
-      b[a] = b[a] / A[a * 6 + a];
-    }
-  };
+  const bool singular = lu6_factor(A, piv);
   // the Newton step on the strains: y_c = y - J_y^-1 e_w, x_c = x - X_y J_y^-1 e_w
   {
     double b[6];
 #pragma unroll
     for (int a = 0; a < 6; a++) b[a] = row[a * ldr];
-    solve(b);
+    lu6_solve(A, piv, b);
     if (o.vu0) {
 #pragma unroll
       for (int a = 0; a < 6; a++) put(o.vu0 + r * 6 + a, rows.vu[r * 6 + a] - b[a]);
@@ -152,7 +108,7 @@ __global__ __launch_bounds__(64) void loaded_tip_sens(double delta_p, double del
 #pragma unroll
       for (int a = 0; a < 6; a++) put(blk + 51 + a * S + k, b[a]);
     }
-    solve(b);
+    lu6_solve(A, piv, b);
     if (o.W) {
 #pragma unroll
       for (int a = 0; a < 6; a++) put(o.W + (r * 6 + a) * S + k, b[a]);
@@ -180,7 +136,7 @@ __global__ __launch_bounds__(64) void loaded_tip_sens(double delta_p, double del
       if (g == 0) { b[h + 0] = cs; if (turn) b[h + 1] = -sn; }
       else if (g == 1) { if (turn) b[h + 0] = sn; b[h + 1] = cs; }
       else b[h + 2] = 1.0;
-      solve(b);
+      lu6_solve(A, piv, b);
 #pragma unroll
       for (int q = 0; q < 3; q++) {
         double s = 0.0;

@@ -683,6 +683,17 @@ const trk::FkOut kFkOutNone{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr
     default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");                                              \
   }
 
+// The same over the state size S (1 .. TRK_IK_MAX_S), with SS the constant expression: the step kernels' instantiations.
+#define TRK_STATE_SIZE_CASE(SIZE, ...) case SIZE: { constexpr int SS = SIZE; __VA_ARGS__; } break;
+#define TRK_FOR_STATE_SIZE(ctx, S, ...)                                                                                    \
+  switch (S) {                                                                                                             \
+    TRK_STATE_SIZE_CASE(1, __VA_ARGS__) TRK_STATE_SIZE_CASE(2, __VA_ARGS__) TRK_STATE_SIZE_CASE(3, __VA_ARGS__)              \
+    TRK_STATE_SIZE_CASE(4, __VA_ARGS__) TRK_STATE_SIZE_CASE(5, __VA_ARGS__) TRK_STATE_SIZE_CASE(6, __VA_ARGS__)              \
+    TRK_STATE_SIZE_CASE(7, __VA_ARGS__) TRK_STATE_SIZE_CASE(8, __VA_ARGS__) TRK_STATE_SIZE_CASE(9, __VA_ARGS__)              \
+    TRK_STATE_SIZE_CASE(10, __VA_ARGS__)                                                                                    \
+    default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "state size out of range");                                             \
+  }
+
 int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, hipStream_t s, int lane = 0) {
   if (n <= 0) return TR_OK;
   ProfScope ps(ctx, 0, s);

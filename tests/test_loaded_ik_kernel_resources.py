@@ -67,6 +67,6 @@ def test_step_kernel_does_not_spill(tmp_path, S):
 
 def test_small_kernels_have_no_scratch_and_no_spills(tmp_path):
     remarks = _compile(tmp_path, "small", STEP_TU % 3)
-    for kernel in ("8ikl_init", "10ikl_gather", "10ikl_finish"):
+    for kernel in ("7lm_init", "10ikl_gather", "10ikl_finish"):
         f = _figures(remarks, "_ZN3trk" + kernel)
         assert f["scratch"] == 0 and f["vspill"] == 0 and f["sspill"] == 0, kernel
