@@ -482,6 +482,21 @@ int tr_voxelize_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, con
 int tr_connect_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
                                     const double *states, int64_t n_states, const int32_t *edges, int64_t n_edges, int64_t *offsets,
                                     uint64_t *valid_bits, int32_t *n_fk, int64_t *n_unconverged, int64_t *n_integrations);
+/* The tips of loaded shapes alone: tr_fk_loaded_batch's shooting (`shoot`, NULL: its defaults; wrench / dist rows and `guess` as
+ * there, NULL guess: cold) and fk_shape.p.back() of the integration at the final strains -- bit for bit tr_fk_loaded_batch's last
+ * point, tr_voxelize_batch_loaded's tip and the loaded vertex phase's.  The shapes are integrated into the context's point workspace
+ * a chunk at a time, so no plane is ever n columns wide.
+ *   tips n x 3, converged n, vu0 n x 6 (the accepted base strains) -- all optional
+ *   rounds_out  optional int64[2]: shooting rounds (one host synchronisation each), the sum of the problems' integrations
+ * A state whose shooting does not converge has converged = 0 and the tip of its last strains: never an error of the call.  Robots with
+ * retraction: TR_ERR_UNSUPPORTED; n == 0: TR_OK.  The _dev form takes device arrays; its run is the null stream's (the device is
+ * drained before it) and ends synchronised.  A state's result does not depend on the batch or on TENDON_HIP_SHOOT_CHUNK. */
+int tr_fk_loaded_tips(tr_ctx *ctx, const tr_shoot_params *shoot, const double *states, int64_t n, const double *wrench, int64_t wrench_ld,
+                      const double *dist, int64_t dist_ld, const double *guess, double *tips, uint8_t *converged, double *vu0,
+                      int64_t *rounds_out);
+int tr_fk_loaded_tips_dev(tr_ctx *ctx, const tr_shoot_params *shoot, const double *d_states, int64_t n, const double *d_wrench,
+                          int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess, double *d_tips,
+                          uint8_t *d_converged, double *d_vu0, int64_t *rounds_out, void *stream);
 
 /* ---- tip inverse kinematics on loaded shapes --------------------------------------------- */
 
@@ -821,6 +836,46 @@ int tr_roadmap_solve_tips_connect(tr_roadmap *rm, const tr_space_params *sp, con
  * differs from their ik_vertex, out[3] requests REACHED that the one-edge rule, restricted to the pairs (i, N_q[i]), does not reach.
  * The source search counts into `nearest` of tr_roadmap_tip_query_profile. */
 int tr_roadmap_tip_connect_stats(tr_roadmap *rm, int64_t out[4]);
+
+/* ---- tip-goal queries on LOADED shapes ----
+ * With TendonRobot::general_shape installed as the checker's FK (apps/profile_chained_plan.cpp:407-451) roadmapIk takes every shape
+ * from voxelStateChecker_->fk (:3052, :3187): its IK, its last-valid edge checks and its closest-state rule all run on loaded shapes.
+ * These calls are that for ONE load set per call (`loads`: tr_edge_loads' meaning of BASE and WORLD, NULL: no load; warm_start is not
+ * read -- every solve is cold).  `shoot` goes to all three solvers (NULL: each one's own defaults -- tr_ik_loaded_batch's for the IK,
+ * tr_fk_loaded_batch's for the pair check and rule 5L).  `connect` NULL or k_connect 0: the one-edge rule.  Rules 1 - 6 with:
+ *   1L.  Rule 1 unchanged.  The tips are the roadmap's and must be LOADED tips: given to tr_roadmap_set_tips by the caller, or made by
+ *        tr_roadmap_set_tips_loaded.  Tips the roadmap computed itself with tr_fk_tips_dev (the NULL form of tr_roadmap_set_tips) are
+ *        unloaded ones: TR_ERR_INVALID_ARG.
+ *   2L.  ALL n k problems in ONE tr_ik_loaded_batch_dev, cold (guess = NULL), bounds as in rule 2: x_i, tip_i, err_i, vu0_i,
+ *        equilibrium_i -- that call's bits.
+ *   3L / 3'L.  (ok, t) = checkMotion(source, x_i, last_valid) on loaded samples: all live pairs of the call in ONE
+ *        tr_validate_edges_loaded with last_valid_t, the same loads, cold.  A sample that does not converge is an invalid sample.
+ *        (Host-array form, as the unloaded rule's.)
+ *   4L / 4'L.  TR_TIPQ_REACHED additionally needs equilibrium_i.
+ *   5L / 5'L.  The tip of g = interpolate(source, x_i, t) comes from a cold tr_fk_loaded_tips_dev solve of g under g's own load rows
+ *        (WORLD loads turned by g's rotation: edge_sincos, the rows of the pair check's samples), one solve per live pair.  A g whose
+ *        solve does not converge is not a candidate.  A request with a neighbour but no candidate ends TR_TIPQ_NO_NEIGHBOR (outputs
+ *        NaN, vertices -1): a state without an equilibrium is never handed out as a goal.
+ *   6.   Rule 6 unchanged (the cached sets of a roadmap built under loads are loaded sets already).
+ *   vu0 (optional, n x 6): the base strains of the chosen state -- the IK's when REACHED, the g solve's when CLOSEST, NaN otherwise.
+ *   counts (optional, int64[4]): pairs checked, IK answers without an equilibrium (slots that hold a neighbour), g solves
+ *        unconverged, integrations (the IK's of those slots + the pair check's + the g solves').
+ * Every result row is a function of its request, the roadmap, the grid, the loads and the parameters alone: not of the rest of the
+ * batch, not of TENDON_HIP_SHOOT_CHUNK.  tr_roadmap_tip_query_profile and tr_roadmap_tip_connect_stats answer for these calls too.
+ * Robots with retraction: TR_ERR_UNSUPPORTED; a bad frame or max_iters < 0: TR_ERR_INVALID_ARG; n == 0: TR_OK before anything else
+ * is asked for.  The calls run on the null stream and share the context's one shooting workspace. */
+int tr_roadmap_ik_batch_loaded(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                               const tr_shoot_params *shoot, const tr_edge_loads *loads, const double *requests, int64_t n, double *controls,
+                               double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome,
+                               double *last_valid_t, double *vu0, int64_t *counts);
+int tr_roadmap_solve_tips_loaded(tr_roadmap *rm, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                 const tr_shoot_params *shoot, const tr_edge_loads *loads, const int32_t *starts, const double *requests, int64_t n,
+                                 int32_t n_threads, double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex,
+                                 int32_t *outcome, double *last_valid_t, double *vu0, int64_t *counts, int32_t *status, double *cost,
+                                 int64_t *path_offsets, tr_roadmap_stats *stats);
+/* tr_roadmap_set_tips with the tips of the vertices' LOADED shapes: one cold tr_fk_loaded_tips_dev solve per vertex under its own load
+ * rows.  A vertex whose solve does not converge has no tip (its present bit is cleared). */
+int tr_roadmap_set_tips_loaded(tr_roadmap *rm, const tr_shoot_params *shoot, const tr_edge_loads *loads, const uint64_t *present_bits);
 
 /* The connection loop itself (motion-planning/VoxelCachedLazyPRM.cpp:1491-1502: for every vertex v and every neighbour n
  * of connectionStrategy_(v), `if (!getEdge(v, n)) connectVertices(v, n)`): the undirected edge set of the k-nearest

@@ -45,6 +45,36 @@ inline void check(const tr_ctx *ctx, int status) {
   }
 }
 
+namespace detail {
+// The library's sine and cosine for turning WORLD load rows (csrc/edge_sincos.hpp), restated: k = rint(x 2/pi), r = (x - k hi) -
+// k lo, Taylor polynomials in Horner form -- the same IEEE operations in the same order, so the same bits (compile without
+// floating-point contraction: the baseline x86-64 target has no fused multiply-add).
+inline void edge_sincos(double x, double &s, double &c) {
+  const double k = std::rint(x * 0.63661977236758138);
+  const double r = (x - k * 1.57079632673412561417e+00) - k * 6.07710050650619224932e-11;
+  const double z = r * r;
+  static const double cs[8] = {1.0 / 355687428096000.0, -1.0 / 1307674368000.0, 1.0 / 6227020800.0, -1.0 / 39916800.0,
+                               1.0 / 362880.0, -1.0 / 5040.0, 1.0 / 120.0, -1.0 / 6.0};
+  static const double cc[9] = {-1.0 / 6402373705728000.0, 1.0 / 20922789888000.0, -1.0 / 87178291200.0, 1.0 / 479001600.0,
+                               -1.0 / 3628800.0, 1.0 / 40320.0, -1.0 / 720.0, 1.0 / 24.0, -0.5};
+  double ps = cs[0], pc = cc[0];
+  for (int i = 1; i < 8; i++) ps = cs[i] + z * ps;
+  for (int i = 1; i < 9; i++) pc = cc[i] + z * pc;
+  const double sr = r + r * (z * ps), cr = 1.0 + z * pc;
+  const int q = (int)((long long)k & 3);
+  s = q == 0 ? sr : (q == 1 ? cr : (q == 2 ? -sr : -cr));
+  c = q == 0 ? cr : (q == 1 ? -sr : (q == 2 ? -cr : sr));
+}
+// a load row (force, moment) turned by Rz(-theta): (x, y, z) -> (c x + s y, c y - s x, z)
+inline void edge_turn_row(const double *w, double s, double c, double *o) {
+  for (int h = 0; h < 2; h++) {
+    o[3 * h + 0] = c * w[3 * h + 0] + s * w[3 * h + 1];
+    o[3 * h + 1] = c * w[3 * h + 1] - s * w[3 * h + 0];
+    o[3 * h + 2] = w[3 * h + 2];
+  }
+}
+}  // namespace detail
+
 namespace tendon {
 
 struct BackboneSpecs {              // tendon/BackboneSpecs.h:14-20
@@ -258,6 +288,43 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     check(c, tr_tip_jacobian_loaded(c, &prm, (wrench.empty() && dist.empty()) ? nullptr : &ld, states.data(), (int64_t)n, opt.delta,
                                     guess.empty() ? nullptr : guess.data(), out.tips.data(), out.J.data(), out.compliance.data(), nullptr,
                                     out.vu0.data(), out.equilibrium.data(), nullptr, out.n_integrations.data(), rounds));
+    return out;
+  }
+
+  struct LoadedTips {
+    std::vector<double> tips;          // n x 3: fk_shape.p.back() of the loaded shapes
+    std::vector<double> vu0;           // n x 6: the accepted base strains (v0, u0)
+    std::vector<uint8_t> converged;    // the shooting reached the residual threshold
+    int64_t rounds = 0, n_integrations = 0;
+  };
+  /// The tips of generalShapeBatch's shapes alone (tr_fk_loaded_tips: the shapes stay on the device), cold, under ONE load set as
+  /// VoxelBackboneValidityChecker::setLoads holds it (checker.loads()): frame BASE gives every state the same rows, WORLD turns them
+  /// by Rz(-theta) of the state's rotation with the library's own sine and cosine (detail::edge_sincos), so the rows are those of
+  /// the loaded edge calls bit for bit.
+  LoadedTips loaded_tips_batch(const std::vector<double> &states, size_t n, const tr_edge_loads &loads,
+                               const ShootOptions &opt = ShootOptions()) const {
+    const size_t S = state_size(), N = tendons.size();
+    if (states.size() != n * S) throw std::invalid_argument("State is not the right size");
+    tr_ctx *c = context();
+    const tr_shoot_params prm{opt.max_iters, opt.mu_init, opt.stop_threshold_JT_err_inf, opt.stop_threshold_Dp, opt.finite_difference_delta};
+    const bool turn = loads.frame == TR_LOAD_FRAME_WORLD && enable_rotation;
+    std::vector<double> w(loads.wrench, loads.wrench + 6), d(loads.dist, loads.dist + 6);
+    if (turn) {
+      w.resize(6 * n); d.resize(6 * n);
+      for (size_t i = 0; i < n; i++) {
+        double s, co;
+        detail::edge_sincos(states[i * S + N], s, co);
+        detail::edge_turn_row(loads.wrench, s, co, &w[6 * i]);
+        detail::edge_turn_row(loads.dist, s, co, &d[6 * i]);
+      }
+    }
+    LoadedTips out;
+    out.tips.resize(3 * n); out.vu0.resize(6 * n); out.converged.resize(n);
+    int64_t r2[2] = {0, 0};
+    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error)
+    check(c, tr_fk_loaded_tips(c, &prm, states.data(), (int64_t)n, w.data(), turn ? 6 : 0, d.data(), turn ? 6 : 0, nullptr, out.tips.data(),
+                               out.converged.data(), out.vu0.data(), r2));
+    out.rounds = r2[0]; out.n_integrations = r2[1];
     return out;
   }
 
@@ -1405,6 +1472,68 @@ class VoxelCachedLazyPRM {
                                          s.ik.controls.data(), s.ik.tip_positions.data(), s.ik.error.data(), s.ik.neighbor_vertex.data(),
                                          s.ik.ik_vertex.data(), s.ik.outcome.data(), s.ik.last_valid_t.data(), s.roadmap.status.data(),
                                          s.roadmap.cost.data(), off.data(), &s.roadmap.stats));
+    rcheck(tr_roadmap_tip_connect_stats(rm_, s.ik.connect_stats.data()));
+    std::vector<int32_t> pv((size_t)off[n]);
+    rcheck(tr_roadmap_fetch_paths(rm_, pv.data(), (int64_t)pv.size()));
+    s.roadmap.paths.resize(n);
+    for (size_t q = 0; q < n; q++) s.roadmap.paths[q].assign(pv.begin() + off[q], pv.begin() + off[q + 1]);
+    return s;
+  }
+
+  // ---- tip queries on LOADED shapes (tr_roadmap_ik_batch_loaded / tr_roadmap_solve_tips_loaded / tr_roadmap_set_tips_loaded; rules
+  // 1L - 5'L in include/tendon_hip.h).  The load set is given explicitly, in the struct VoxelBackboneValidityChecker::setLoads holds
+  // (checker.loads()); roadmapIk* and solveToTips* on a checker with loads keep throwing. ----
+  struct LoadedTipResults : AccurateTipResults {
+    std::vector<double> vu0;                 // n x 6: the base strains (v0, u0) of the goal state's equilibrium
+    std::array<int64_t, 4> counts{};         // pairs checked, IK answers without an equilibrium, last valid states unconverged, integrations
+  };
+  struct LoadedTipSolution { LoadedTipResults ik; Solution roadmap; };
+  /// The vertices' tips from cold loaded solves of the roadmap's states (a vertex without an equilibrium has no tip).  A roadmap
+  /// built by createRoadmap after setLoads holds loaded tips already.
+  void setTipsLoaded(const tr_edge_loads &loads) {
+    sync_tips();
+    std::vector<bool> has(milestoneCount());
+    for (size_t v = 0; v < milestoneCount(); v++) has[v] = has_tip_[v] != 0;
+    const auto bits = detail::pack(has);
+    rcheck(tr_roadmap_set_tips_loaded(rm_, nullptr, &loads, bits.data()));
+  }
+  /// roadmapIkBatch (k_connect = 0) or roadmapIkBatchAccurate on loaded shapes under `loads`, every solve cold.
+  LoadedTipResults roadmapIkBatchLoaded(const std::vector<std::array<double, 3>> &requests, const tr_edge_loads &loads, double tolerance = 1e-4,
+                                        size_t k = 5, size_t k_connect = 0, double max_distance = std::numeric_limits<double>::infinity()) {
+    need_validators("roadmapIkBatchLoaded");
+    sync_tips();
+    const size_t n = requests.size();
+    LoadedTipResults r;
+    static_cast<TipResults &>(r) = tip_results(n);
+    r.ik_vertex.resize(n); r.vu0.resize(6 * n);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    const tr_tip_connect_params cp{(int32_t)k_connect, max_distance};
+    rcheck(tr_roadmap_ik_batch_loaded(rm_, &mv_->space, &prm, &cp, nullptr, &loads, n ? requests[0].data() : nullptr, (int64_t)n, r.controls.data(),
+                                      r.tip_positions.data(), r.error.data(), r.neighbor_vertex.data(), r.ik_vertex.data(), r.outcome.data(),
+                                      r.last_valid_t.data(), r.vu0.data(), r.counts.data()));
+    rcheck(tr_roadmap_tip_connect_stats(rm_, r.connect_stats.data()));
+    return r;
+  }
+  /// ... followed by solveWithRoadmap from starts[q] to request q's connection vertex, as solveToTips.
+  LoadedTipSolution solveToTipsLoaded(const std::vector<int32_t> &starts, const std::vector<std::array<double, 3>> &requests,
+                                      const tr_edge_loads &loads, double tolerance = 1e-4, size_t k = 5, size_t k_connect = 0, int n_threads = 0,
+                                      double max_distance = std::numeric_limits<double>::infinity()) {
+    if (starts.size() != requests.size()) throw std::invalid_argument("starts and requests differ in length");
+    need_validators("solveToTipsLoaded");
+    sync_tips();
+    const size_t n = requests.size();
+    LoadedTipSolution s;
+    static_cast<TipResults &>(s.ik) = tip_results(n);
+    s.ik.ik_vertex.resize(n); s.ik.vu0.resize(6 * n);
+    s.roadmap.status.resize(n); s.roadmap.cost.resize(n);
+    std::vector<int64_t> off(n + 1, 0);
+    const tr_tip_query_params prm = tip_params(tolerance, k);
+    const tr_tip_connect_params cp{(int32_t)k_connect, max_distance};
+    rcheck(tr_roadmap_solve_tips_loaded(rm_, &mv_->space, &prm, &cp, nullptr, &loads, starts.data(), n ? requests[0].data() : nullptr, (int64_t)n,
+                                        n_threads, s.ik.controls.data(), s.ik.tip_positions.data(), s.ik.error.data(),
+                                        s.ik.neighbor_vertex.data(), s.ik.ik_vertex.data(), s.ik.outcome.data(), s.ik.last_valid_t.data(),
+                                        s.ik.vu0.data(), s.ik.counts.data(), s.roadmap.status.data(), s.roadmap.cost.data(), off.data(),
+                                        &s.roadmap.stats));
     rcheck(tr_roadmap_tip_connect_stats(rm_, s.ik.connect_stats.data()));
     std::vector<int32_t> pv((size_t)off[n]);
     rcheck(tr_roadmap_fetch_paths(rm_, pv.data(), (int64_t)pv.size()));

@@ -17,11 +17,12 @@ from .collision import VoxelOctree
 from .motion_planning import (VoxelEnvironment, VoxelBackboneValidityChecker, VoxelValidityChecker, VoxelBackboneMotionValidator,
                               VoxelBackboneDiscreteMotionValidator, FunctionTimer, Environment, Problem)
 from . import workloads, distributed, roadmap, rmp, tip_control
-from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan
+from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan, chained_plan_loaded
 
 __all__ = [
     "TendonHipError", "InvalidArgument", "OutOfRange", "DomainError", "LengthError", "HipError", "Unsupported",
     "build", "LIB_PATH", "Engine", "unpack_bits", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot", "PointForces",
     "VoxelOctree", "VoxelEnvironment", "VoxelBackboneValidityChecker", "VoxelValidityChecker", "VoxelBackboneMotionValidator", "VoxelBackboneDiscreteMotionValidator", "Environment", "Problem",
-    "FunctionTimer", "workloads", "distributed", "roadmap", "RoadmapBuilder", "VoxelCachedLazyPRM", "chained_plan", "tip_control",
+    "FunctionTimer", "workloads", "distributed", "roadmap", "RoadmapBuilder", "VoxelCachedLazyPRM", "chained_plan", "chained_plan_loaded",
+    "tip_control",
 ]

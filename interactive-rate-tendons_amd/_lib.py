@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
     "tr_ik_loaded_batch", "tr_ik_loaded_batch_dev",
     "tr_tip_jacobian_loaded", "tr_tip_jacobian_loaded_dev",
+    "tr_fk_loaded_tips", "tr_fk_loaded_tips_dev",
+    "tr_roadmap_ik_batch_loaded", "tr_roadmap_solve_tips_loaded", "tr_roadmap_set_tips_loaded",
 )
 
 
@@ -150,13 +152,14 @@ def _units():
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
-                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp"]
+                    "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp",
+                    "tipq_loaded_kernel.hpp"]
     fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
                "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
     u = [("tendon_hip.o", "tendon_hip.hip", [], main_deps + [HEADER]),
          ("cache_merge.o", "cache_merge.hip", [], ["cache_merge.hip", "cache_merge.hpp"]),
-         ("roadmap.o", "roadmap.hip", ["-pthread"], roadmap_deps + [HEADER]),
+         ("roadmap.o", "roadmap.hip", ["-pthread"], roadmap_deps + ["edge_sincos.hpp", HEADER]),   # (tendon_hip.o's too)
          ("sample.o", "sample.hip", [], ["sample.hip", "sample.hpp", "tr_types.hpp"])]
     q_deps = fk_deps + ["edge_queue_kernel.hpp", "edge_kernel.hpp"]
     l_deps = fk_deps + ["fk_loaded_kernel.hpp"]
@@ -395,6 +398,12 @@ def lib():
     L.tr_roadmap_solve_tips_connect.argtypes = [vp, P(TrSpaceParams), tqp, tcp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, i32p, dp, i32p,
                                                 dp, P(i64), P(TrRoadmapStats)]
     L.tr_roadmap_tip_connect_stats.argtypes = [vp, P(i64)]
+    L.tr_fk_loaded_tips.argtypes = [vp, shp, dp, i64, dp, i64, dp, i64, dp, dp, P(C.c_uint8), dp, P(i64)]
+    L.tr_fk_loaded_tips_dev.argtypes = [vp, shp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, P(i64), vp]
+    L.tr_roadmap_ik_batch_loaded.argtypes = [vp, P(TrSpaceParams), tqp, tcp, shp, elp, dp, i64, dp, dp, dp, i32p, i32p, i32p, dp, dp, P(i64)]
+    L.tr_roadmap_solve_tips_loaded.argtypes = [vp, P(TrSpaceParams), tqp, tcp, shp, elp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, i32p,
+                                               dp, dp, P(i64), i32p, dp, P(i64), P(TrRoadmapStats)]
+    L.tr_roadmap_set_tips_loaded.argtypes = [vp, shp, elp, P(u64)]
     L.tr_profile_begin.argtypes = [vp]
     L.tr_profile_read.argtypes = [vp, P(i64), dp]
     L.tr_profile_end.argtypes = [vp]

@@ -195,9 +195,97 @@ int voxelize_edges_loaded_indexed_impl(tr_ctx *c, const tr_space_params *sp, con
   return TR_OK;
 }
 
+// tr_fk_loaded_tips*'s body: n device states under per-state (or one, ld = 0) load rows, solved by shoot_chunk_solve into the point
+// workspace a chunk at a time -- planes exist for one chunk only -- and loaded_tip_rows on each chunk.  Null stream; ends synchronised.
+int loaded_tips_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, int64_t n, const double *d_wrench, int64_t wrench_ld,
+                    const double *d_dist, int64_t dist_ld, const double *d_guess, double *d_tips, uint8_t *d_conv, double *d_vu0,
+                    int64_t *rounds_out) {
+  LoadedEdges le{};
+  le.c = c;
+  le.prm = prm;
+  int rc;
+  const int64_t chunk = std::min<int64_t>(shoot_chunk_size(c), std::min<int64_t>(c->max_chunk, (int64_t)1 << 16));
+  if ((rc = ensure_workspace(c, std::min(n, chunk)))) return rc;
+  const int64_t cap = c->ws.ld;
+  if ((rc = le.reserve(cap)) || (rc = le.clear_tally())) return rc;
+  const int S = c->K.state_size;
+  int64_t rounds = 0, nu = 0, ni = 0;
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    uint8_t *conv = d_conv ? d_conv + off : c->ws.conv;
+    if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, m, cap, d_wrench ? d_wrench + off * wrench_ld : c->shoot.zero6, d_wrench ? wrench_ld : 0,
+                                rows_at(d_dist, off, dist_ld), dist_ld, rows_at(d_guess, off, 6), ws_fk_out(c, 0), conv, rows_at(d_vu0, off, 6),
+                                nullptr, nullptr, nullptr, c->ledge.calls, nullptr, rounds))) return rc;
+    {
+      ProfScope ps(c, 3, nullptr);
+      hipLaunchKernelGGL(trk::loaded_sample_tally, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t *)conv,
+                         (const int32_t *)c->ledge.calls, m, c->ledge.tally);
+      HIP_TRY(c, hipGetLastError());
+    }
+    if (d_tips && (rc = loaded_tips(c, m, d_tips + off * 3))) return rc;
+  }
+  if ((rc = le.add_tally(&nu, &ni))) return rc;                          // (synchronises the null stream)
+  if (rounds_out) { rounds_out[0] = rounds; rounds_out[1] = ni; }
+  return TR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tr_fk_loaded_tips_dev(tr_ctx *c, const tr_shoot_params *shoot, const double *d_states, int64_t n, const double *d_wrench, int64_t wrench_ld,
+                          const double *d_dist, int64_t dist_ld, const double *d_guess, double *d_tips, uint8_t *d_converged, double *d_vu0,
+                          int64_t *rounds_out, void *stream) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (rounds_out) rounds_out[0] = rounds_out[1] = 0;
+  int rc;
+  if ((rc = shoot_check(c, n, wrench_ld, dist_ld))) return rc;
+  trk::ShootParams prm;
+  if ((rc = shoot_params(c, shoot, prm))) return rc;
+  if (n == 0) return TR_OK;
+  if (!d_states) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());          // the run is the null stream's; the workspaces are shared with *_dev calls on other streams
+  if ((rc = loaded_tips_run(c, prm, d_states, n, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, d_tips, d_converged, d_vu0, rounds_out))) return rc;
+  return note_dev_work(c, (hipStream_t)stream);
+}
+
+int tr_fk_loaded_tips(tr_ctx *c, const tr_shoot_params *shoot, const double *states, int64_t n, const double *wrench, int64_t wrench_ld,
+                      const double *dist, int64_t dist_ld, const double *guess, double *tips, uint8_t *converged, double *vu0,
+                      int64_t *rounds_out) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (rounds_out) rounds_out[0] = rounds_out[1] = 0;
+  int rc;
+  if ((rc = shoot_check(c, n, wrench_ld, dist_ld))) return rc;
+  trk::ShootParams prm;
+  if ((rc = shoot_params(c, shoot, prm))) return rc;
+  if (n == 0) return TR_OK;
+  if (!states) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());
+  const int S = c->K.state_size;
+  const int64_t chunk = shoot_io_chunk(c);       // the staging of tr_fk_loaded_batch: states, load rows, guess, strains, flags
+  if ((rc = shoot_reserve_io(c, n, false)) || (rc = ensure_staging(c, std::min(n, chunk)))) return rc;
+  tr_ctx::ShootDev &k = c->shoot;
+  int64_t rounds[2] = {0, 0};
+  for (int64_t off = 0; off < n; off += chunk) {
+    const int64_t m = std::min(chunk, n - off);
+    int64_t r2[2] = {0, 0};
+    if ((rc = upload_rows(c, k.io_states, states, S, off, m, S))) return rc;
+    if (wrench && (rc = upload_rows(c, k.io_w, wrench, wrench_ld, off, m, 6))) return rc;
+    if (dist && (rc = upload_rows(c, k.io_d, dist, dist_ld, off, m, 6))) return rc;
+    if (guess && (rc = upload_rows(c, k.io_g, guess, 6, off, m, 6))) return rc;
+    if ((rc = loaded_tips_run(c, prm, k.io_states, m, wrench ? k.io_w : nullptr, wrench_ld ? 6 : 0, dist ? k.io_d : nullptr, dist_ld ? 6 : 0,
+                              guess ? k.io_g : nullptr, c->ws.tips, k.io_conv, k.io_vu, r2))) return rc;
+    rounds[0] += r2[0]; rounds[1] += r2[1];
+    if (tips) HIP_TRY(c, hipMemcpy(tips + 3 * off, c->ws.tips, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if ((rc = download_rows(c, converged, k.io_conv, off, m)) || (rc = download_rows(c, vu0, k.io_vu, off, m, 6))) return rc;
+  }
+  if (rounds_out) { rounds_out[0] = rounds[0]; rounds_out[1] = rounds[1]; }
+  return TR_OK;
+}
 
 int tr_sample_valid_vertices_loaded_dev(tr_ctx *c, const tr_shoot_params *shoot, const tr_edge_loads *loads, uint64_t seed, uint64_t first_candidate,
                                         const double *lo, const double *hi, int64_t n_want, int64_t max_candidates, double *d_states, double *d_tips,

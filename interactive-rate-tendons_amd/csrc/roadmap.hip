@@ -53,6 +53,7 @@
 #include "roadmap_kernel.hpp"
 #include "tipq_kernel.hpp"
 #include "stateq_kernel.hpp"
+#include "tipq_loaded_kernel.hpp"
 #include "handback_feed.hpp"
 
 namespace {
@@ -205,6 +206,7 @@ struct tr_roadmap {
   // validity bytes in HBM for the life of the roadmap, and one grow-only arena for the arrays of a call
   struct DevTips {
     bool set = false;
+    bool own_tips = false;               // the tips are tr_fk_tips_dev's of the states (unloaded): the loaded tip queries refuse them
     double *d_tips = nullptr, *d_states = nullptr;
     double *d_soa = nullptr;             // the states coordinate by coordinate ([S][V]): what state_knn streams
     uint8_t *d_vstat = nullptr;          // the image of `vstat` the kernel filters by; sent again only when `vstat` differs from `vstat_sent`

@@ -8,6 +8,10 @@
 // started from (:3242-3244, :3276-3287); the graph itself is not edited.  The accurate rule (RMAP_IK_ACCURATE: the *_connect entry
 // points) tries an edge from every state-space neighbour of the IK answer as well (:3237-3244): state_knn on the IK answers ->
 // tipq_pair_rows -> ONE last-valid edge check of all the pairs -> tipq_interp + tr_fk_tips_dev on the pairs -> tipq_select_pairs.
+// On LOADED shapes (the *_loaded entry points; with general_shape installed roadmapIk takes every shape from voxelStateChecker_->fk,
+// :3052, :3187) the same body runs with a TipLoaded evaluator at the three places that differ: ONE tr_ik_loaded_batch_dev ->
+// ONE tr_validate_edges_loaded with last_valid_t -> tipql_live_rows + tr_fk_loaded_tips_dev + tipql_scatter -> tipql_select
+// (tipq_loaded_kernel.hpp), every solve cold.
 namespace {
 
 void free_tips(tr_roadmap *r) {
@@ -79,6 +83,32 @@ struct TipBuffers {
   }
 };
 
+// what the loaded calls (tr_roadmap_ik_batch_loaded ...) keep beside TipBuffers: per slot the IK's equilibrium flag, strains and
+// integrations; per pair the g solve's converged flag and strains; the dense arrays of the live pairs (rows, never planes); outputs
+struct LoadedTipBuffers {
+  uint8_t *eq, *gconv, *convc, *o_flags;
+  int32_t *fkc, *live, *o_ik;
+  double *xvu, *gvu, *gl, *gw, *gd, *tipc, *vuc, *o_vu;
+  void carve(TipArena &a, int64_t n, int k, int S, int kc) {
+    const size_t m = (size_t)n * (size_t)k, mp = m * (size_t)(kc > 0 ? kc + 1 : 1);
+    eq = a.take<uint8_t>(m); fkc = a.take<int32_t>(m); xvu = a.take<double>(m * 6);
+    gconv = a.take<uint8_t>(mp); gvu = a.take<double>(mp * 6); live = a.take<int32_t>(mp);
+    gl = a.take<double>(mp * S); gw = a.take<double>(mp * 6); gd = a.take<double>(mp * 6);
+    tipc = a.take<double>(mp * 3); convc = a.take<uint8_t>(mp); vuc = a.take<double>(mp * 6);
+    o_vu = a.take<double>((size_t)n * 6); o_ik = a.take<int32_t>((size_t)n); o_flags = a.take<uint8_t>((size_t)n);
+  }
+};
+
+// The evaluator of the three places where the loaded rules differ (the IK batch, the pair check, the tips of g): null = the unloaded
+// rules with their launches, order and bits.  One load set per call; every solve is cold.
+struct TipLoaded {
+  const tr_shoot_params *shoot;
+  tr_edge_loads loads;                  // warm_start = 0
+  trk::TipqLoadsK k;                    // the same set as the kernels take it
+  double *vu0;                          // optional outputs
+  int64_t *counts;
+};
+
 constexpr int kTipQ = 4, kTipG = 4;     // requests per wave, tiles in flight (tip_knn)
 
 // Slices of the tip array: a batch that fills the device with request groups streams it whole; a handful of requests cuts it so
@@ -106,17 +136,20 @@ int tip_arena(tr_roadmap *r, size_t bytes) {
   return TR_OK;
 }
 
-int tip_buffers(tr_roadmap *r, int64_t n, int k, bool full, TipBuffers &b, int &slices, int kc = 0, int *c_slices = nullptr) {
+int tip_buffers(tr_roadmap *r, int64_t n, int k, bool full, TipBuffers &b, int &slices, int kc = 0, int *c_slices = nullptr,
+                LoadedTipBuffers *lb = nullptr) {
   slices = tip_slices(n, r->V);
   const int cs = kc > 0 ? state_slices(r, n * k) : 1;
   if (c_slices) *c_slices = cs;
   TipArena size;
   TipBuffers dummy;
   dummy.carve(size, n, k, r->S, slices, full, kc, cs);
+  if (lb) { LoadedTipBuffers dl; dl.carve(size, n, k, r->S, kc); }
   if (const int rc = tip_arena(r, size.used)) return rc;
   TipArena a;
   a.base = r->dt.arena;
   b.carve(a, n, k, r->S, slices, full, kc, cs);
+  if (lb) lb->carve(a, n, k, r->S, kc);
   return TR_OK;
 }
 
@@ -218,9 +251,10 @@ unsigned tipq_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 // Rules 1 - 5 behind the lock, for both connection rules; every output may be null.  connect null or k_connect 0: every candidate
 // slot has ONE source, the vertex IK started from (rules 3 - 5; ik_vertex = neighbor_vertex); otherwise the k_connect state-space
 // neighbours of its IK answer and that vertex (rules 3' - 5').  count_stats: this is a *_connect call, dt.connect_stats follows it.
+// L: the loaded rules' evaluator (2L - 5'L), null for the unloaded ones.
 int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
                      bool count_stats, const double *requests, int64_t n, double *controls, double *tips, double *error,
-                     int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t) {
+                     int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t, const TipLoaded *L = nullptr) {
   const tr_tip_query_params def{5, 1e-4, tr_ik_params{100, 0.1, 1e-9, 1e-4, 1e-4, 1e-6}};      // roadmapIk's defaults and what it hands to IK
   const tr_tip_query_params &p = params ? *params : def;
   const tr_space_params spd{0.02, 0.01, 0.0001};                                                // Problem.h:59-62
@@ -246,8 +280,10 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   // 1. neighbours
   if ((rc = tips_validity(r))) return rc;
   TipBuffers b;
+  LoadedTipBuffers lb{};
   int slices = 1, c_slices = 1;
-  if ((rc = tip_buffers(r, n, k, true, b, slices, kc, &c_slices))) return rc;
+  if ((rc = tip_buffers(r, n, k, true, b, slices, kc, &c_slices, L ? &lb : nullptr))) return rc;
+  int64_t n_integrations = 0, n_no_equilibrium = 0, n_g_unconverged = 0;
   RM_HIP(r, hipMemcpyAsync(b.req, requests, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, nullptr));
   if ((rc = launch_nearest(r, b.req, n, k, slices, b, b.nbr, nullptr))) return rc;
   // 2. IK from every neighbour, one batch
@@ -257,7 +293,18 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   std::vector<int32_t> nbr((size_t)m);
   RM_HIP(r, hipMemcpy(nbr.data(), b.nbr, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));     // (synchronises: the nearest phase ends here)
   lap(0);
-  if ((rc = tr_ik_batch_dev(r->ctx, &p.ik, b.starts, m, b.goals, 3, nullptr, nullptr, b.x, b.xtip, b.err, nullptr, nullptr, &d.st_ik_rounds, nullptr)))
+  if (L) {
+    int64_t rounds[2] = {0, 0};
+    if ((rc = tr_ik_loaded_batch_dev(r->ctx, &p.ik, L->shoot, &L->loads, b.starts, m, b.goals, 3, nullptr, nullptr, nullptr, b.x, b.xtip, b.err,
+                                     nullptr, lb.fkc, lb.xvu, lb.eq, rounds, nullptr))) return rfail(r, rc, tr_last_error(r->ctx));
+    d.st_ik_rounds = rounds[0];
+    std::vector<uint8_t> eq((size_t)m);
+    std::vector<int32_t> fkc((size_t)m);
+    RM_HIP(r, hipMemcpy(eq.data(), lb.eq, (size_t)m, hipMemcpyDeviceToHost));
+    RM_HIP(r, hipMemcpy(fkc.data(), lb.fkc, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t s = 0; s < m; s++)
+      if (nbr[(size_t)s] >= 0) { n_no_equilibrium += eq[(size_t)s] == 0; n_integrations += fkc[(size_t)s]; }
+  } else if ((rc = tr_ik_batch_dev(r->ctx, &p.ik, b.starts, m, b.goals, 3, nullptr, nullptr, b.x, b.xtip, b.err, nullptr, nullptr, &d.st_ik_rounds, nullptr)))
     return rfail(r, rc, tr_last_error(r->ctx));
   // 3. partial edges: checkMotion(states[N], x, last_valid) on the slots that hold a neighbour (host-array form: Q k S doubles each way)
   std::vector<double> x((size_t)m * S);
@@ -290,7 +337,13 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
       std::memcpy(&ea[(size_t)i * S], &r->states[(size_t)src[(size_t)live[(size_t)i]] * S], (size_t)S * sizeof(double));
       std::memcpy(&eb[(size_t)i * S], &x[(size_t)(live[(size_t)i] / P) * S], (size_t)S * sizeof(double));
     }
-    if ((rc = tr_validate_edges_last_valid(r->ctx, &space, ea.data(), eb.data(), ml, bits.data(), et.data(), nullptr))) return rfail(r, rc, tr_last_error(r->ctx));
+    if (L) {
+      int64_t ni = 0;
+      if ((rc = tr_validate_edges_loaded(r->ctx, &space, L->shoot, &L->loads, ea.data(), eb.data(), ml, bits.data(), et.data(), nullptr, nullptr,
+                                         nullptr, &ni))) return rfail(r, rc, tr_last_error(r->ctx));
+      n_integrations += ni;
+    } else if ((rc = tr_validate_edges_last_valid(r->ctx, &space, ea.data(), eb.data(), ml, bits.data(), et.data(), nullptr)))
+      return rfail(r, rc, tr_last_error(r->ctx));
     for (int64_t i = 0; i < ml; i++) {
       ok[(size_t)live[(size_t)i]] = (uint8_t)((bits[(size_t)i >> 6] >> (i & 63)) & 1);
       t[(size_t)live[(size_t)i]] = et[(size_t)i];
@@ -302,8 +355,34 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   // 4 - 5. the last valid state of every pair, its tip, and the choice
   hipLaunchKernelGGL(trk::tipq_interp, dim3(tipq_grid(mp)), dim3(256), 0, nullptr, d_a, d_b, (const double *)b.t, mp, S, r->rot ? r->NT : -1, b.g);
   RM_HIP(r, hipGetLastError());
-  if ((rc = fk_tips_chunked(r, b.g, mp, b.gtip))) return rc;
-  if (kc > 0)
+  if (L) {
+    // 5L: one cold loaded solve per live pair, dense; a dead pair has converged = 0
+    RM_HIP(r, hipMemsetAsync(lb.gconv, 0, (size_t)mp, nullptr));
+    if (ml > 0) {
+      std::vector<int32_t> live32((size_t)ml);
+      for (int64_t i = 0; i < ml; i++) live32[(size_t)i] = (int32_t)live[(size_t)i];
+      RM_HIP(r, hipMemcpy(lb.live, live32.data(), (size_t)ml * sizeof(int32_t), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(trk::tipql_live_rows, dim3(tipq_grid(ml)), dim3(256), 0, nullptr, (const double *)b.g, (const int32_t *)lb.live, ml, S,
+                         r->rot ? r->NT : -1, L->k, lb.gl, lb.gw, lb.gd);
+      RM_HIP(r, hipGetLastError());
+      int64_t rounds[2] = {0, 0};
+      if ((rc = tr_fk_loaded_tips_dev(r->ctx, L->shoot, lb.gl, ml, lb.gw, 6, lb.gd, 6, nullptr, lb.tipc, lb.convc, lb.vuc, rounds, nullptr)))
+        return rfail(r, rc, tr_last_error(r->ctx));
+      n_integrations += rounds[1];
+      hipLaunchKernelGGL(trk::tipql_scatter, dim3(tipq_grid(ml)), dim3(256), 0, nullptr, (const int32_t *)lb.live, ml, (const double *)lb.tipc,
+                         (const uint8_t *)lb.convc, (const double *)lb.vuc, b.gtip, lb.gconv, lb.gvu);
+      RM_HIP(r, hipGetLastError());
+      std::vector<uint8_t> conv((size_t)ml);
+      RM_HIP(r, hipMemcpy(conv.data(), lb.convc, (size_t)ml, hipMemcpyDeviceToHost));
+      for (const uint8_t c : conv) n_g_unconverged += c == 0;
+    }
+    hipLaunchKernelGGL(trk::tipql_select, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, P, S,
+                       p.tolerance, (const int32_t *)(kc > 0 ? b.src : b.nbr), (const double *)b.x, (const double *)b.xtip, (const double *)b.err,
+                       (const uint8_t *)lb.eq, (const double *)lb.xvu, (const uint8_t *)b.ok, (const double *)b.t, (const double *)b.g,
+                       (const double *)b.gtip, (const uint8_t *)lb.gconv, (const double *)lb.gvu, b.o_controls, b.o_tip, b.o_err, b.o_nbr, lb.o_ik,
+                       b.o_outcome, b.o_t, lb.o_vu, lb.o_flags);
+  } else if ((rc = fk_tips_chunked(r, b.g, mp, b.gtip))) return rc;
+  else if (kc > 0)
     hipLaunchKernelGGL(trk::tipq_select_pairs, dim3(tipq_grid(n)), dim3(256), 0, nullptr, (const int32_t *)b.nbr, (const double *)b.req, n, k, P, S,
                        p.tolerance, (const int32_t *)b.src, (const double *)b.x, (const double *)b.xtip, (const double *)b.err, (const uint8_t *)b.ok,
                        (const double *)b.t, (const double *)b.g, (const double *)b.gtip, b.o_controls, b.o_tip, b.o_err, b.o_nbr, b.o_ik,
@@ -317,16 +396,17 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
   if (tips) RM_HIP(r, hipMemcpyAsync(tips, b.o_tip, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (error) RM_HIP(r, hipMemcpyAsync(error, b.o_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (neighbor_vertex) RM_HIP(r, hipMemcpyAsync(neighbor_vertex, b.o_nbr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
-  if (ik_vertex) RM_HIP(r, hipMemcpyAsync(ik_vertex, kc > 0 ? b.o_ik : b.o_nbr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (ik_vertex) RM_HIP(r, hipMemcpyAsync(ik_vertex, L ? lb.o_ik : (kc > 0 ? b.o_ik : b.o_nbr), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+  if (L && L->vu0) RM_HIP(r, hipMemcpyAsync(L->vu0, lb.o_vu, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   if (outcome) RM_HIP(r, hipMemcpyAsync(outcome, b.o_outcome, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
   if (last_valid_t) RM_HIP(r, hipMemcpyAsync(last_valid_t, b.o_t, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, nullptr));
   RM_HIP(r, hipStreamSynchronize(nullptr));
   if (count_stats) {
     // [0] pairs checked, [1] REACHED, [2] connection vertex != IK vertex, [3] REACHED where the one-edge rule is not
     d.connect_stats[0] = ml;
-    if (kc > 0) {
+    if (kc > 0 || L) {
       std::vector<uint8_t> fl((size_t)n);
-      RM_HIP(r, hipMemcpy(fl.data(), b.o_flags, (size_t)n, hipMemcpyDeviceToHost));
+      RM_HIP(r, hipMemcpy(fl.data(), L ? lb.o_flags : b.o_flags, (size_t)n, hipMemcpyDeviceToHost));
       for (const uint8_t f : fl) {
         d.connect_stats[1] += (f & TRK_TIPQ_FLAG_REACHED) != 0; d.connect_stats[2] += (f & TRK_TIPQ_FLAG_MOVED) != 0;
         d.connect_stats[3] += (f & TRK_TIPQ_FLAG_GAINED) != 0;
@@ -337,6 +417,7 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
       for (const int32_t o : oc) d.connect_stats[1] += o == TR_TIPQ_REACHED;
     }
   }
+  if (L && L->counts) { L->counts[0] = ml; L->counts[1] = n_no_equilibrium; L->counts[2] = n_g_unconverged; L->counts[3] = n_integrations; }
   lap(3);
   return TR_OK;
 }
@@ -344,15 +425,35 @@ int tip_query_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_quer
 int solve_tips_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
                       bool count_stats, const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls,
                       double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
-                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats);
+                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats, const TipLoaded *L = nullptr);
 
-}  // namespace
+// What the loaded entry points check before rules 1 - 5, in this order: the frame, the robot and the solver's parameters (shoot_check's
+// and shoot_params' wording, through an empty tr_fk_loaded_tips_dev), an empty call, the roadmap's tips.  `empty`: nothing to do.
+int tip_loaded_begin(tr_roadmap *r, const tr_shoot_params *shoot, const tr_edge_loads *loads, int64_t n, double *vu0, int64_t *counts,
+                     TipLoaded &L, bool &empty) {
+  empty = false;
+  L = TipLoaded{};
+  L.shoot = shoot; L.vu0 = vu0; L.counts = counts;
+  if (counts) for (int i = 0; i < 4; i++) counts[i] = 0;
+  if (loads) {
+    if (loads->frame != TR_LOAD_FRAME_BASE && loads->frame != TR_LOAD_FRAME_WORLD)
+      return rfail(r, TR_ERR_INVALID_ARG, "bad argument (frame: TR_LOAD_FRAME_BASE or TR_LOAD_FRAME_WORLD)");
+    L.loads = *loads;
+  }
+  L.loads.warm_start = 0;
+  for (int q = 0; q < 6; q++) { L.k.wrench[q] = L.loads.wrench[q]; L.k.dist[q] = L.loads.dist[q]; }
+  L.k.world = L.loads.frame == TR_LOAD_FRAME_WORLD;
+  if (const int rc = tr_fk_loaded_tips_dev(r->ctx, shoot, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+    return rfail(r, rc, tr_last_error(r->ctx));
+  if (n == 0) { empty = true; return TR_OK; }
+  if (r->dt.set && r->dt.own_tips)
+    return rfail(r, TR_ERR_INVALID_ARG, "the roadmap's tips are those of UNLOADED shapes (tr_roadmap_set_tips computed them with tr_fk_tips_dev): "
+                                        "pass loaded tips to tr_roadmap_set_tips or call tr_roadmap_set_tips_loaded");
+  return TR_OK;
+}
 
-extern "C" {
-
-int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *present_bits) {
-  if (!r) return TR_ERR_INVALID_ARG;
-  RmLock lock_(r);
+// tr_roadmap_set_tips behind the lock
+int set_tips_locked(tr_roadmap *r, const double *tips, const uint64_t *present_bits) {
   RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
   free_tips(r);
   auto &d = r->dt;
@@ -385,7 +486,94 @@ int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *prese
   RM_HIP(r, hipMemcpy(d.d_present, d.present.data(), nw * sizeof(uint64_t), hipMemcpyHostToDevice));
   d.vstat_sent.clear();                                     // (differs from `vstat` unless the roadmap is empty: the first call sends it)
   d.set = true;
+  d.own_tips = tips == nullptr;
   return TR_OK;
+}
+
+// a device array of the call, handed back when the call ends
+struct TipScratch {
+  void *p = nullptr;
+  ~TipScratch() { if (p) dev_cache().release(p); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int tr_roadmap_set_tips(tr_roadmap *r, const double *tips, const uint64_t *present_bits) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  return set_tips_locked(r, tips, present_bits);
+}
+
+int tr_roadmap_set_tips_loaded(tr_roadmap *r, const tr_shoot_params *shoot, const tr_edge_loads *loads, const uint64_t *present_bits) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  TipLoaded L;
+  bool empty;
+  int rc;
+  if ((rc = tip_loaded_begin(r, shoot, loads, 0, nullptr, nullptr, L, empty))) return rc;
+  const int64_t V = r->V;
+  const int S = r->S;
+  std::vector<double> tips((size_t)std::max<int64_t>(V, 1) * 3, 0.0);
+  std::vector<uint64_t> present((size_t)V / 64 + 1, 0);
+  for (int64_t v = 0; v < V; v++)
+    if (!present_bits || ((present_bits[v >> 6] >> (v & 63)) & 1)) present[(size_t)v >> 6] |= (uint64_t)1 << (v & 63);
+  if (V > 0) {
+    RM_HIP(r, hipSetDevice(tr_device(r->ctx)));
+    const int dev = tr_device(r->ctx);
+    TipScratch st, w, dd, tp, cv;
+    RM_HIP(r, dev_cache().alloc(dev, &st.p, (size_t)V * S * sizeof(double)));
+    RM_HIP(r, dev_cache().alloc(dev, &w.p, (size_t)V * 6 * sizeof(double)));
+    RM_HIP(r, dev_cache().alloc(dev, &dd.p, (size_t)V * 6 * sizeof(double)));
+    RM_HIP(r, dev_cache().alloc(dev, &tp.p, (size_t)V * 3 * sizeof(double)));
+    RM_HIP(r, dev_cache().alloc(dev, &cv.p, (size_t)V));
+    RM_HIP(r, hipMemcpy(st.p, r->states.data(), (size_t)V * S * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(trk::tipql_load_rows, dim3(tipq_grid(V)), dim3(256), 0, nullptr, (const double *)st.p, V, S, r->rot ? r->NT : -1, L.k,
+                       (double *)w.p, (double *)dd.p);
+    RM_HIP(r, hipGetLastError());
+    if ((rc = tr_fk_loaded_tips_dev(r->ctx, shoot, (const double *)st.p, V, (const double *)w.p, 6, (const double *)dd.p, 6, nullptr, (double *)tp.p,
+                                    (uint8_t *)cv.p, nullptr, nullptr, nullptr))) return rfail(r, rc, tr_last_error(r->ctx));
+    std::vector<uint8_t> conv((size_t)V);
+    RM_HIP(r, hipMemcpy(tips.data(), tp.p, (size_t)V * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    RM_HIP(r, hipMemcpy(conv.data(), cv.p, (size_t)V, hipMemcpyDeviceToHost));
+    for (int64_t v = 0; v < V; v++)
+      if (!conv[(size_t)v]) present[(size_t)v >> 6] &= ~((uint64_t)1 << (v & 63));      // no equilibrium: no tip
+  }
+  return set_tips_locked(r, tips.data(), present.data());
+}
+
+int tr_roadmap_ik_batch_loaded(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                               const tr_shoot_params *shoot, const tr_edge_loads *loads, const double *requests, int64_t n, double *controls,
+                               double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome,
+                               double *last_valid_t, double *vu0, int64_t *counts) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  TipLoaded L;
+  bool empty;
+  if (const int rc = tip_loaded_begin(r, shoot, loads, n, vu0, counts, L, empty)) return rc;
+  if (empty) return TR_OK;
+  return tip_query_locked(r, sp, params, connect, true, requests, n, controls, tips, error, neighbor_vertex, ik_vertex, outcome, last_valid_t, &L);
+}
+
+int tr_roadmap_solve_tips_loaded(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
+                                 const tr_shoot_params *shoot, const tr_edge_loads *loads, const int32_t *starts, const double *requests, int64_t n,
+                                 int32_t n_threads, double *controls, double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex,
+                                 int32_t *outcome, double *last_valid_t, double *vu0, int64_t *counts, int32_t *status, double *cost,
+                                 int64_t *path_offsets, tr_roadmap_stats *stats) {
+  if (!r) return TR_ERR_INVALID_ARG;
+  RmLock lock_(r);
+  TipLoaded L;
+  bool empty;
+  if (const int rc = tip_loaded_begin(r, shoot, loads, n, vu0, counts, L, empty)) return rc;
+  if (empty) {
+    reset_last_solve(r, 0);
+    if (path_offsets) path_offsets[0] = 0;
+    if (stats) *stats = tr_roadmap_stats{0, 0, 0, 0};
+    return TR_OK;
+  }
+  return solve_tips_locked(r, sp, params, connect, true, starts, requests, n, n_threads, controls, tips, error, neighbor_vertex, ik_vertex, outcome,
+                           last_valid_t, status, cost, path_offsets, stats, &L);
 }
 
 int tr_roadmap_nearest_tips_dev(tr_roadmap *r, const double *d_requests, int64_t n, int32_t k, int32_t *d_vertices, double *d_dist2) {
@@ -514,7 +702,7 @@ namespace {
 int solve_tips_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_query_params *params, const tr_tip_connect_params *connect,
                       bool count_stats, const int32_t *starts, const double *requests, int64_t n, int32_t n_threads, double *controls,
                       double *tips, double *error, int32_t *neighbor_vertex, int32_t *ik_vertex, int32_t *outcome, double *last_valid_t,
-                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats) {
+                      int32_t *status, double *cost, int64_t *path_offsets, tr_roadmap_stats *stats, const TipLoaded *L) {
   if (n < 0 || (n > 0 && (!starts || !requests || !status || !path_offsets))) return rfail(r, TR_ERR_INVALID_ARG, "bad argument");
   reset_last_solve(r, n);
   if (path_offsets) path_offsets[0] = 0;
@@ -528,7 +716,7 @@ int solve_tips_locked(tr_roadmap *r, const tr_space_params *sp, const tr_tip_que
   if (!neighbor_vertex) { own_nbr.resize((size_t)n); neighbor_vertex = own_nbr.data(); }
   if (!outcome) { own_outcome.resize((size_t)n); outcome = own_outcome.data(); }
   int rc;
-  if ((rc = tip_query_locked(r, sp, params, connect, count_stats, requests, n, controls, tips, error, neighbor_vertex, ik_vertex, outcome, last_valid_t)))
+  if ((rc = tip_query_locked(r, sp, params, connect, count_stats, requests, n, controls, tips, error, neighbor_vertex, ik_vertex, outcome, last_valid_t, L)))
     return rc;
   if (n == 0) return TR_OK;
   // rule 6: the roadmap query to the connection vertex; a request without a neighbour has no goal

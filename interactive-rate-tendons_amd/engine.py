@@ -347,6 +347,48 @@ class Engine:
             opt(d_fk_calls, torch.int32, n, "d_fk_calls"), C.byref(rounds), self._stream_ptr(stream)))
         return int(rounds.value)
 
+    def fk_loaded_tips(self, states, wrench=None, dist=None, frame="base", guess=None, **shoot):
+        """The tips of LOADED shapes alone (tr_fk_loaded_tips): fk_loaded_batch's shooting and the last point of its shape, bit for
+        bit, without the shapes crossing the bus.  wrench / dist: (n, 6) rows as fk_loaded_batch takes them (frame must then be
+        'base'), or ONE (6,) set in `frame` -- 'world' turns it per state, the rows of sample_loads.  guess (n, 6) or None: cold.
+        **shoot: fk_loaded_batch's solver arguments.  Returns dict(tips, converged, vu0, rounds, n_integrations)."""
+        st = self._states(states)
+        n = st.shape[0]
+        if frame not in ("base", "world"):
+            raise L.InvalidArgument("frame must be 'base' or 'world'")
+        if frame == "world":
+            wrench, dist = self.sample_loads(st, wrench, dist, "world")
+        w, wld = self._load_rows(wrench, n, "wrench")
+        d, dld = self._load_rows(dist, n, "dist")
+        g = None
+        if guess is not None:
+            g = _f64(guess)
+            if g.shape != (n, 6):
+                raise L.InvalidArgument("guess must be (n, 6)")
+        prm = self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+        tips, vu0, conv = np.empty((n, 3)), np.empty((n, 6)), np.empty(n, dtype=np.uint8)
+        rounds = (C.c_int64 * 2)()
+        opt = lambda a: _dp(a) if a is not None else None
+        L.check(self._ctx, self.lib.tr_fk_loaded_tips(self._ctx, C.byref(prm), _dp(st), n, opt(w), wld, opt(d), dld, opt(g), _dp(tips),
+                                                      conv.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(vu0), rounds))
+        return dict(tips=tips, converged=conv.astype(bool), vu0=vu0, rounds=int(rounds[0]), n_integrations=int(rounds[1]))
+
+    def fk_loaded_tips_dev(self, d_states, n, d_tips, d_wrench=None, wrench_ld=6, d_dist=None, dist_ld=6, d_guess=None, d_conv=None,
+                           d_vu0=None, stream=None, **shoot):
+        """tr_fk_loaded_tips_dev: device tensors in and out (wrench_ld / dist_ld = 0: one row for all); returns (rounds, integrations)."""
+        torch = _torch()
+        f64 = torch.float64
+        opt = lambda t, dt, m, nm: self._check_dev(t, dt, m, nm) if t is not None else None
+        rows = lambda rl: 6 if rl == 0 else (n - 1) * rl + 6
+        prm = self._shoot_params(**{**self._SHOOT_DEFAULTS, **shoot})
+        rounds = (C.c_int64 * 2)()
+        L.check(self._ctx, self.lib.tr_fk_loaded_tips_dev(
+            self._ctx, C.byref(prm), self._check_dev(d_states, f64, n * self.state_size, "d_states"), int(n),
+            opt(d_wrench, f64, rows(wrench_ld), "d_wrench"), int(wrench_ld), opt(d_dist, f64, rows(dist_ld), "d_dist"), int(dist_ld),
+            opt(d_guess, f64, 6 * n, "d_guess"), opt(d_tips, f64, 3 * n, "d_tips"), opt(d_conv, torch.uint8, n, "d_conv"),
+            opt(d_vu0, f64, 6 * n, "d_vu0"), rounds, self._stream_ptr(stream)))
+        return int(rounds[0]), int(rounds[1])
+
     def validate_loaded(self, states, wrench=None, dist=None, guess=None, check_voxels=True, **shoot):
         """isValid of the LOADED shapes: fk_loaded_batch_dev into validate_shapes_dev (converged = the shooting's, tendon-length
         limits, self-collision, the backbone or sphere sweep against the grid).  Returns dict(valid, bits, flags)."""

@@ -732,6 +732,89 @@ class VoxelCachedLazyPRM:
         o.update(status=status, cost=cost, path_offsets=off, path_vertices=pv, paths=_Paths(pv, off))
         return o
 
+    # ---- tip-goal queries on LOADED shapes (tr_roadmap_*_loaded, include/tendon_hip.h: rules 1L - 5'L) --------------------------
+    def _loaded_args(self, wrench, dist, frame, shoot):
+        """(tr_edge_loads, tr_shoot_params or None): one load set per call; shoot None = every solver's own defaults, a dict =
+        fk_loaded_batch's arguments by name, handed to the IK's shooting, the pair check and the solves of rule 5L alike."""
+        eng = self.engine
+        ld = eng._edge_loads(wrench, dist, frame, False)
+        if shoot is None:
+            return ld, None
+        bad = set(shoot) - set(eng._SHOOT_DEFAULTS)
+        if bad:
+            raise TypeError("unknown shooting parameter(s): %s" % ", ".join(sorted(bad)))
+        return ld, eng._shoot_params(**{**eng._SHOOT_DEFAULTS, **shoot})
+
+    def set_tips_loaded(self, wrench=None, dist=None, frame="base", present=None, **shoot):
+        """set_tips with the tips of the vertices' LOADED shapes (tr_roadmap_set_tips_loaded): one cold solve per vertex under its
+        own load rows; a vertex without an equilibrium has no tip.  **shoot: fk_loaded_batch's solver arguments."""
+        C = self._C
+        from .distributed import pack_bits
+        ld, prm = self._loaded_args(wrench, dist, frame, shoot or None)
+        pb = None
+        if present is not None:
+            pr = np.asarray(present, dtype=bool)
+            if pr.shape != (len(self.states),):
+                raise self._L.InvalidArgument("present must be (n_vertices,)")
+            pb = np.ascontiguousarray(pack_bits(pr))
+        self._check(self.lib.tr_roadmap_set_tips_loaded(self._rm, C.byref(prm) if prm is not None else None, C.byref(ld),
+                                                        pb.ctypes.data_as(C.POINTER(C.c_uint64)) if pb is not None else None))
+
+    def _loaded_tip_call(self, starts, requests, wrench, dist, frame, tolerance, k, motion_validator, ik, shoot, connect_k,
+                         connect_max_distance, n_threads):
+        C, L_ = self._C, self._L
+        r = self._requests(requests)
+        n = len(r)
+        ld, sprm = self._loaded_args(wrench, dist, frame, shoot)
+        prm, sp = self._tip_params(k, tolerance, ik, motion_validator)
+        cp = L_.TrTipConnectParams(int(connect_k), float(connect_max_distance))
+        o = self._tip_outputs(n)
+        o.update(ik_vertex=np.empty(n, dtype=np.int32), vu0=np.empty((n, 6)), counts=np.zeros(4, dtype=np.int64))
+        dp, i32, i64 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        outs = (o["controls"].ctypes.data_as(dp), o["tip"].ctypes.data_as(dp), o["error"].ctypes.data_as(dp),
+                o["neighbor_vertex"].ctypes.data_as(i32), o["ik_vertex"].ctypes.data_as(i32), o["outcome"].ctypes.data_as(i32),
+                o["last_valid_t"].ctypes.data_as(dp), o["vu0"].ctypes.data_as(dp), o["counts"].ctypes.data_as(i64))
+        head = (self._rm, C.byref(sp), C.byref(prm), C.byref(cp), C.byref(sprm) if sprm is not None else None, C.byref(ld))
+        if starts is None:
+            self._check(self.lib.tr_roadmap_ik_batch_loaded(*head, r.ctypes.data_as(dp), n, *outs))
+        else:
+            s = np.ascontiguousarray(starts, dtype=np.int32).reshape(-1)
+            if len(s) != n:
+                raise L_.InvalidArgument("starts and requests differ in length")
+            status, cost, off = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n + 1, dtype=np.int64)
+            st = L_.TrRoadmapStats()
+            self._check(self.lib.tr_roadmap_solve_tips_loaded(*head, s.ctypes.data_as(i32), r.ctypes.data_as(dp), n, int(n_threads), *outs,
+                                                              status.ctypes.data_as(i32), cost.ctypes.data_as(dp), off.ctypes.data_as(i64),
+                                                              C.byref(st)))
+            pv = np.zeros(int(off[-1]), dtype=np.int32)
+            self._check(self.lib.tr_roadmap_fetch_paths(self._rm, pv.ctypes.data_as(i32), len(pv)))
+            self.stats = dict(rounds=st.rounds, items_checked=st.items_checked, astar_runs=st.astar_runs, expanded=st.expanded)
+            o.update(status=status, cost=cost, path_offsets=off, path_vertices=pv, paths=_Paths(pv, off))
+        if connect_k != 0:
+            o["connect_stats"] = self._connect_stats()
+        else:
+            del o["ik_vertex"]
+        return o
+
+    def roadmap_ik_loaded_batch(self, requests, wrench=None, dist=None, frame="base", tolerance=1e-4, k=5, motion_validator=None, ik=None,
+                                shoot=None, connect_k=0, connect_max_distance=np.inf):
+        """roadmap_ik_batch on LOADED shapes (tr_roadmap_ik_batch_loaded; rules 1L - 5'L in include/tendon_hip.h) under ONE load set:
+        wrench = (F_e, L_e), dist = (f_e, l_e), (6,) each, frame 'base' or 'world' as in validate_edges_loaded.  The roadmap's tips
+        must be loaded tips (create_roadmap under set_loads passes them; set_tips_loaded makes them).  IK, the last-valid edge check
+        and the tip of the last valid state all run on loaded shapes, every solve cold; REACHED needs the IK answer's equilibrium, and
+        a request none of whose candidate states has one ends NO_NEIGHBOR.  shoot: None, or a dict of fk_loaded_batch's solver
+        arguments for all three.  -> roadmap_ik_batch's fields plus vu0 (n, 6: the base strains of `controls`), counts (pairs
+        checked, IK answers without an equilibrium, last-valid states unconverged, integrations), and ik_vertex / connect_stats
+        when connect_k > 0.  The checker-routed calls (roadmap_ik_batch ...) keep refusing a checker with loads."""
+        return self._loaded_tip_call(None, requests, wrench, dist, frame, tolerance, k, motion_validator, ik, shoot, connect_k,
+                                     connect_max_distance, 0)
+
+    def solve_to_tips_loaded(self, starts, requests, wrench=None, dist=None, frame="base", tolerance=1e-4, k=5, motion_validator=None,
+                             ik=None, shoot=None, n_threads=0, connect_k=0, connect_max_distance=np.inf):
+        """solve_to_tips on LOADED shapes: roadmap_ik_loaded_batch, then solveWithRoadmap from starts[q] to the connection vertex."""
+        return self._loaded_tip_call(starts, requests, wrench, dist, frame, tolerance, k, motion_validator, ik, shoot, connect_k,
+                                     connect_max_distance, n_threads)
+
     def search_state_bytes(self):
         """Device memory the graph searches hold for this roadmap between calls (tr_roadmap_search_state_bytes)."""
         b = self._C.c_int64(0)
@@ -785,6 +868,22 @@ def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_valid
     -> dict(hops: per hop the solve_to_tips result plus start_state (C, S), prefix_cost (C,), total_cost (C,), active (C,);
             cost (C,): the sum over the chain's solved hops; solved (C,): every hop solved)."""
     prm._refuse_loaded("chained_plan")
+    return _chain_hops(prm, start_vertex, waypoints, lambda at, req: prm.solve_to_tips(
+        at, req, tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, n_threads=n_threads, connect_k=connect_k,
+        connect_max_distance=connect_max_distance))
+
+
+def chained_plan_loaded(prm, start_vertex, waypoints, wrench=None, dist=None, frame="base", tolerance=1e-4, k=5, motion_validator=None,
+                        ik=None, shoot=None, n_threads=0, connect_k=0, connect_max_distance=np.inf):
+    """chained_plan's loop on LOADED shapes: hop h of every chain is one solve_to_tips_loaded call under the one load set (wrench,
+    dist, frame).  Same result fields; every hop also carries vu0 and counts."""
+    return _chain_hops(prm, start_vertex, waypoints, lambda at, req: prm.solve_to_tips_loaded(
+        at, req, wrench=wrench, dist=dist, frame=frame, tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, shoot=shoot,
+        n_threads=n_threads, connect_k=connect_k, connect_max_distance=connect_max_distance))
+
+
+def _chain_hops(prm, start_vertex, waypoints, solve):
+    """chained_plan's loop; solve(start vertices, requests) answers one hop of the active chains."""
     wp = np.asarray(waypoints, dtype=np.float64)
     if wp.ndim == 2:
         wp = wp[None]
@@ -803,8 +902,7 @@ def chained_plan(prm, start_vertex, waypoints, tolerance=1e-4, k=5, motion_valid
         idx = np.flatnonzero(active)
         res = dict(active=active.copy(), start_state=state.copy(), prefix_cost=np.zeros(C_), total_cost=np.full(C_, np.inf), chains=idx)
         if len(idx):
-            r = prm.solve_to_tips(at[idx], wp[idx, h], tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, n_threads=n_threads,
-                                  connect_k=connect_k, connect_max_distance=connect_max_distance)
+            r = solve(at[idx], wp[idx, h])
             res.update(r)
             ok = r["status"] == L.TR_QUERY_SOLVED
             # the reversed connecting edge of the previous hop

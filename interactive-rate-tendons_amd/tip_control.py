@@ -235,6 +235,12 @@ def tip_compliance_loaded(robot, states, wrench=None, dist=None, frame="base", g
     return dict(compliance=r["compliance"], tips=r["tips"], vu0=r["vu0"], equilibrium=r["equilibrium"])
 
 
+def loaded_tips_batch_device(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, **shoot):
+    """The tips of the LOADED shapes of a batch of states (Engine.fk_loaded_tips: the shapes stay on the device): dict(tips,
+    converged, vu0, rounds, n_integrations).  What a tip-goal loop under load measures its progress with."""
+    return robot.engine(device).fk_loaded_tips(states, wrench=wrench, dist=dist, frame=frame, guess=guess, **shoot)
+
+
 def damped_resolved_rate_update_batch_device(robot, states, v_times_dt, lam=0.1, finite_difference_delta=1e-6, wrench=None, dist=None,
                                              frame="base", device=0):
     """tip_control::damped_resolved_rate_update (tip_control.cpp:418-483) for a batch: the next state of every row of `states` for
