@@ -236,8 +236,9 @@ typedef struct {
  * problem: classical RK4 over t_range(0, L, dL) from p = 0, R = I and base strains (v0, u0) with tendon_deriv's loaded right-hand
  * side (tendon_deriv.cpp:331-332), solved for the six strains by single shooting until the tip balance
  * e = (F_e_est - F_e, L_e_est - L_e) of PointForces::calc_point_forces (TendonRobot.cpp:188-217, routing at s = L) vanishes.
- *   - The distributed load is ONE CONSTANT VECTOR PAIR per problem (gravity).  The reference takes functions of (t, p); a
- *     position-dependent load is not offered.
+ *   - The distributed load is ONE CONSTANT VECTOR PAIR per problem (gravity), times the context's load profile w(s) where one is
+ *     installed (tr_set_load_profile, below).  The reference takes functions of (t, p); a load whose direction varies along the
+ *     backbone, and a position-dependent load, are not offered.
  *   - The optimiser is this library's own Levenberg-Marquardt (tr_ik_batch's, without bounds) with levmar's central-difference
  *     Jacobian (d_j = max(|1e-4 p_j|, delta)) and gain-ratio damping; it is not levmar's code path.  The damping term is
  *     mu diag(J^T J) with mu starting at mu_init (Marquardt's scaling: strains, curvatures, forces and moments put nine decades
@@ -275,6 +276,26 @@ int tr_fk_loaded_batch_dev(tr_ctx *ctx, const tr_shoot_params *params, const dou
                            double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L, double *d_Li, uint8_t *d_converged,
                            int32_t *d_n_points, double *d_vu0_out, double *d_vuL_out, double *d_residual_out, int32_t *d_iters_out,
                            int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
+
+/* A load profile: a scalar weight w(s) along arc length that every loaded call of the context applies to its distributed load.  At
+ * every RK4 stage a problem sees w(s) f_e, w(s) l_e, where (f_e, l_e) is the row the call would use without a profile (per-problem
+ * rows in tr_fk_loaded_batch, the call's one set after its frame handling elsewhere); the tip wrench is not scaled.  This is
+ * f_e(t) = rho(t) g: a mass that varies along the backbone, under gravity.  A load whose DIRECTION varies with s, or any dependence
+ * on the position p, is not offered.
+ *   w is piecewise linear over n_knots >= 1 knots (s[k], w[k]): s strictly increasing and finite, w finite; outside
+ *   [s[0], s[n_knots - 1]] the end value holds; for x in [s[k], s[k+1]]  w = w[k] + (w[k+1] - w[k]) * ((x - s[k]) / (s[k+1] - s[k]))
+ *   in this operation order, in fp64, without contraction, with k the LAST knot at or below x (so a knot's own weight holds at
+ *   the knot exactly).
+ * The host evaluates w once into a table of 1 + 3 n_steps doubles at the abscissae of the RK4 stages, indexed like the routing
+ * table: entry 0 at s = 0; entries 1 + 3k, 1 + 3k + 1, 1 + 3k + 2 at t_k, t_k + h_k * 0.5, t_k + h_k of step k.  The kernels read a
+ * stage's weight from it and form w * f_e[q], w * l_e[q], each product rounded once.
+ * tr_set_load_profile first waits for the context's device work (a queued *_dev call keeps the profile it was issued under), then
+ * installs the table; tr_clear_load_profile removes it (the calls run as without one).  Robots with retraction:
+ * TR_ERR_UNSUPPORTED.  Bad knots or weights: TR_ERR_INVALID_ARG. */
+int tr_set_load_profile(tr_ctx *ctx, int64_t n_knots, const double *s, const double *w);
+int tr_clear_load_profile(tr_ctx *ctx);
+/* The installed table: *n_out = its length (0: no profile installed); table_out (may be NULL) receives min(capacity, *n_out) entries. */
+int tr_get_load_profile(tr_ctx *ctx, double *table_out, int64_t capacity, int64_t *n_out);
 
 /* ---- state validity: StateValidityChecker::isValid -------------------------------------- */
 

@@ -263,6 +263,27 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     return out;
   }
 
+  /// A load profile (tr_set_load_profile): the piecewise-linear weight w(arc length) over the knots (s[k], w[k]) that every loaded
+  /// call of this robot's context applies to its distributed load from now on: general_shape, generalShapeBatch, the loaded tip
+  /// Jacobian, IK and tips, and the loaded checks of a checker built on this robot.  The tip wrench is not scaled.  Knots that are
+  /// not strictly increasing, a non-finite number or sizes that differ: std::invalid_argument; a retraction-enabled robot:
+  /// std::runtime_error.
+  void set_load_profile(const std::vector<double> &s, const std::vector<double> &w) const {
+    if (s.size() != w.size()) throw std::invalid_argument("load profile: one weight per knot");
+    tr_ctx *c = context();
+    check(c, tr_set_load_profile(c, (int64_t)s.size(), s.data(), w.data()));
+  }
+  void clear_load_profile() const { tr_ctx *c = context(); check(c, tr_clear_load_profile(c)); }
+  /// the installed table of weights at the RK4 stages' abscissae (tr_get_load_profile); empty: no profile installed
+  std::vector<double> load_profile_table() const {
+    tr_ctx *c = context();
+    int64_t n = 0;
+    check(c, tr_get_load_profile(c, nullptr, 0, &n));
+    std::vector<double> out((size_t)n);
+    if (n > 0) check(c, tr_get_load_profile(c, out.data(), n, &n));
+    return out;
+  }
+
   /// tip_jacobian_batch on the shapes of generalShapeBatch (tr_tip_jacobian_loaded): one shooting solve and 13 + 2 S integrations
   /// per state.  `wrench` holds (F_e, L_e), `dist` (f_e, l_e) per unit length, 6 values each or empty (zero), ONE set per call;
   /// `guess` holds n rows (v, u) or is empty.  rounds (optional): shooting rounds.
@@ -655,16 +676,30 @@ class VoxelBackboneValidityChecker {
   /// wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, 6 values each (empty: zero); world: the loads are fixed behind the
   /// state's rotation (every sample's rows are turned by Rz(-theta)), else before it (tr_fk_loaded_batch's frame)
   void setLoads(const std::vector<double> &wrench, const std::vector<double> &dist, bool world = false, bool warm_start = false) {
-    if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6))
-      throw std::invalid_argument("wrench and dist hold 6 values each: one load set");
-    loads_ = tr_edge_loads{};
-    for (size_t q = 0; q < wrench.size(); q++) loads_.wrench[q] = wrench[q];
-    for (size_t q = 0; q < dist.size(); q++) loads_.dist[q] = dist[q];
-    loads_.frame = world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
-    loads_.warm_start = warm_start ? 1 : 0;
-    has_loads_ = true;
+    check_load_sizes(wrench, dist);
+    if (has_profile_) check(ctx_, tr_clear_load_profile(ctx_));     // (a profile belongs to the setLoads that gave it)
+    has_profile_ = false;
+    store_loads(wrench, dist, world, warm_start);
   }
-  void clearLoads() { has_loads_ = false; }
+  /// the same with a load profile (tr_set_load_profile) on `dist`: the weight w(arc length) over the knots (profile_s[k],
+  /// profile_w[k]), installed on this checker's context until clearLoads() or the next setLoads.  A call that throws (sizes, bad
+  /// knots: std::invalid_argument; a retraction robot: std::runtime_error) leaves the checker's loads and profile as they were: the
+  /// profile is checked and installed before the load set is replaced.
+  void setLoads(const std::vector<double> &wrench, const std::vector<double> &dist, const std::vector<double> &profile_s,
+                const std::vector<double> &profile_w, bool world = false, bool warm_start = false) {
+    if (profile_s.size() != profile_w.size()) throw std::invalid_argument("load profile: one weight per knot");
+    check_load_sizes(wrench, dist);
+    check(ctx_, tr_set_load_profile(ctx_, (int64_t)profile_s.size(), profile_s.data(), profile_w.data()));
+    has_profile_ = true;
+    store_loads(wrench, dist, world, warm_start);
+  }
+  void clearLoads() {
+    has_loads_ = false;
+    if (has_profile_) check(ctx_, tr_clear_load_profile(ctx_));
+    has_profile_ = false;
+  }
+  /// true while a setLoads with a profile is in force
+  bool hasLoadProfile() const { return has_profile_; }
   /// the load set, or nullptr when none is set
   const tr_edge_loads *loads() const { return has_loads_ ? &loads_ : nullptr; }
 
@@ -696,7 +731,19 @@ class VoxelBackboneValidityChecker {
   const tendon::TendonRobot &robot_;
   tr_ctx *ctx_;
   tr_edge_loads loads_{};
-  bool has_loads_ = false;
+  bool has_loads_ = false, has_profile_ = false;
+  static void check_load_sizes(const std::vector<double> &wrench, const std::vector<double> &dist) {
+    if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6))
+      throw std::invalid_argument("wrench and dist hold 6 values each: one load set");
+  }
+  void store_loads(const std::vector<double> &wrench, const std::vector<double> &dist, bool world, bool warm_start) {
+    loads_ = tr_edge_loads{};
+    for (size_t q = 0; q < wrench.size(); q++) loads_.wrench[q] = wrench[q];
+    for (size_t q = 0; q < dist.size(); q++) loads_.dist[q] = dist[q];
+    loads_.frame = world ? TR_LOAD_FRAME_WORLD : TR_LOAD_FRAME_BASE;
+    loads_.warm_start = warm_start ? 1 : 0;
+    has_loads_ = true;
+  }
 };
 
 /// VoxelValidityChecker (motion-planning/VoxelValidityChecker.h:18-26): the same interface; the robot is

@@ -11,7 +11,7 @@ There is no CPU fallback: without the built library or without a GPU the compute
 from . import _lib
 from ._lib import (TendonHipError, InvalidArgument, OutOfRange, DomainError, LengthError, HipError, Unsupported,
                    build, LIB_PATH)
-from .engine import Engine, unpack_bits
+from .engine import Engine, unpack_bits, load_profile_table
 from .tendon import BackboneSpecs, TendonSpecs, TendonResult, TendonRobot, PointForces
 from .collision import VoxelOctree
 from .motion_planning import (VoxelEnvironment, VoxelBackboneValidityChecker, VoxelValidityChecker, VoxelBackboneMotionValidator,
@@ -21,7 +21,7 @@ from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan, chained_p
 
 __all__ = [
     "TendonHipError", "InvalidArgument", "OutOfRange", "DomainError", "LengthError", "HipError", "Unsupported",
-    "build", "LIB_PATH", "Engine", "unpack_bits", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot", "PointForces",
+    "build", "LIB_PATH", "Engine", "unpack_bits", "load_profile_table", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot", "PointForces",
     "VoxelOctree", "VoxelEnvironment", "VoxelBackboneValidityChecker", "VoxelValidityChecker", "VoxelBackboneMotionValidator", "VoxelBackboneDiscreteMotionValidator", "Environment", "Problem",
     "FunctionTimer", "workloads", "distributed", "roadmap", "RoadmapBuilder", "VoxelCachedLazyPRM", "chained_plan", "chained_plan_loaded",
     "tip_control",

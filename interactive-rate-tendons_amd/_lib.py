@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "tr_tip_jacobian_loaded", "tr_tip_jacobian_loaded_dev",
     "tr_fk_loaded_tips", "tr_fk_loaded_tips_dev",
     "tr_roadmap_ik_batch_loaded", "tr_roadmap_solve_tips_loaded", "tr_roadmap_set_tips_loaded",
+    "tr_set_load_profile", "tr_clear_load_profile", "tr_get_load_profile",
 )
 
 
@@ -146,8 +147,8 @@ OBJ_DIR = os.path.join(SRC_DIR, "_obj")
 def _units():
     """(object name, source, extra flags): the C ABI + K2..K6, the cache merge, and K1 once per
     (tendon count, kernel: shared grid / retraction / fused with K2 / verdict-only / verdict-only with retraction / edge queue /
-    loaded) so its instantiations compile in parallel, and the linearisation kernel of the loaded IK once per tendon count
-    (fk_lin_inst.hip: files of its own, so the K1 units keep their dependencies)."""
+    loaded / loaded under a load profile) so its instantiations compile in parallel, and the linearisation kernel of the loaded IK
+    once per tendon count and form (fk_lin_inst.hip: files of its own, so the K1 units keep their dependencies)."""
     fk_deps = ["fk_inst.hip", "fk_launch.hpp", "fk_kernel.hpp", "fk_retract_kernel.hpp", "fused_kernel.hpp", "verdict_kernel.hpp",
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
@@ -155,22 +156,23 @@ def _units():
                     "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp",
                     "tipq_loaded_kernel.hpp"]
     fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
-               "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp"] + roadmap_deps
+               "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp", "fk_loaded_body.inc", "fk_loaded_lin_body.inc"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
     u = [("tendon_hip.o", "tendon_hip.hip", [], main_deps + [HEADER]),
          ("cache_merge.o", "cache_merge.hip", [], ["cache_merge.hip", "cache_merge.hpp"]),
          ("roadmap.o", "roadmap.hip", ["-pthread"], roadmap_deps + ["edge_sincos.hpp", HEADER]),   # (tendon_hip.o's too)
          ("sample.o", "sample.hip", [], ["sample.hip", "sample.hpp", "tr_types.hpp"])]
     q_deps = fk_deps + ["edge_queue_kernel.hpp", "edge_kernel.hpp"]
-    l_deps = fk_deps + ["fk_loaded_kernel.hpp"]
+    l_deps = fk_deps + ["fk_loaded_kernel.hpp", "fk_loaded_body.inc"]
     for n in range(1, 9):
-        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l")):
+        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l"), (7, "p")):
             u.append(("fk_%s%d.o" % (tag, n), "fk_inst.hip", ["-DTRK_INST_N=%d" % n, "-DTRK_INST_KIND=%d" % kind],
-                      q_deps if kind == 5 else (l_deps if kind == 6 else fk_deps)))
+                      q_deps if kind == 5 else (l_deps if kind in (6, 7) else fk_deps)))
     lin_deps = ["fk_lin_inst.hip", "fk_lin_launch.hpp", "fk_loaded_lin_kernel.hpp", "fk_loaded_kernel.hpp", "edge_sincos.hpp", "fk_launch.hpp",
-                "fk_kernel.hpp", "tr_types.hpp"]
+                "fk_kernel.hpp", "tr_types.hpp", "fk_loaded_body.inc", "fk_loaded_lin_body.inc"]
     for n in range(1, 9):
         u.append(("fk_i%d.o" % n, "fk_lin_inst.hip", ["-DTRK_INST_N=%d" % n], lin_deps))
+        u.append(("fk_j%d.o" % n, "fk_lin_inst.hip", ["-DTRK_INST_N=%d" % n, "-DTRK_LIN_PROFILE"], lin_deps))
     return u
 
 
@@ -404,6 +406,9 @@ def lib():
     L.tr_roadmap_solve_tips_loaded.argtypes = [vp, P(TrSpaceParams), tqp, tcp, shp, elp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, i32p,
                                                dp, dp, P(i64), i32p, dp, P(i64), P(TrRoadmapStats)]
     L.tr_roadmap_set_tips_loaded.argtypes = [vp, shp, elp, P(u64)]
+    L.tr_set_load_profile.argtypes = [vp, i64, dp, dp]
+    L.tr_clear_load_profile.argtypes = [vp]
+    L.tr_get_load_profile.argtypes = [vp, dp, i64, P(i64)]
     L.tr_profile_begin.argtypes = [vp]
     L.tr_profile_read.argtypes = [vp, P(i64), dp]
     L.tr_profile_end.argtypes = [vp]

@@ -33,6 +33,7 @@ struct LoadedIn {
   const double *tip_route;                     // [N][6] routing at s = L
   double *res; int64_t ldr;                    // [6][ldr] tip residual of every lane (structure of arrays), or null
   double *vu_tip;                              // [lanes][6] strains (v, u) at the tip, or null
+  const double *weights = nullptr;             // the load profile's table, [1 + 3 n_steps] weights indexed like the routing table; null: none
 };
 
 struct FusedSweepArgs;
@@ -62,12 +63,15 @@ template <int N> void launch_fk_edge_queue(const FkLaunch &a, const VerdictArgs 
 template <int N> int fk_edge_queue_waves_per_cu(const RobotK &K, size_t lds);
 
 // the loaded FK (fk_loaded_kernel.hpp): a.n lanes, a.d_states the problems' states, a.out the outputs (column = lane)
+// (in.weights null: fk_loaded_uniform; else fk_loaded_profile, whose instantiations are objects of their own, kind 7)
 template <int N> void launch_fk_loaded(const FkLaunch &a, const LoadedIn &in);
+template <int N> void launch_fk_loaded_profile(const FkLaunch &a, const LoadedIn &in);
 // start strains of a.n problems: `guess` rows (v, u), or (guess null) the unloaded solution of the problem's tensions
 template <int N> void launch_shoot_start(const FkLaunch &a, const double *guess, double *vu);
 
 #define TRK_DECL_FK(N) template <> void launch_fk_uniform<N>(const FkLaunch &); template <> void launch_fk_retract<N>(const FkLaunch &); \
-  template <> void launch_fk_loaded<N>(const FkLaunch &, const LoadedIn &); template <> void launch_shoot_start<N>(const FkLaunch &, const double *, double *); \
+  template <> void launch_fk_loaded<N>(const FkLaunch &, const LoadedIn &); template <> void launch_fk_loaded_profile<N>(const FkLaunch &, const LoadedIn &); \
+  template <> void launch_shoot_start<N>(const FkLaunch &, const double *, double *); \
   template <> void launch_fk_sweep_fused<N>(const FkLaunch &, const FusedSweepArgs *, size_t); \
   template <> void launch_fk_sweep_fused_list<N>(const FkLaunch &, const FusedSweepArgs *, size_t, const int32_t *, const uint32_t *); \
   template <> void launch_fk_verdict<N>(const FkLaunch &, const VerdictArgs *, size_t, bool, bool); \

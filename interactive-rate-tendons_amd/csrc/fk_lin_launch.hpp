@@ -17,12 +17,17 @@ struct LinIn {
   double delta_y, delta_p;                     // finite_difference_delta of the shooting and of the IK
   const double *tip_route;                     // [N][6] routing at s = L
   double *out; int64_t ldr;                    // [9][ldr]: 6 residual planes, then 3 planes of the tip after rotate_z
+  const double *weights = nullptr;             // the load profile's table (fk_launch.hpp: LoadedIn::weights); null: none
 };
 
 // a.n lanes; of `a` the kernel reads n, K, rotation, d_tab, d_steps, n_steps and stream
+// (in.weights null: fk_loaded_lin; else fk_loaded_lin_profile, compiled from fk_lin_inst.hip with -DTRK_LIN_PROFILE into objects of
+// its own)
 template <int N> void launch_fk_loaded_lin(const FkLaunch &a, const LinIn &in);
+template <int N> void launch_fk_loaded_lin_profile(const FkLaunch &a, const LinIn &in);
 
-#define TRK_DECL_LIN(N) template <> void launch_fk_loaded_lin<N>(const FkLaunch &, const LinIn &);
+#define TRK_DECL_LIN(N) template <> void launch_fk_loaded_lin<N>(const FkLaunch &, const LinIn &); \
+  template <> void launch_fk_loaded_lin_profile<N>(const FkLaunch &, const LinIn &);
 TRK_DECL_LIN(1) TRK_DECL_LIN(2) TRK_DECL_LIN(3) TRK_DECL_LIN(4) TRK_DECL_LIN(5) TRK_DECL_LIN(6) TRK_DECL_LIN(7) TRK_DECL_LIN(8)
 #undef TRK_DECL_LIN
 

@@ -114,9 +114,23 @@ int parse_loads(tr_ctx *c, const tr_edge_loads *loads, Loads &dst) {
   return TR_OK;
 }
 
+// the installed load profile's table on the device, or null: what every integration of the loaded calls is launched with
+const double *profile_weights(const tr_ctx *c) { return c->profile.on ? c->profile.d_table : nullptr; }
+
+// w(x) of a load profile (include/tendon_hip.h: tr_set_load_profile), in the operation order written there
+double profile_at(int64_t K, const double *s, const double *w, double x) {
+#pragma clang fp contract(off)
+  if (!(x > s[0])) return w[0];
+  if (!(x < s[K - 1])) return w[K - 1];
+  int64_t k = 0;
+  while (k + 2 < K && s[k + 1] <= x) k++;
+  return w[k] + (w[k + 1] - w[k]) * ((x - s[k]) / (s[k + 1] - s[k]));
+}
+
 // `lanes` integrations: lane t is problem list[t / Q] (list null: t / Q) of d_states from strains vu[t]
 int shoot_fk(tr_ctx *c, const double *d_states, int64_t lanes, int64_t ld, const trk::FkOut &out, trk::LoadedIn in, hipStream_t s) {
   in.tip_route = c->shoot.tip_route;
+  in.weights = profile_weights(c);
   const trk::FkLaunch a = fk_launch_args(c, d_states, lanes, ld, out, out.R != nullptr, s);
   TRK_FOR_TENDONS(c, trk::launch_fk_loaded<N>(a, in));
   HIP_TRY(c, hipGetLastError());
@@ -204,6 +218,52 @@ int shoot_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, in
 }  // namespace
 
 extern "C" {
+
+int tr_set_load_profile(tr_ctx *c, int64_t n_knots, const double *s, const double *w) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (n_knots < 1 || !s || !w) return fail(c, TR_ERR_INVALID_ARG, "bad argument (load profile: n_knots >= 1 knots and weights)");
+  for (int64_t k = 0; k < n_knots; k++) {
+    if (!std::isfinite(s[k]) || !std::isfinite(w[k])) return fail(c, TR_ERR_INVALID_ARG, "bad argument (load profile: knots and weights must be finite)");
+    if (k > 0 && !(s[k] > s[k - 1])) return fail(c, TR_ERR_INVALID_ARG, "bad argument (load profile: knots must be strictly increasing)");
+  }
+  if (const int rc = shoot_check(c, 0, 0, 0)) return rc;
+  const size_t n = 1 + 3 * c->steps.size();
+  std::vector<double> table(n);
+  table[0] = profile_at(n_knots, s, w, 0.0);
+  for (size_t k = 0; k < c->steps.size(); k++) {
+    const double tk = c->step_t[k], h = c->steps[k].h;
+    table[1 + 3 * k + 0] = profile_at(n_knots, s, w, tk);
+    table[1 + 3 * k + 1] = profile_at(n_knots, s, w, tk + h * 0.5);
+    table[1 + 3 * k + 2] = profile_at(n_knots, s, w, tk + h);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipDeviceSynchronize());          // launches that still read the previous table (any stream) finish first
+  if (!c->profile.d_table) HIP_TRY(c, hipMalloc((void **)&c->profile.d_table, n * sizeof(double)));
+  c->profile.on = false;                       // (a failed upload leaves no profile installed)
+  HIP_TRY(c, hipMemcpy(c->profile.d_table, table.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  c->profile.table.swap(table);
+  c->profile.on = true;
+  return TR_OK;
+}
+
+int tr_clear_load_profile(tr_ctx *c) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  c->profile.on = false;                       // (launches already queued hold the table's pointer, and the table stays)
+  c->profile.table.clear();
+  return TR_OK;
+}
+
+int tr_get_load_profile(tr_ctx *c, double *table_out, int64_t capacity, int64_t *n_out) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (!n_out || capacity < 0) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  const int64_t n = c->profile.on ? (int64_t)c->profile.table.size() : 0;
+  *n_out = n;
+  if (table_out) for (int64_t k = 0; k < std::min(n, capacity); k++) table_out[k] = c->profile.table[k];
+  return TR_OK;
+}
 
 int tr_fk_loaded_batch_dev(tr_ctx *c, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
                            const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess,

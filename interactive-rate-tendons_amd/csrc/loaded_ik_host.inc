@@ -97,6 +97,7 @@ int ikl_linearise(tr_ctx *c, const IklCall &call, const int32_t *list, int64_t a
   lin.world = call.loads.world; lin.Q = Q;
   lin.delta_y = call.sprm.delta; lin.delta_p = call.prm.delta;
   lin.tip_route = c->shoot.tip_route;
+  lin.weights = profile_weights(c);
   lin.out = k.lin; lin.ldr = k.lanes;
   hipLaunchKernelGGL(trk::ikl_gather, dim3(ik_grid(active, 64)), dim3(64), 0, s, call.prm, ikl_state(c), list, active, call.loads, d_guess,
                      ikl_rows(c));

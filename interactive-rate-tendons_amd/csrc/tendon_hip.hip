@@ -153,6 +153,7 @@ struct tr_ctx {
   // shared arc-length grid
   std::vector<double> t;          // backbone abscissae (s_start = 0)
   std::vector<StepK> steps;
+  std::vector<double> step_t;     // the abscissa every step starts at
   double *d_tab = nullptr;
   StepK *d_steps = nullptr;
   PolyK *d_poly = nullptr;        // routing polynomials (retraction kernel)
@@ -344,6 +345,13 @@ struct tr_ctx {
     int64_t *sens_n = nullptr;
     DevOwner chunk, once, sens;                                     // sized by probs; the counter; by sens_probs
   } ikl;
+  // the load profile of the loaded calls (tr_set_load_profile, loaded_host.inc): the weights at the RK4 stages' abscissae, indexed
+  // like the routing table; d_table is allocated at the first install and lives with the context
+  struct LoadProfile {
+    bool on = false;
+    std::vector<double> table;    // [1 + 3 steps] while on
+    double *d_table = nullptr;
+  } profile;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
@@ -1134,7 +1142,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
   // t[j+1]-cur > eps; every interval restarts at exactly t[j]) and the routing table
   c->t = t_range(0.0, rb->L, rb->dL);
   K.n_points = (int)c->t.size();
-  std::vector<double> step_t;
+  std::vector<double> &step_t = c->step_t;
   for (size_t j = 0; j + 1 < c->t.size(); j++) {
     double cur = c->t[j];
     const double tn = c->t[j + 1];
@@ -1230,6 +1238,7 @@ void tr_destroy(tr_ctx *c) {
     for (void *q : sp) if (q) (void)hipFree(q);
     if (sm.h_ctr) (void)hipHostFree(sm.h_ctr);
   }
+  if (c->profile.d_table) (void)hipFree(c->profile.d_table);
   if (c->d_item_src) (void)hipFree(c->d_item_src);
   if (c->d_item_edge) (void)hipFree(c->d_item_edge);
   for (void *q : c->knn.p) if (q) (void)hipFree(q);

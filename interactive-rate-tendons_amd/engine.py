@@ -3,6 +3,7 @@
 Device buffers are torch tensors (torch is the memory / stream plumbing, nothing more); every
 compute call goes through the C ABI in include/tendon_hip.h.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -51,6 +52,53 @@ def edge_sincos(x):
     return s, c
 
 
+def _profile_knots(knots, weights):
+    """The checked (knots, weights) of a load profile as float64 rows: tr_set_load_profile's argument rules."""
+    s, w = _f64(knots).reshape(-1), _f64(weights).reshape(-1)
+    if s.size < 1 or s.size != w.size:
+        raise L.InvalidArgument("bad argument (load profile: n_knots >= 1 knots and weights)")
+    if not (np.isfinite(s).all() and np.isfinite(w).all()):
+        raise L.InvalidArgument("bad argument (load profile: knots and weights must be finite)")
+    if not (np.diff(s) > 0).all():
+        raise L.InvalidArgument("bad argument (load profile: knots must be strictly increasing)")
+    return s, w
+
+
+def load_profile_at(knots, weights, x):
+    """w(x) of a piecewise-linear load profile, in tr_set_load_profile's operation order (include/tendon_hip.h): the end values
+    outside the knots; else, with k the last knot at or below x, w_k + (w_k+1 - w_k) * ((x - s_k) / (s_k+1 - s_k))."""
+    s, w = knots, weights
+    x = float(x)
+    if not x > s[0]:
+        return float(w[0])
+    if not x < s[-1]:
+        return float(w[-1])
+    k = 0
+    while k + 2 < len(s) and s[k + 1] <= x:
+        k += 1
+    return float(w[k] + (w[k + 1] - w[k]) * ((x - s[k]) / (s[k + 1] - s[k])))
+
+
+def load_profile_table(robot, knots, weights):
+    """The table tr_set_load_profile installs for `robot`, in numpy and without a GPU: 1 + 3 n_steps weights at the abscissae of the
+    RK4 stages, indexed like the routing table (entry 0 at s = 0; 1 + 3k, + 1, + 2 at t_k, t_k + h * 0.5, t_k + h), bit for bit."""
+    if robot.enable_retraction:
+        raise L.Unsupported("loaded FK (general_shape) is not built for robots with retraction")
+    s, w = _profile_knots(knots, weights)
+    t, dL, eps = robot._t(0.0), float(robot.specs.dL), float(np.finfo(float).eps)
+    out = [load_profile_at(s, w, 0.0)]
+    for j in range(len(t) - 1):                      # integrate_times' steps (tr_create): min(dL, t[j+1] - cur) while that exceeds eps
+        cur, tn, any_step = float(t[j]), float(t[j + 1]), False
+        while tn - cur > eps:
+            h = min(dL, tn - cur)
+            out += [load_profile_at(s, w, cur), load_profile_at(s, w, cur + h * 0.5), load_profile_at(s, w, cur + h)]
+            cur += h
+            any_step = True
+        if not any_step:
+            out += [load_profile_at(s, w, cur)] * 3
+    return np.array(out)
+
+
 class Engine:
     """One context of libtendon_hip.so: tr_create ... tr_destroy."""
 
@@ -88,6 +136,7 @@ class Engine:
         self.state_size = lib.tr_state_size(ctx)
         self.num_points = lib.tr_num_points(ctx)
         self.has_grid = False
+        self._load_profile = None
 
     def close(self):
         if self._ctx is not None:
@@ -292,6 +341,50 @@ class Engine:
         if a.shape == (n, 6):
             return a, 6
         raise L.InvalidArgument("%s must be (6,) or (n, 6)" % name)
+
+    # ---- the load profile of every loaded call (tr_set_load_profile): a weight w(s) on the distributed load ------------------------
+    def set_load_profile(self, knots, weights):
+        """Install the piecewise-linear weight w(s) over (knots, weights): from now on every loaded call of this engine integrates
+        under w(s) f_e, w(s) l_e (the tip wrench is not scaled).  Waits for the engine's queued device work first."""
+        s, w = _profile_knots(knots, weights)
+        L.check(self._ctx, self.lib.tr_set_load_profile(self._ctx, s.size, _dp(s), _dp(w)))
+        self._load_profile = (s.copy(), w.copy())
+
+    def clear_load_profile(self):
+        L.check(self._ctx, self.lib.tr_clear_load_profile(self._ctx))
+        self._load_profile = None
+
+    def load_profile(self):
+        """(knots, weights) of the installed profile, or None."""
+        return self._load_profile
+
+    def load_profile_table(self):
+        """The installed table at the stage abscissae (tr_get_load_profile); length 0: no profile installed."""
+        n = C.c_int64(0)
+        L.check(self._ctx, self.lib.tr_get_load_profile(self._ctx, None, 0, C.byref(n)))
+        out = np.empty(int(n.value))
+        if out.size:
+            L.check(self._ctx, self.lib.tr_get_load_profile(self._ctx, _dp(out), out.size, C.byref(n)))
+        return out
+
+    @contextlib.contextmanager
+    def load_profile_scope(self, profile):
+        """Context manager: `profile` = (knots, weights) installed for the block, the previous one (or none) restored after it, also
+        when the block raises.  profile None: the block runs under whatever is installed.  Every install waits for the device and
+        uploads a table (tr_set_load_profile), so a block costs one device synchronisation, and a second one for the restore when a
+        profile was installed before it: install once with set_load_profile where many calls share a profile."""
+        if profile is None:
+            yield
+            return
+        before = self.load_profile()
+        self.set_load_profile(*profile)
+        try:
+            yield
+        finally:
+            if before is None:
+                self.clear_load_profile()
+            else:
+                self.set_load_profile(*before)
 
     def fk_loaded_batch(self, states, wrench=None, dist=None, guess=None, want_R=False, max_iters=100, mu_init=0.1,
                         stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6):

@@ -157,16 +157,32 @@ class VoxelBackboneValidityChecker:
     # (apps/profile_chained_plan.cpp:407-451): from then on the checker's FK, and with it the motion validator's, is the loaded one ----
     _loads = None
 
-    def set_loads(self, wrench=None, dist=None, frame="base", warm_start=None, **shoot):
+    _profile = None
+
+    def set_loads(self, wrench=None, dist=None, frame="base", warm_start=None, profile=None, **shoot):
         """wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, one (6,) row each (None: zero).  frame='base': fixed before the
         state's rotation (fk_loaded_batch's frame); 'world': fixed behind it, every state's rows turned by Rz(-theta).  Afterwards
         is_valid and the motion validators on this checker judge LOADED shapes, and a RoadmapBuilder on it builds on them (vertex
-        phase, connect, both voxel caches; roadmap.py); clear_loads() restores the unloaded checks."""
+        phase, connect, both voxel caches; roadmap.py); clear_loads() restores the unloaded checks.  profile = (knots, weights): a
+        weight w(s) along the backbone on `dist` (Engine.set_load_profile), installed on the checker's engine until clear_loads() or
+        the next set_loads; load_profile() reports it."""
         self.engine._edge_loads(wrench, dist, frame, warm_start)              # argument checks
+        if profile is not None:
+            self.engine.set_load_profile(*profile)
+        elif self._profile is not None:
+            self.engine.clear_load_profile()
+        self._profile = self.engine.load_profile() if profile is not None else None
         self._loads = dict(wrench=wrench, dist=dist, frame=frame, warm_start=warm_start, **shoot)
 
     def clear_loads(self):
+        if self._profile is not None:
+            self.engine.clear_load_profile()
+        self._profile = None
         self._loads = None
+
+    def load_profile(self):
+        """(knots, weights) of the profile set_loads installed, or None."""
+        return self._profile
 
     def loads(self):
         return self._loads

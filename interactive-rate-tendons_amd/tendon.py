@@ -156,11 +156,13 @@ class TendonRobot:
 
     def general_shape(self, state, f_e=(0.0, 0.0, 0.0), l_e=(0.0, 0.0, 0.0), F_e=(0.0, 0.0, 0.0), L_e=(0.0, 0.0, 0.0), u_guess=None,
                       v_guess=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
-                      finite_difference_delta=1e-6, device=0) -> TendonResult:          # TendonRobot.h:155-219
+                      finite_difference_delta=1e-6, device=0, load_profile=None) -> TendonResult:          # TendonRobot.h:155-219
         """The shape under a tip force / moment F_e, L_e and a distributed force / moment f_e, l_e per unit length, in the base frame
         before the state's rotation (the reference rotates the solved shape).  f_e, l_e are CONSTANT vectors (gravity); the
-        reference's functions of (t, p) are not offered.  Without u_guess / v_guess the shooting starts from the unloaded solution of the
-        tensions, not from the reference's straight rod (v, u) = (e3, 0): pass u_guess=(0, 0, 0), v_guess=(0, 0, 1) for that."""
+        reference's functions of (t, p) are not offered, but load_profile=(knots, weights) scales them by a piecewise-linear weight
+        w(s) along the backbone (Engine.set_load_profile; installed for this call, the engine's previous profile restored after
+        it).  Without u_guess / v_guess the shooting starts from the unloaded solution of the tensions, not from the reference's
+        straight rod (v, u) = (e3, 0): pass u_guess=(0, 0, 0), v_guess=(0, 0, 1) for that."""
         state = np.asarray(state, dtype=np.float64).reshape(-1)
         if state.size != self.state_size():
             raise L.InvalidArgument("State is not the right size")
@@ -170,15 +172,17 @@ class TendonRobot:
                                     np.asarray((0.0, 0.0, 0.0) if u_guess is None else u_guess, float).reshape(3)])[None]
         out = self.general_shape_batch(state[None], f_e, l_e, F_e, L_e, guess=guess, want_R=True, max_iters=max_iters, mu_init=mu_init,
                                        stop_threshold_JT_err_inf=stop_threshold_JT_err_inf, stop_threshold_Dp=stop_threshold_Dp,
-                                       finite_difference_delta=finite_difference_delta, device=device)
+                                       finite_difference_delta=finite_difference_delta, device=device, load_profile=load_profile)
         n = int(out["n_points"][0])
         R = out["R"][0, :n].reshape(n, 3, 3).transpose(0, 2, 1)
         return TendonResult(t=self._t(0.0)[:n], p=out["p"][0, :n], R=R, L=float(out["L"][0]), L_i=out["L_i"][0],
                             converged=bool(out["converged"][0]), v_i=out["vu0"][0, :3].copy(), u_i=out["vu0"][0, 3:].copy(),
                             v_f=out["vuL"][0, :3].copy(), u_f=out["vuL"][0, 3:].copy())
 
-    def general_shape_batch(self, states, f_e=None, l_e=None, F_e=None, L_e=None, guess=None, want_R=False, device=0, **shoot):
-        """general_shape for a batch: every load is (3,) for all states or (n, 3) (None: zero); guess (n, 6) rows (v, u) or None.
+    def general_shape_batch(self, states, f_e=None, l_e=None, F_e=None, L_e=None, guess=None, want_R=False, device=0, load_profile=None,
+                            **shoot):
+        """general_shape for a batch: every load is (3,) for all states or (n, 3) (None: zero); guess (n, 6) rows (v, u) or None;
+        load_profile (knots, weights): the weight w(s) on f_e, l_e for this call (None: the engine's installed profile, if any).
         Returns Engine.fk_loaded_batch's dict."""
         st = np.atleast_2d(np.asarray(states, dtype=np.float64))
         n = st.shape[0]
@@ -192,13 +196,16 @@ class TendonRobot:
                 return np.concatenate([a, b])
             return np.concatenate([np.broadcast_to(a, (n, 3)), np.broadcast_to(b, (n, 3))], axis=1)
 
-        return self.engine(device).fk_loaded_batch(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), guess=guess, want_R=want_R, **shoot)
+        eng = self.engine(device)
+        with eng.load_profile_scope(load_profile):
+            return eng.fk_loaded_batch(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), guess=guess, want_R=want_R, **shoot)
 
     def tip_jacobian_loaded_batch(self, states, f_e=None, l_e=None, F_e=None, L_e=None, frame="base", guess=None, delta=1e-6,
-                                  want=("J",), device=0, **shoot):
+                                  want=("J",), device=0, load_profile=None, **shoot):
         """tip_jacobian_batch on the shapes of general_shape_batch: d tip / d state (n, 3, S) of the LOADED tips and, on request,
         the tip compliance d tip / d (F_e, L_e) (n, 3, 6), from one shooting solve and 13 + 2 S integrations per state.  Loads
-        in general_shape_batch's order, (3,) each: one set per call (frame='world': fixed behind the state's rotation).  Returns
+        in general_shape_batch's order, (3,) each: one set per call (frame='world': fixed behind the state's rotation); load_profile as in
+        general_shape_batch.  Returns
         Engine.tip_jacobian_loaded's dict."""
         st = np.atleast_2d(np.asarray(states, dtype=np.float64))
 
@@ -208,8 +215,10 @@ class TendonRobot:
             z = np.zeros(3)
             return np.concatenate([np.asarray(z if a is None else a, float).reshape(3), np.asarray(z if b is None else b, float).reshape(3)])
 
-        return self.engine(device).tip_jacobian_loaded(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), frame=frame, guess=guess,
-                                                       delta=delta, want=want, **shoot)
+        eng = self.engine(device)
+        with eng.load_profile_scope(load_profile):
+            return eng.tip_jacobian_loaded(st, wrench=pair(F_e, L_e), dist=pair(f_e, l_e), frame=frame, guess=guess, delta=delta, want=want,
+                                           **shoot)
 
     def _stiffness(self):
         s = self.specs

@@ -199,10 +199,12 @@ def inverse_kinematics_device(robot, initial_state, des, max_iters=100, mu_init=
     return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
 
 
-def inverse_kinematics_loaded_batch_device(robot, initial_states, des, wrench=None, dist=None, frame="base", guess=None, device=0, **lm):
+def inverse_kinematics_loaded_batch_device(robot, initial_states, des, wrench=None, dist=None, frame="base", guess=None, device=0,
+                                           load_profile=None, **lm):
     """tip_control::inverse_kinematics with TendonRobot::general_shape as its FK, for a batch, on the device (tr_ik_loaded_batch):
     solve tip(state under the load) = des from every row of initial_states.  wrench = (F_e, L_e), dist = (f_e, l_e): one (6,) set
-    per call, frame 'base' (fixed before the state's rotation) or 'world' (fixed behind rotate_z, e.g. gravity).  **lm:
+    per call, frame 'base' (fixed before the state's rotation) or 'world' (fixed behind rotate_z, e.g. gravity).  load_profile =
+    (knots, weights): a weight w(s) along the backbone on `dist` for this call (Engine.load_profile_scope).  **lm:
     inverse_kinematics_batch's solver arguments, the shooting's with the prefix shoot_ (shoot_max_iters ...).  The scheme is
     tests/loaded_ik_reference.py's.  Returns inverse_kinematics_batch_device's fields (num_fk_calls: integrations; launches: outer
     rounds) plus vu0 (the base strains of each returned state's equilibrium), equilibrium (False: the start's shooting did not
@@ -215,34 +217,42 @@ def inverse_kinematics_loaded_batch_device(robot, initial_states, des, wrench=No
     des = np.asarray(des, dtype=np.float64)
     if des.ndim == 2 and des.shape[0] == 1 and p.shape[0] != 1:
         des = des[0]
-    r = robot.engine(device).ik_loaded_batch(p, des, wrench=wrench, dist=dist, frame=frame, guess=guess, **lm)
+    eng = robot.engine(device)
+    with eng.load_profile_scope(load_profile):
+        r = eng.ik_loaded_batch(p, des, wrench=wrench, dist=dist, frame=frame, guess=guess, **lm)
     return dict(state=r["state"], tip=r["tip"], error=r["error"], iters=r["iters"].astype(int), num_fk_calls=r["num_fk_calls"].astype(int),
                 launches=r["rounds"], vu0=r["vu0"], equilibrium=r["equilibrium"], shoot_rounds=r["shoot_rounds"])
 
 
-def inverse_kinematics_loaded_device(robot, initial_state, des, wrench=None, dist=None, frame="base", guess=None, device=0, **lm):
+def inverse_kinematics_loaded_device(robot, initial_state, des, wrench=None, dist=None, frame="base", guess=None, device=0,
+                                     load_profile=None, **lm):
     """inverse_kinematics_loaded_batch_device for one start state: an IKResult (error = inf without an equilibrium at the start)."""
     g = None if guess is None else np.asarray(guess, float).reshape(1, 6)
-    r = inverse_kinematics_loaded_batch_device(robot, np.asarray(initial_state, float).reshape(1, -1), des, wrench, dist, frame, g, device, **lm)
+    r = inverse_kinematics_loaded_batch_device(robot, np.asarray(initial_state, float).reshape(1, -1), des, wrench, dist, frame, g, device,
+                                               load_profile, **lm)
     return IKResult(r["state"][0], r["tip"][0], float(r["error"][0]), int(r["iters"][0]), int(r["num_fk_calls"][0]))
 
 
-def tip_compliance_loaded(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, **shoot):
+def tip_compliance_loaded(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, load_profile=None, **shoot):
     """How far the loaded tip gives way under a push: d tip / d (F_e, L_e) (n, 3, 6) in m/N and m/(N m) at the equilibria of
     `states` under the load, with respect to the wrench as given (frame 'world': a wrench fixed behind rotate_z)
     (tr_tip_jacobian_loaded).  Returns dict(compliance, tips, vu0, equilibrium); a state without an equilibrium has NaN rows."""
-    r = robot.engine(device).tip_jacobian_loaded(states, wrench=wrench, dist=dist, frame=frame, guess=guess, want=("compliance",), **shoot)
+    eng = robot.engine(device)
+    with eng.load_profile_scope(load_profile):
+        r = eng.tip_jacobian_loaded(states, wrench=wrench, dist=dist, frame=frame, guess=guess, want=("compliance",), **shoot)
     return dict(compliance=r["compliance"], tips=r["tips"], vu0=r["vu0"], equilibrium=r["equilibrium"])
 
 
-def loaded_tips_batch_device(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, **shoot):
+def loaded_tips_batch_device(robot, states, wrench=None, dist=None, frame="base", guess=None, device=0, load_profile=None, **shoot):
     """The tips of the LOADED shapes of a batch of states (Engine.fk_loaded_tips: the shapes stay on the device): dict(tips,
     converged, vu0, rounds, n_integrations).  What a tip-goal loop under load measures its progress with."""
-    return robot.engine(device).fk_loaded_tips(states, wrench=wrench, dist=dist, frame=frame, guess=guess, **shoot)
+    eng = robot.engine(device)
+    with eng.load_profile_scope(load_profile):
+        return eng.fk_loaded_tips(states, wrench=wrench, dist=dist, frame=frame, guess=guess, **shoot)
 
 
 def damped_resolved_rate_update_batch_device(robot, states, v_times_dt, lam=0.1, finite_difference_delta=1e-6, wrench=None, dist=None,
-                                             frame="base", device=0):
+                                             frame="base", device=0, load_profile=None):
     """tip_control::damped_resolved_rate_update (tip_control.cpp:418-483) for a batch: the next state of every row of `states` for
     the tip displacement v_times_dt ((3,) or one row per state).  The reference runs ONE Levenberg-Marquardt iteration towards
     fk(q) + v_times_dt with mu_init = lambda, all three stop thresholds at 1e-9 and Bounds.from_robot centred on q; here that is
@@ -262,16 +272,17 @@ def damped_resolved_rate_update_batch_device(robot, states, v_times_dt, lam=0.1,
         tips = _tips(robot, p, device)
         return eng.ik_batch(p, np.ascontiguousarray(tips + v), **lm)["state"]
     w, d = eng.sample_loads(p, wrench, dist, frame)                      # every state's rows (a world-frame set: turned by its rotation)
-    out = eng.fk_loaded_batch(p, wrench=w, dist=d)
-    tips = out["p"][np.arange(len(p)), out["n_points"] - 1]
-    return eng.ik_loaded_batch(p, np.ascontiguousarray(tips + v), wrench=wrench, dist=dist, frame=frame, guess=out["vu0"], **lm)["state"]
+    with eng.load_profile_scope(load_profile):
+        out = eng.fk_loaded_batch(p, wrench=w, dist=d)
+        tips = out["p"][np.arange(len(p)), out["n_points"] - 1]
+        return eng.ik_loaded_batch(p, np.ascontiguousarray(tips + v), wrench=wrench, dist=dist, frame=frame, guess=out["vu0"], **lm)["state"]
 
 
 def damped_resolved_rate_update_device(robot, state, v_times_dt, lam=0.1, finite_difference_delta=1e-6, wrench=None, dist=None,
-                                       frame="base", device=0):
+                                       frame="base", device=0, load_profile=None):
     """damped_resolved_rate_update_batch_device for one state: the next state (S,)."""
     return damped_resolved_rate_update_batch_device(robot, np.asarray(state, float).reshape(1, -1), v_times_dt, lam,
-                                                    finite_difference_delta, wrench, dist, frame, device)[0]
+                                                    finite_difference_delta, wrench, dist, frame, device, load_profile)[0]
 
 
 def roadmap_ik(robot, goal_tip, vertex_states, vertex_tips, k=10, tolerance=1e-4, **lm):
