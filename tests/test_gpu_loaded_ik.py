@@ -123,6 +123,32 @@ def _same(a, b, rows_a=slice(None), rows_b=slice(None)):
         assert np.array_equal(a[k][rows_a], b[k][rows_b], equal_nan=True), k
 
 
+@pytest.mark.parametrize("key", ["n1_B", "config1_B"])
+def test_the_calls_of_growing_max_iters_extend_each_other(world, solved, key):
+    """The invariants of the iteration that need no truth (the unloaded step kernel's replay is tests/test_gpu_ik_steps.py): the
+    call with max_iters = k + 1 extends the call with max_iters = k, counts do not fall, the error does not rise, and a step that
+    did not move the state left state, tip and vu0 as they were, bit for bit."""
+    s = solved(key)
+    eng = world(PROBLEMS[key][0])[3]
+    calls = [ik(eng, s["starts"], s["goals"], s["wrench"], s["dist"], s["frame"], max_iters=k) for k in range(11)]
+    assert (calls[0]["iters"] == 0).all()
+    moved = 0
+    for k, (a, b) in enumerate(zip(calls, calls[1:])):
+        assert np.array_equal(a["equilibrium"], b["equilibrium"]), k
+        di = b["iters"] - a["iters"]
+        assert np.isin(di, (0, 1)).all() and (a["iters"] <= k).all(), k
+        assert (b["num_fk_calls"] >= a["num_fk_calls"]).all(), k
+        assert (b["num_fk_calls"][di == 0] == a["num_fk_calls"][di == 0]).all(), k
+        eq = a["equilibrium"]
+        assert (b["error"][eq] <= a["error"][eq]).all(), k
+        _same(a, b, di == 0, di == 0)
+        same_state = (a["state"].view(np.uint64) == b["state"].view(np.uint64)).all(1)
+        for name in ("tip", "vu0", "error"):
+            assert np.array_equal(a[name][same_state], b[name][same_state], equal_nan=True), (k, name)
+        moved += int((~same_state).sum())
+    assert moved >= len(s["starts"])                      # the iteration did run
+
+
 @pytest.mark.parametrize("key", ["config1_B", "config1_C", "n1_B", "config1_full"])
 def test_it_is_a_solution(world, solved, key):
     robot, rob, fx, eng = world(PROBLEMS[key][0])
