@@ -858,6 +858,88 @@ int tr_roadmap_solve_tips_connect(tr_roadmap *rm, const tr_space_params *sp, con
  * The source search counts into `nearest` of tr_roadmap_tip_query_profile. */
 int tr_roadmap_tip_connect_stats(tr_roadmap *rm, int64_t out[4]);
 
+/* ---- queries between ARBITRARY states: attach on the device, seeded search ----------------------------------
+ * tr_roadmap_solve answers for pairs of roadmap VERTICES.  The reference's solvePrep (motion-planning/VoxelCachedLazyPRM.cpp:2978-3020)
+ * turns the problem's start and goal STATES into milestones with addMilestone(state, connect = true) (:1854-1885), which joins each to
+ * its connectionStrategy_ neighbours, and A* runs over the augmented graph; apps/roadmap_chained_plan.cpp:533,548-552 starts every hop
+ * at the state the robot is in.  Here that is two primitives and their composition; the graph itself is never edited.
+ *
+ * Attach (tr_roadmap_attach_states): for n states (n x state_size; any state of the space, retraction and rotation robots included)
+ * and a direction -- TR_ATTACH_OUT: the motion LEAVES the state, TR_ATTACH_IN: it ARRIVES at it --
+ *   A1. valid[i] (one byte) is tr_validate_batch's bit for the state under the installed checker and the current grid (solvePrep only
+ *       admits valid states).
+ *   A2. vertices[i][0..k) and cost[i][0..k) are exactly tr_roadmap_nearest_states(state_i, k, max_distance): the (dist, vertex index)
+ *       order among the vertices valid in the current grid, tr_knn's arithmetic, -1 / +inf padding; the vertex validity learned on the
+ *       way is kept in the roadmap.  An INVALID state gets a row of -1 / +inf.
+ *   A3. edge_ok[i][j] (one byte) is the verdict bit of checkMotion(state_i, states[vertices[i][j]]) for OUT, of
+ *       checkMotion(states[vertices[i][j]], state_i) for IN: the bit tr_validate_edges gives for the pair in that order.  Padded slots
+ *       and the slots of invalid states give 0 and take no FK sample.
+ *   A4. n_fk (optional, n x k) are the FK samples per slot as tr_validate_edges_indexed counts them over the array [roadmap states |
+ *       query states] (end states once per array, not per pair); n_domain_errors (optional) as in the edge calls.
+ * A state's row does not depend on the other states, their order or n.  k: 1 .. 64; a NULL tr_attach_params* means k = 10 and INFINITY
+ * (connect_k's defaults); a NULL tr_space_params* the defaults of Problem.h:59-62.  Needs tr_roadmap_set_tips, as
+ * tr_roadmap_nearest_states does; n == 0: TR_OK.  Between the states going up and the result arrays coming down the index PAIRS never
+ * cross the bus, only their number: tr_validate_batch_dev -> state_knn -> the live slots compacted in slot order into index pairs
+ * over one device array (the roadmap's rows, resident from the first call on, with the query rows behind them; attach_kernel.hpp) ->
+ * ONE tr_validate_edges_indexed_dev -> the verdict words scattered back to n x k bytes.  What that edge call computes does pass
+ * through the host INSIDE it, as in every use of it: its per-pair results come down, and the packed verdict words (one bit per pair;
+ * with n_fk also the counts, 4 bytes per pair) go up again to the arrays the scatter reads.  The _dev form takes and returns device pointers
+ * on the context's GPU with the same bits and synchronises as tr_roadmap_nearest_states_dev does. */
+#define TR_ATTACH_OUT 0
+#define TR_ATTACH_IN  1
+typedef struct {
+  int32_t k;
+  double max_distance;
+} tr_attach_params;
+int tr_roadmap_attach_states(tr_roadmap *rm, const tr_space_params *sp, const tr_attach_params *params, int32_t direction,
+                             const double *states, int64_t n, uint8_t *valid, int32_t *vertices, double *cost, uint8_t *edge_ok,
+                             int32_t *n_fk, int64_t *n_domain_errors);
+int tr_roadmap_attach_states_dev(tr_roadmap *rm, const tr_space_params *sp, const tr_attach_params *params, int32_t direction,
+                                 const double *d_states, int64_t n, uint8_t *d_valid, int32_t *d_vertices, double *d_cost,
+                                 uint8_t *d_edge_ok, int32_t *d_n_fk, int64_t *n_domain_errors);
+/* Seeded search -- a search from several weighted sources to several weighted targets (the reference's TODO :2011-2013, "Solve A* with
+ * multiple goals simultaneously").  Query q has source seeds (u_i, c_i) = (src_vertices, src_costs)[src_offsets[q] .. src_offsets[q+1])
+ * and target seeds (v_j, d_j) likewise; vertices in [0, n_vertices) (else TR_ERR_OUT_OF_RANGE), costs finite and >= 0 (else
+ * TR_ERR_INVALID_ARG); direct_cost[q] (optional array; +inf or NULL: none) is the cost of a connection that bypasses the roadmap.
+ *   S1. The answer minimises c_i + dist(u_i, v_j) + d_j, dist = the shortest path in the roadmap minus the items invalid in the current
+ *       grid; u_i == v_j is allowed (an empty roadmap part).  The direct connection wins when direct_cost <= that minimum.
+ *   S2. Validity is found lazily exactly as tr_roadmap_solve finds it: the same rounds of candidate paths, the same K4 launches, the same
+ *       three eager rules, TENDON_HIP_LAZY_ONLY honoured; what a call learns is kept for the next.  Seed vertices of unknown validity
+ *       are tested before the first search, as the end points of tr_roadmap_solve are; an invalid seed vertex drops its seed.
+ *   S3. cost is summed left to right from the source: ((c_i + w_1) + w_2 ...) + d_j, which is A*'s own g.
+ *   S4. status: TR_QUERY_SOLVED, or TR_QUERY_NO_PATH -- no finite combination, an empty seed list without a direct cost included.
+ *       src_pick / dst_pick (optional): indices into the query's seed lists, -1 when the direct connection won or there is no path;
+ *       path_offsets and tr_roadmap_fetch_paths: the vertex path u_i ... v_j, empty for a direct answer; stats as tr_roadmap_solve.
+ * A query's answer does not depend on the batch.  The searches (astar_seeded: the sources enter the open list with g = c_i, a virtual
+ * goal is relaxed with g(v_j) + d_j when a target vertex is expanded, heuristic min_j (h(v, v_j) + d_j), landmark terms included) run
+ * on the HOST THREADS at every batch size: the rounds of this call never launch roadmap_astar, and tr_roadmap_search_stats out[0]
+ * stays 0 after it. */
+int tr_roadmap_solve_seeded(tr_roadmap *rm, int64_t n_queries, const int64_t *src_offsets, const int32_t *src_vertices,
+                            const double *src_costs, const int64_t *dst_offsets, const int32_t *dst_vertices, const double *dst_costs,
+                            const double *direct_cost, int32_t n_threads, int32_t *status, double *cost, int32_t *src_pick,
+                            int32_t *dst_pick, int64_t *path_offsets, tr_roadmap_stats *stats);
+/* State-to-state queries -- solvePrep + solveWithRoadmap for n (start state, goal state) pairs (starts, goals: n x state_size).  ONE
+ * attach pass: the starts attached OUT, the goals IN, and the direct edges checkMotion(start_q, goal_q) where the rule below applies,
+ * the pairs of all three in one edge-check call.  Then:
+ *   T1. an invalid start state: TR_QUERY_INVALID_START; otherwise an invalid goal state: TR_QUERY_INVALID_GOAL (solvePrep :2995-3010).
+ *   T2. the direct edge is tried when both states are valid and d(start, goal) <= max(cost_s[k-1], cost_g[k-1]) (padding counts as
+ *       +inf) and <= max_distance: when the other state would be among the k nearest if it were a milestone, as in the reference after
+ *       both addMilestone calls.  d in tr_knn's arithmetic.
+ *   T3. otherwise the result of the seeded search: seeds = the slots with edge_ok, at their attach distances; direct_cost =
+ *       d(start, goal) when the direct edge is valid.
+ * Outputs (status and path_offsets required, the others may be NULL): cost; start_vertex / goal_vertex, the picked connection
+ * vertices (-1 for a direct answer or none); direct (one byte); src_pick / dst_pick, the picked SLOTS of the attach rows (0 .. k-1,
+ * -1 likewise); the vertex paths through tr_roadmap_fetch_paths (start state and goal state precede and follow them).
+ * Deliberate differences from the reference: nothing is inserted into the graph; the attachments are validated eagerly in one batch
+ * instead of lazily; the neighbours are drawn from the vertices valid in the current grid. */
+int tr_roadmap_solve_states(tr_roadmap *rm, const tr_space_params *sp, const tr_attach_params *params, const double *starts,
+                            const double *goals, int64_t n, int32_t n_threads, int32_t *status, double *cost, int32_t *start_vertex,
+                            int32_t *goal_vertex, uint8_t *direct, int32_t *src_pick, int32_t *dst_pick, int64_t *path_offsets,
+                            tr_roadmap_stats *stats);
+/* Host wall time of the phases of the last tr_roadmap_solve_states in milliseconds (instrumentation): out[0] validity + nearest +
+ * pairs, out[1] edges, out[2] seeded search, out[3] results. */
+int tr_roadmap_state_query_profile(tr_roadmap *rm, double out[4]);
+
 /* ---- tip-goal queries on LOADED shapes ----
  * With TendonRobot::general_shape installed as the checker's FK (apps/profile_chained_plan.cpp:407-451) roadmapIk takes every shape
  * from voxelStateChecker_->fk (:3052, :3187): its IK, its last-valid edge checks and its closest-state rule all run on loaded shapes.

@@ -1475,6 +1475,88 @@ class VoxelCachedLazyPRM {
     rcheck(tr_roadmap_nearest_states(rm_, queries.data(), (int64_t)n, (int32_t)k, max_distance, r.vertices.data(), r.distance.data()));
     return r;
   }
+  // ---- queries between arbitrary states (tr_roadmap_attach_states / tr_roadmap_solve_seeded / tr_roadmap_solve_states) ----
+  enum AttachDirection { ATTACH_OUT = TR_ATTACH_OUT, ATTACH_IN = TR_ATTACH_IN };
+  struct Attachments {
+    std::vector<uint8_t> valid;            // n: the state is valid (solvePrep only admits such)
+    std::vector<int32_t> vertices;         // n x k, -1 padded: nearestStates' rows; all -1 for an invalid state
+    std::vector<double> cost;              // n x k, +inf where padded
+    std::vector<uint8_t> edge_ok;          // n x k: checkMotion(state, vertex) for ATTACH_OUT, checkMotion(vertex, state) for ATTACH_IN
+    std::vector<int32_t> n_fk;             // n x k
+    int64_t n_domain_errors = 0;
+  };
+  /// addMilestone(state, connect = true) for a batch of states (n x state size, flat) without editing the graph: rules A1 - A4 of
+  /// include/tendon_hip.h in one device-resident pass.
+  Attachments attachStates(const std::vector<double> &states, AttachDirection direction = ATTACH_OUT, size_t k = 10,
+                           double max_distance = std::numeric_limits<double>::infinity()) {
+    if (states.size() % S_ != 0) throw std::invalid_argument("attachStates: states must be n x state size");
+    need_validators("attachStates");
+    refuse_loaded("attachStates");
+    sync_tips();
+    const size_t n = states.size() / S_;
+    Attachments a;
+    a.valid.assign(n, 0); a.vertices.assign(n * k, -1); a.cost.assign(n * k, std::numeric_limits<double>::infinity());
+    a.edge_ok.assign(n * k, 0); a.n_fk.assign(n * k, 0);
+    const tr_attach_params prm{(int32_t)k, max_distance};
+    rcheck(tr_roadmap_attach_states(rm_, &mv_->space, &prm, (int32_t)direction, states.data(), (int64_t)n, a.valid.data(), a.vertices.data(),
+                                    a.cost.data(), a.edge_ok.data(), a.n_fk.data(), &a.n_domain_errors));
+    return a;
+  }
+  struct Seeds {                           // per query a list of (vertex, cost) seeds, as CSR
+    std::vector<int64_t> offsets{0};
+    std::vector<int32_t> vertices;
+    std::vector<double> costs;
+    void add_query(const std::vector<int32_t> &v, const std::vector<double> &c) {
+      if (v.size() != c.size()) throw std::invalid_argument("Seeds: a query's vertices and costs differ in length");
+      vertices.insert(vertices.end(), v.begin(), v.end()); costs.insert(costs.end(), c.begin(), c.end());
+      offsets.push_back((int64_t)vertices.size());
+    }
+    size_t queries() const { return offsets.size() - 1; }
+  };
+  struct SeededSolution : Solution {
+    std::vector<int32_t> src_pick, dst_pick;   // indices into the query's seed lists; -1: the direct connection won, or no path
+  };
+  /// Searches from several weighted sources to several weighted targets per query (rules S1 - S4): the answer minimises
+  /// c_i + dist(u_i, v_j) + d_j; direct_cost (empty: none; +inf per query: none) is a connection that bypasses the roadmap and wins ties.
+  SeededSolution solveSeeded(const Seeds &src, const Seeds &dst, const std::vector<double> &direct_cost = {}, int n_threads = 0) {
+    if (src.queries() != dst.queries()) throw std::invalid_argument("solveSeeded: src and dst differ in their number of queries");
+    const size_t n = src.queries();
+    if (!direct_cost.empty() && direct_cost.size() != n) throw std::invalid_argument("solveSeeded: one direct cost per query");
+    refuse_loaded("solveSeeded");
+    sync();
+    SeededSolution s;
+    s.status.resize(n); s.cost.resize(n); s.src_pick.resize(n); s.dst_pick.resize(n);
+    std::vector<int64_t> off(n + 1, 0);
+    rcheck(tr_roadmap_solve_seeded(rm_, (int64_t)n, src.offsets.data(), src.vertices.data(), src.costs.data(), dst.offsets.data(),
+                                   dst.vertices.data(), dst.costs.data(), direct_cost.empty() ? nullptr : direct_cost.data(), n_threads,
+                                   s.status.data(), s.cost.data(), s.src_pick.data(), s.dst_pick.data(), off.data(), &s.stats));
+    fetch_paths(s, off);
+    return s;
+  }
+  struct StateSolution : SeededSolution {      // src_pick / dst_pick: the picked slots of the attach rows
+    std::vector<int32_t> start_vertex, goal_vertex;   // the picked connection vertices; -1 for a direct answer or none
+    std::vector<uint8_t> direct;                      // the query is answered by the edge start state -> goal state
+  };
+  /// solvePrep + solveWithRoadmap between arbitrary start and goal STATES (n x state size each, flat; rules T1 - T3): the motion of a
+  /// solved query is start state, paths[q], goal state, and cost includes both connections.  Nothing is inserted into the graph.
+  StateSolution solveStates(const std::vector<double> &starts, const std::vector<double> &goals, size_t k = 10,
+                            double max_distance = std::numeric_limits<double>::infinity(), int n_threads = 0) {
+    if (starts.size() % S_ != 0 || starts.size() != goals.size()) throw std::invalid_argument("solveStates: starts and goals must both be n x state size");
+    need_validators("solveStates");
+    refuse_loaded("solveStates");
+    sync_tips();
+    const size_t n = starts.size() / S_;
+    StateSolution s;
+    s.status.resize(n); s.cost.resize(n); s.src_pick.resize(n); s.dst_pick.resize(n); s.start_vertex.resize(n); s.goal_vertex.resize(n);
+    s.direct.resize(n);
+    std::vector<int64_t> off(n + 1, 0);
+    const tr_attach_params prm{(int32_t)k, max_distance};
+    rcheck(tr_roadmap_solve_states(rm_, &mv_->space, &prm, starts.data(), goals.data(), (int64_t)n, n_threads, s.status.data(), s.cost.data(),
+                                   s.start_vertex.data(), s.goal_vertex.data(), s.direct.data(), s.src_pick.data(), s.dst_pick.data(), off.data(),
+                                   &s.stats));
+    fetch_paths(s, off);
+    return s;
+  }
   struct AccurateTipResults : TipResults {   // neighbor_vertex: the connection vertex, a state-space neighbour of the goal state
     std::vector<int32_t> ik_vertex;          // the vertex IK started from
     std::array<int64_t, 4> connect_stats{};  // pairs checked, reached, connection vertex != ik_vertex, reached only by this rule
@@ -1611,6 +1693,14 @@ class VoxelCachedLazyPRM {
     if (st == TR_ERR_OUT_OF_RANGE) throw std::out_of_range(m);
     if (st == TR_ERR_INVALID_ARG) throw std::invalid_argument(m);
     throw std::runtime_error(m);
+  }
+  /// the vertex paths of the last solve call into s.paths
+  void fetch_paths(Solution &s, const std::vector<int64_t> &off) const {
+    const size_t n = off.size() - 1;
+    std::vector<int32_t> pv((size_t)off[n]);
+    rcheck(tr_roadmap_fetch_paths(rm_, pv.data(), (int64_t)pv.size()));
+    s.paths.resize(n);
+    for (size_t q = 0; q < n; q++) s.paths[q].assign(pv.begin() + off[q], pv.begin() + off[q + 1]);
   }
   void need_validators(const char *what) const {
     if (!mv_) throw std::runtime_error(std::string(what) + ": missing voxel motion validator");      // the reference's setup_ == false (:1286-1298)

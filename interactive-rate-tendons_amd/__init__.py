@@ -17,12 +17,13 @@ from .collision import VoxelOctree
 from .motion_planning import (VoxelEnvironment, VoxelBackboneValidityChecker, VoxelValidityChecker, VoxelBackboneMotionValidator,
                               VoxelBackboneDiscreteMotionValidator, FunctionTimer, Environment, Problem)
 from . import workloads, distributed, roadmap, rmp, tip_control
-from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan, chained_plan_loaded
+from .roadmap import RoadmapBuilder, VoxelCachedLazyPRM, chained_plan, chained_plan_loaded, chained_plan_from_states
 
 __all__ = [
     "TendonHipError", "InvalidArgument", "OutOfRange", "DomainError", "LengthError", "HipError", "Unsupported",
     "build", "LIB_PATH", "Engine", "unpack_bits", "load_profile_table", "BackboneSpecs", "TendonSpecs", "TendonResult", "TendonRobot", "PointForces",
     "VoxelOctree", "VoxelEnvironment", "VoxelBackboneValidityChecker", "VoxelValidityChecker", "VoxelBackboneMotionValidator", "VoxelBackboneDiscreteMotionValidator", "Environment", "Problem",
     "FunctionTimer", "workloads", "distributed", "roadmap", "RoadmapBuilder", "VoxelCachedLazyPRM", "chained_plan", "chained_plan_loaded",
+    "chained_plan_from_states",
     "tip_control",
 ]

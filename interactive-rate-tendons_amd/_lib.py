@@ -50,6 +50,8 @@ ABI_SYMBOLS = (
     "tr_fk_loaded_tips", "tr_fk_loaded_tips_dev",
     "tr_roadmap_ik_batch_loaded", "tr_roadmap_solve_tips_loaded", "tr_roadmap_set_tips_loaded",
     "tr_set_load_profile", "tr_clear_load_profile", "tr_get_load_profile",
+    "tr_roadmap_attach_states", "tr_roadmap_attach_states_dev", "tr_roadmap_solve_seeded", "tr_roadmap_solve_states",
+    "tr_roadmap_state_query_profile",
 )
 
 
@@ -95,6 +97,13 @@ class TrTipQueryParams(C.Structure):
 
 class TrTipConnectParams(C.Structure):
     _fields_ = [("k_connect", C.c_int32), ("max_distance", C.c_double)]
+
+
+class TrAttachParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("max_distance", C.c_double)]
+
+
+TR_ATTACH_OUT, TR_ATTACH_IN = 0, 1
 
 
 class TrRoadmapStats(C.Structure):
@@ -154,7 +163,7 @@ def _units():
     # roadmap.hip is assembled from parts (one object): every part is listed here, and so kept out of tendon_hip.o's dependencies
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
                     "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp",
-                    "tipq_loaded_kernel.hpp"]
+                    "tipq_loaded_kernel.hpp", "attach_kernel.hpp", "roadmap_attach_host.inc"]
     fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
                "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp", "fk_loaded_body.inc", "fk_loaded_lin_body.inc"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
@@ -406,6 +415,13 @@ def lib():
     L.tr_roadmap_solve_tips_loaded.argtypes = [vp, P(TrSpaceParams), tqp, tcp, shp, elp, i32p, dp, i64, C.c_int32, dp, dp, dp, i32p, i32p, i32p,
                                                dp, dp, P(i64), i32p, dp, P(i64), P(TrRoadmapStats)]
     L.tr_roadmap_set_tips_loaded.argtypes = [vp, shp, elp, P(u64)]
+    atp, u8p = P(TrAttachParams), P(C.c_uint8)
+    L.tr_roadmap_attach_states.argtypes = [vp, P(TrSpaceParams), atp, C.c_int32, dp, i64, u8p, i32p, dp, u8p, i32p, P(i64)]
+    L.tr_roadmap_attach_states_dev.argtypes = [vp, P(TrSpaceParams), atp, C.c_int32, vp, i64, vp, vp, vp, vp, vp, P(i64)]
+    L.tr_roadmap_solve_seeded.argtypes = [vp, i64, P(i64), i32p, dp, P(i64), i32p, dp, dp, C.c_int32, i32p, dp, i32p, i32p, P(i64), P(TrRoadmapStats)]
+    L.tr_roadmap_solve_states.argtypes = [vp, P(TrSpaceParams), atp, dp, dp, i64, C.c_int32, i32p, dp, i32p, i32p, u8p, i32p, i32p, P(i64),
+                                          P(TrRoadmapStats)]
+    L.tr_roadmap_state_query_profile.argtypes = [vp, dp]
     L.tr_set_load_profile.argtypes = [vp, i64, dp, dp]
     L.tr_clear_load_profile.argtypes = [vp]
     L.tr_get_load_profile.argtypes = [vp, dp, i64, P(i64)]

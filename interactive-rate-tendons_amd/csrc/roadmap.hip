@@ -29,6 +29,8 @@
 // lower bounds (tr_roadmap_prepare): distances from a few extremal vertices over the FULL graph; |d(l, v) - d(l, goal)| never
 // exceeds the distance from v to the goal, and stays a lower bound when invalid items leave the graph (distances only
 // grow).  The path A* returns is still the shortest one -- an admissible heuristic only changes how few vertices are expanded.
+// Queries between arbitrary STATES (tr_roadmap_attach_states / _solve_seeded / _solve_states; roadmap_attach_host.inc) run the same rounds
+// with astar_seeded as the search -- on the host threads at every batch size: those calls never launch roadmap_astar.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,6 +56,7 @@
 #include "tipq_kernel.hpp"
 #include "stateq_kernel.hpp"
 #include "tipq_loaded_kernel.hpp"
+#include "attach_kernel.hpp"
 #include "handback_feed.hpp"
 
 namespace {
@@ -218,6 +221,10 @@ struct tr_roadmap {
     double phase_ms[5] = {0, 0, 0, 0, 0};   // of the last call: nearest, IK, edges, select, solve
     int64_t st_ik_rounds = 0;
     int64_t connect_stats[4] = {0, 0, 0, 0};   // of the last *_connect call (tr_roadmap_tip_connect_stats)
+    // the attach phase (roadmap_attach_host.inc): the roadmap's rows with room for ext_cap query rows behind them, what the index pairs refer to
+    double *d_ext = nullptr;
+    int64_t ext_cap = 0;
+    double state_phase_ms[4] = {0, 0, 0, 0};   // of the last tr_roadmap_solve_states: nearest + validity, edges, seeded search, results
   } dt;
 };
 
@@ -261,6 +268,7 @@ void free_dev(tr_roadmap *r) {
 #include "roadmap_search_host.inc"
 #include "roadmap_solve_host.inc"
 #include "roadmap_tips_host.inc"
+#include "roadmap_attach_host.inc"
 
 extern "C" {
 

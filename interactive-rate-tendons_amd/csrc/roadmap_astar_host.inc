@@ -21,28 +21,17 @@ inline double state_distance(const tr_roadmap *r, const double *a, const double 
 // 2^-24 relative per distance; the fp64 path sums behind them differ from A*'s own sums by ~1e-16 per hop)
 constexpr double kLmSlack = 1.0 / (1 << 21);
 
-// astarSearch (:2950-2976): A* with the state-space distance to the goal as heuristic (costHeuristic :2773-2775 ->
-// motionCostHeuristic), edge weights as given; stops when the goal is taken off the open list (AStarGoalVisitor).
-// Vertices / edges known invalid are not part of the graph (the reference has removed them).  Returns false when the
-// goal cannot be reached.  path: goal ... start (vertex ids), path_e: the edges between them.
-// With landmark tables the heuristic is the larger of that distance and the landmark bounds: admissible, so the goal
-// leaves the open list with the same (optimal) cost and, ties apart, the same parents; a vertex whose cost improves after
-// it was expanded is opened again (with the consistent state-space distance alone that never happens).
-// `cap` > 0: the search gives up after that many expansions (*abandoned = true, false returned): tr_roadmap_solve then answers it with a
-// parallel sweep on the device (sweep_search below) -- a search that expands a large part of the graph is a poor fit for one core.
-bool astar(const tr_roadmap *r, Scratch &sc, int32_t start, int32_t goal, std::vector<int32_t> &path, std::vector<int32_t> &path_e,
-           int64_t &expanded, int64_t cap = 0, bool *abandoned = nullptr) {
-  if (sc.node.size() != (size_t)r->V) { sc.node.assign((size_t)r->V, Node{0.0, 0.0, -1, -1, 0u, 0u}); sc.gen = 0; }
-  if (++sc.gen == 0) { for (Node &nd : sc.node) nd.stamp = 0u; sc.gen = 1; }
-  Node *node = sc.node.data();
-  const uint32_t gen = sc.gen;
-  auto &heap = sc.heap;
-  heap.clear();
-  const double *sg = &r->states[(size_t)goal * r->S];
-  const int L = r->lm_n > 0 ? r->lm_n : 0;
-  const float *lg = L ? &r->lm_d[(size_t)goal * L] : nullptr;
-  const double inf = std::numeric_limits<double>::infinity();
-  auto heuristic = [&](int32_t v) -> double {
+// The heuristic of one search towards one goal vertex: the state-space distance (costHeuristic :2773-2775 -> motionCostHeuristic),
+// and with landmark tables the larger of that and the landmark bounds; +inf where a landmark shows v and the goal in different components.
+struct GoalHeuristic {
+  const tr_roadmap *const r;
+  const double *const sg;
+  const int L;
+  const float *const lg;
+  GoalHeuristic(const tr_roadmap *r_, int32_t goal)
+      : r(r_), sg(&r_->states[(size_t)goal * r_->S]), L(r_->lm_n > 0 ? r_->lm_n : 0), lg(L ? &r_->lm_d[(size_t)goal * L] : nullptr) {}
+  double operator()(int32_t v) const {
+    const double inf = std::numeric_limits<double>::infinity();
     double h = state_distance(r, &r->states[(size_t)v * r->S], sg);
     if (L) {
       // (SR_LM_FAR where a vertex is not connected to the landmark: two far entries bound nothing -- their term is hugely negative --, one
@@ -71,7 +60,29 @@ bool astar(const tr_roadmap *r, Scratch &sc, int32_t start, int32_t goal, std::v
       if ((double)best > h) h = (double)best;
     }
     return h;
-  };
+  }
+};
+
+// astarSearch (:2950-2976): A* with the state-space distance to the goal as heuristic (costHeuristic :2773-2775 ->
+// motionCostHeuristic), edge weights as given; stops when the goal is taken off the open list (AStarGoalVisitor).
+// Vertices / edges known invalid are not part of the graph (the reference has removed them).  Returns false when the
+// goal cannot be reached.  path: goal ... start (vertex ids), path_e: the edges between them.
+// With landmark tables the heuristic is the larger of that distance and the landmark bounds: admissible, so the goal
+// leaves the open list with the same (optimal) cost and, ties apart, the same parents; a vertex whose cost improves after
+// it was expanded is opened again (with the consistent state-space distance alone that never happens).
+// `cap` > 0: the search gives up after that many expansions (*abandoned = true, false returned): tr_roadmap_solve then answers it with a
+// parallel sweep on the device (sweep_search below) -- a search that expands a large part of the graph is a poor fit for one core.
+bool astar(const tr_roadmap *r, Scratch &sc, int32_t start, int32_t goal, std::vector<int32_t> &path, std::vector<int32_t> &path_e,
+           int64_t &expanded, int64_t cap = 0, bool *abandoned = nullptr) {
+  if (sc.node.size() != (size_t)r->V) { sc.node.assign((size_t)r->V, Node{0.0, 0.0, -1, -1, 0u, 0u}); sc.gen = 0; }
+  if (++sc.gen == 0) { for (Node &nd : sc.node) nd.stamp = 0u; sc.gen = 1; }
+  Node *node = sc.node.data();
+  const uint32_t gen = sc.gen;
+  auto &heap = sc.heap;
+  heap.clear();
+  const GoalHeuristic heuristic(r, goal);
+  const int L = heuristic.L;
+  const double inf = std::numeric_limits<double>::infinity();
   auto cmp = [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; };
   node[start] = Node{0.0, heuristic(start), start, -1, gen, 0u};
   if (node[start].h == inf) return false;
@@ -136,6 +147,109 @@ bool astar(const tr_roadmap *r, Scratch &sc, int32_t start, int32_t goal, std::v
     if (v == start) break;
     path_e.push_back(node[v].parent_edge);
   }
+  return true;
+}
+
+// The queries of tr_roadmap_solve_seeded: per query CSR lists of source seeds (u_i, c_i) and target seeds (v_j, d_j), an optional direct
+// cost (+inf or no array: none), and the picks that come back (indices into the query's lists; -1: the direct connection, or no answer)
+struct SeededQueries {
+  const int64_t *src_off; const int32_t *src_v; const double *src_c;
+  const int64_t *dst_off; const int32_t *dst_v; const double *dst_c;
+  const double *direct;
+  int32_t *src_pick, *dst_pick;
+};
+
+// astar from several weighted sources to several weighted targets: the sources enter the open list with g = c_i, a virtual goal record
+// is relaxed with g(v_j) + d_j whenever a target vertex is expanded, and the search ends when the virtual goal leaves the open list --
+// with min over i, j of c_i + dist(u_i, v_j) + d_j, summed left to right from the source as every g is.  The heuristic towards the
+// virtual goal is min_j (h(v, v_j) + d_j) with GoalHeuristic's h (landmark terms included): admissible as each term is; vertices are
+// opened again when their cost improves, as in astar.  Seeds whose vertex is known invalid are not seeds.  The direct connection wins
+// when direct <= that minimum; the search stops as soon as nothing on the open list can beat it.  Returns false when there is no
+// answer at all; a direct answer leaves path / path_e empty and the picks -1.  path: v_j ... u_i, path_e: the edges between them.
+bool astar_seeded(const tr_roadmap *r, Scratch &sc, const SeededQueries &s, int64_t q, std::vector<int32_t> &path, std::vector<int32_t> &path_e,
+                  int64_t &expanded) {
+  if (sc.node.size() != (size_t)r->V) { sc.node.assign((size_t)r->V, Node{0.0, 0.0, -1, -1, 0u, 0u}); sc.gen = 0; }
+  if (++sc.gen == 0) { for (Node &nd : sc.node) nd.stamp = 0u; sc.gen = 1; }
+  Node *node = sc.node.data();
+  const uint32_t gen = sc.gen;
+  auto &heap = sc.heap;
+  heap.clear();
+  path.clear(); path_e.clear();
+  s.src_pick[q] = s.dst_pick[q] = -1;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double direct = s.direct ? s.direct[q] : inf;
+  // the targets that count: per vertex its cheapest seed (the first of equal ones), ordered by vertex for the look-up at expansion
+  // (the list lives with the thread: no allocation per query; a GoalHeuristic is four words of pointers into the roadmap, made where it is used)
+  using Target = SeedTarget;
+  auto &tg = sc.targets;
+  tg.clear();
+  for (int64_t j = s.dst_off[q]; j < s.dst_off[q + 1]; j++)
+    if (r->vstat[(size_t)s.dst_v[j]] != V_INVALID) tg.push_back(Target{s.dst_v[j], s.dst_c[j], (int32_t)(j - s.dst_off[q])});
+  std::sort(tg.begin(), tg.end(), [](const Target &a, const Target &b) { return a.v < b.v || (a.v == b.v && (a.d < b.d || (a.d == b.d && a.j < b.j))); });
+  tg.erase(std::unique(tg.begin(), tg.end(), [](const Target &a, const Target &b) { return a.v == b.v; }), tg.end());
+  auto heuristic = [&](int32_t v) {
+    double h = inf;
+    for (const Target &t : tg) { const double x = GoalHeuristic(r, t.v)(v) + t.d; h = x < h ? x : h; }
+    return h;
+  };
+  auto cmp = [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a.first > b.first; };
+  // the sources: parent = the vertex itself, parent_edge = -(seed index) - 2 (so the pick is read off the path's first record)
+  for (int64_t i = s.src_off[q]; !tg.empty() && i < s.src_off[q + 1]; i++) {
+    const int32_t u = s.src_v[i];
+    if (r->vstat[(size_t)u] == V_INVALID) continue;
+    Node &nu = node[u];
+    if (nu.stamp != gen) { nu.stamp = gen; nu.h = heuristic(u); }
+    else if (!(s.src_c[i] < nu.g)) continue;
+    nu.g = s.src_c[i];
+    nu.parent = u; nu.parent_edge = -(int32_t)(i - s.src_off[q]) - 2; nu.closed = 0u;
+    if (nu.h == inf) { nu.closed = 1u; continue; }
+    heap.emplace_back(nu.g + nu.h, u);
+    std::push_heap(heap.begin(), heap.end(), cmp);
+  }
+  constexpr int32_t kGoal = -1;                  // the virtual goal on the open list
+  double best = inf;                             // its g
+  int32_t best_v = -1, best_j = -1;
+  bool found = false;
+  while (!heap.empty()) {
+    std::pop_heap(heap.begin(), heap.end(), cmp);
+    const double f = heap.back().first;
+    const int32_t u = heap.back().second;
+    heap.pop_back();
+    if (f >= direct) break;                      // whatever is still open costs at least the direct connection
+    if (u == kGoal) { if (f == best) { found = true; break; } continue; }
+    if (node[u].closed) continue;
+    node[u].closed = 1u;
+    expanded++;
+    const double gu = node[u].g;
+    const auto t = std::lower_bound(tg.begin(), tg.end(), u, [](const Target &a, int32_t v) { return a.v < v; });
+    if (t != tg.end() && t->v == u && gu + t->d < best) {
+      best = gu + t->d; best_v = u; best_j = t->j;
+      heap.emplace_back(best, kGoal);
+      std::push_heap(heap.begin(), heap.end(), cmp);
+    }
+    for (const Arc *arc = r->adj.data() + r->adj_off[u], *end = r->adj.data() + r->adj_off[u + 1]; arc != end; ++arc) {
+      const int32_t e = arc->e, v = arc->v;
+      if (r->estat[e] == V_INVALID || r->vstat[v] == V_INVALID) continue;
+      const double gv = gu + arc->w;
+      Node &nv = node[v];
+      if (nv.stamp != gen) { nv.stamp = gen; nv.h = heuristic(v); }
+      else if (!(gv < nv.g)) continue;
+      nv.g = gv;
+      if (nv.h == inf) { nv.closed = 1u; continue; }
+      nv.parent = u; nv.parent_edge = e; nv.closed = 0u;
+      heap.emplace_back(gv + nv.h, v);
+      std::push_heap(heap.begin(), heap.end(), cmp);
+    }
+  }
+  if (!found) return direct < inf;
+  // (the records behind best_v are those its g was summed over: a vertex on that chain whose cost improved later would have been
+  // expanded again before the goal, and best with it)
+  for (int32_t v = best_v;; v = node[v].parent) {
+    path.push_back(v);
+    if (node[v].parent_edge < -1) { s.src_pick[q] = -node[v].parent_edge - 2; break; }
+    path_e.push_back(node[v].parent_edge);
+  }
+  s.dst_pick[q] = best_j;
   return true;
 }
 

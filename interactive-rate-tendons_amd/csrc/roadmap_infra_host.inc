@@ -172,9 +172,11 @@ struct Node {                          // A* state of one vertex in one search: 
   int32_t parent, parent_edge;
   uint32_t stamp, closed;
 };
+struct SeedTarget { int32_t v; double d; int32_t j; };     // astar_seeded: a target vertex, its seed cost, the seed's index in the query's list
 struct Scratch {                       // per host thread, reused across queries: generation-stamped A* state
   std::vector<Node> node;
   std::vector<std::pair<double, int32_t>> heap;
+  std::vector<SeedTarget> targets;     // (astar_seeded: the targets of the query in hand)
   uint32_t gen = 0;
   bool trace = false;                  // TENDON_HIP_SEARCH_HIST=<file> (set per call by tr_roadmap_solve): astar fills trace_f
   double trace_f[4] = {0, 0, 0, 0};    // h(start), and the key taken off the list at the 2 000th / 3 000th / 4 000th expansion

@@ -80,6 +80,7 @@ struct Solve {
   double *const cost;
   const RoadmapSwitches &sw;
   const int T;
+  SeededQueries *const seeded;                          // tr_roadmap_solve_seeded: the queries are seed lists (starts / goals null), every search astar_seeded's
   // (the queries' path vectors live with the roadmap: ten thousand small vectors cost 1 - 2 ms to allocate and to free per call otherwise)
   std::vector<std::vector<int32_t>> &paths, &paths_e;   // per query: vertices goal ... start, the edges between them
   std::vector<int64_t> active;                          // the queries still open; a "position" below is an index into it
@@ -98,8 +99,9 @@ struct Solve {
   std::vector<int64_t> hist;                            // (TENDON_HIP_SEARCH_HIST) per position: expansions of its host search, and Scratch::trace_f
   std::vector<double> hist_f;
 
-  Solve(tr_roadmap *r_, const int32_t *starts_, const int32_t *goals_, int64_t n, int32_t *status_, double *cost_, const RoadmapSwitches &sw_, int T_)
-      : r(r_), starts(starts_), goals(goals_), n_queries(n), status(status_), cost(cost_), sw(sw_), T(T_), paths(r_->paths_buf), paths_e(r_->paths_e_buf),
+  Solve(tr_roadmap *r_, const int32_t *starts_, const int32_t *goals_, int64_t n, int32_t *status_, double *cost_, const RoadmapSwitches &sw_, int T_,
+        SeededQueries *seeded_ = nullptr)
+      : r(r_), starts(starts_), goals(goals_), n_queries(n), status(status_), cost(cost_), sw(sw_), T(T_), seeded(seeded_), paths(r_->paths_buf), paths_e(r_->paths_e_buf),
         vmark((size_t)r_->V, 0), emark((size_t)r_->E, 0) {
     if ((int64_t)paths.size() < n_queries) { paths.resize((size_t)n_queries); paths_e.resize((size_t)n_queries); }
     for (int64_t q = 0; q < n_queries; q++) { paths[(size_t)q].clear(); paths_e[(size_t)q].clear(); }
@@ -111,7 +113,7 @@ struct Solve {
     laps.lap("end points + set-up");
     while (!active.empty()) {
       begin_round();
-      const bool on_device = launch_on_device();
+      const bool on_device = !seeded && launch_on_device();     // (seeded searches: the host threads at every batch size)
       begin_host_searches();
       if (!on_device) host_round(todo);
       else if ((rc = shared_round())) return rc;
@@ -155,7 +157,27 @@ struct Solve {
   }
 
   // the query end points first (solvePrep :2978-3010 only admits valid start / goal states)
+  // tr_roadmap_solve_seeded: the seed vertices of unknown validity are tested first, as the end points are; a seed whose vertex is
+  // invalid is no seed (astar_seeded skips it -- also one that a later eager test finds invalid)
+  int seed_vertices() {
+    for (int side = 0; side < 2; side++) {
+      const int64_t n_seeds = (side ? seeded->dst_off : seeded->src_off)[n_queries];
+      const int32_t *sv = side ? seeded->dst_v : seeded->src_v;
+      for (int64_t i = 0; i < n_seeds; i++)
+        if (r->vstat[(size_t)sv[i]] == V_UNKNOWN && !vmark[(size_t)sv[i]]) { vmark[(size_t)sv[i]] = 1; list.push_back(sv[i]); }
+    }
+    if (const int rc = test_listed()) return rc;
+    for (int64_t q = 0; q < n_queries; q++) {
+      status[q] = TR_QUERY_SOLVED;
+      cost[q] = std::numeric_limits<double>::infinity();
+      seeded->src_pick[q] = seeded->dst_pick[q] = -1;
+      active.push_back(q);
+    }
+    return TR_OK;
+  }
+
   int end_points() {
+    if (seeded) return seed_vertices();
     for (int64_t q = 0; q < n_queries; q++) {
       for (int32_t v : {starts[q], goals[q]})
         if (r->vstat[(size_t)v] == V_UNKNOWN && !vmark[(size_t)v]) { vmark[(size_t)v] = 1; list.push_back(v); }
@@ -192,7 +214,7 @@ struct Solve {
   int start_eager_if_large() {
     if (!r->has_caches || (int64_t)active.size() * 256 < r->V + r->E || sw.lazy_only) return TR_OK;
     if (const int rc = test_everything(true)) return rc;
-    if (!went_eager) return TR_OK;
+    if (!went_eager || seeded) return TR_OK;
     // (end points found invalid by that test: their queries end here, as they would have before the first search)
     std::vector<int64_t> keep;
     for (int64_t q : active) if (!invalid_end_point(q)) keep.push_back(q);
@@ -248,7 +270,7 @@ struct Solve {
     todo.resize(active.size());
     for (size_t k = 0; k < active.size(); k++) todo[k] = k;
     const int cmode = sw.components_mode;
-    if ((int64_t)active.size() >= kComponentMinQueries && (cmode == 2 || (cmode == 1 && r->dc.wanted)) && ensure_labels()) cut_by_labels(todo);
+    if (!seeded && (int64_t)active.size() >= kComponentMinQueries && (cmode == 2 || (cmode == 1 && r->dc.wanted)) && ensure_labels()) cut_by_labels(todo);
     t_round = Clock::now();
   }
 
@@ -286,13 +308,18 @@ struct Solve {
 
   // (after the launch: the first one sets the device searches up, and sweep_cap asks whether they are)
   void begin_host_searches() {
-    cap_sweep = sweep_cap(r, sw);
+    cap_sweep = seeded ? 0 : sweep_cap(r, sw);
     if (sw.hist) { hist.assign(active.size(), 0); hist_f.assign(active.size() * 4, 0.0); }
   }
 
   // one query on a host thread: A*, and past sweep_cap expansions the parallel sweep on the device (which failing, A* to the end)
   void search_on_host(Scratch &sc, size_t k, int64_t &ex) {
     const int64_t q = active[k], ex0 = ex;
+    if (seeded) {
+      found[k] = astar_seeded(r, sc, *seeded, q, paths[(size_t)q], paths_e[(size_t)q], ex) ? 1 : 0;
+      if (sw.hist) hist[k] = ex - ex0;
+      return;
+    }
     bool abandoned = false;
     bool f = astar(r, sc, starts[q], goals[q], paths[(size_t)q], paths_e[(size_t)q], ex, cap_sweep, &abandoned);
     if (abandoned) {
@@ -444,13 +471,23 @@ struct Solve {
         for (size_t i = 1; i + 1 < paths[(size_t)q].size() && ok; i++) ok = r->vstat[(size_t)paths[(size_t)q][i]] == V_VALID;
         for (size_t i = 0; i < paths_e[(size_t)q].size() && ok; i++) ok = r->estat[(size_t)paths_e[(size_t)q][i]] == V_VALID;
         if (ok) {
-          if (cost) { double c = 0; for (size_t i = paths_e[(size_t)q].size(); i-- > 0;) c += r->w[(size_t)paths_e[(size_t)q][i]]; cost[q] = c; }
+          if (seeded) cost[q] = seeded_cost(q);
+          else if (cost) { double c = 0; for (size_t i = paths_e[(size_t)q].size(); i-- > 0;) c += r->w[(size_t)paths_e[(size_t)q][i]]; cost[q] = c; }
         } else part[(size_t)t].push_back(q);
       }
     });
     std::vector<int64_t> still;
     for (const auto &p : part) still.insert(still.end(), p.begin(), p.end());    // (ranges in order: the queries keep their order)
     return still;
+  }
+
+  // ((c_i + w_1) + w_2 ...) + d_j from the source along the accepted path: A*'s own g, then the target seed; the direct cost without a path
+  double seeded_cost(int64_t q) const {
+    const int32_t i = seeded->src_pick[q], j = seeded->dst_pick[q];
+    if (i < 0) return seeded->direct[q];
+    double c = seeded->src_c[seeded->src_off[q] + i];
+    for (size_t e = paths_e[(size_t)q].size(); e-- > 0;) c += r->w[(size_t)paths_e[(size_t)q][e]];
+    return c + seeded->dst_c[seeded->dst_off[q] + j];
   }
 
   void paths_out(int64_t *path_offsets) {
@@ -484,7 +521,8 @@ void Solve::report_hist() const {
   for (size_t k = 0; k < active.size(); k++) (found[k] ? f : nf).push_back(hist[k]);
   std::fprintf(stderr, "[tendon_hip] round %lld:\n", (long long)r->st_rounds);
   report_expansions("found", f); report_expansions("not found", nf);
-  if (!sw.hist_path) return;
+  // (the file's columns describe a search between two vertices: a seeded query has seed lists, no `starts` / `goals` -- the summary above is its report)
+  if (!sw.hist_path || seeded) return;
   FILE *fh = std::fopen(sw.hist_path, "a");                   // (a path: one line per search -- expansions against what could predict them)
   if (!fh) return;
   const int L = r->lm_n > 0 ? r->lm_n : 0;

@@ -16,7 +16,7 @@ namespace {
 
 void free_tips(tr_roadmap *r) {
   auto &d = r->dt;
-  void *p[] = {d.d_tips, d.d_states, d.d_soa, d.d_vstat, d.d_present, d.arena};
+  void *p[] = {d.d_tips, d.d_states, d.d_soa, d.d_vstat, d.d_present, d.arena, d.d_ext};
   for (void *q : p) if (q) dev_cache().release(q);
   d = tr_roadmap::DevTips{};
 }

@@ -624,6 +624,158 @@ class VoxelCachedLazyPRM:
         pd = eng._check_dev(d_dist, torch.float64, n * k, "d_dist") if d_dist is not None else None
         self._check(self.lib.tr_roadmap_nearest_states_dev(self._rm, pq, int(n), int(k), float(max_distance), pv, pd))
 
+    # ---- queries between arbitrary states (tr_roadmap_attach_states .. tr_roadmap_solve_states, include/tendon_hip.h: rules A, S, T) ----
+    def _state_rows(self, states, what):
+        S = self.engine.state_size
+        q = np.ascontiguousarray(states, dtype=np.float64)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != S:
+            raise self._L.InvalidArgument("%s must be (n, state_size)" % what)
+        return q
+
+    def _attach_params(self, k, max_distance, motion_validator):
+        L_, mv = self._L, motion_validator
+        sp = L_.TrSpaceParams(0.02, 0.01, 0.0001) if mv is None else \
+            L_.TrSpaceParams(mv.min_tension_change, mv.min_rotation_change, mv.min_retraction_change)
+        return L_.TrAttachParams(int(k), float(max_distance)), sp
+
+    @staticmethod
+    def _direction(direction):
+        try:
+            return {"out": L.TR_ATTACH_OUT, "in": L.TR_ATTACH_IN}[direction]
+        except KeyError:
+            raise L.InvalidArgument("direction must be 'out' or 'in'") from None
+
+    def attach_states(self, states, direction="out", k=10, max_distance=np.inf, motion_validator=None):
+        """addMilestone(state, connect = true) for a batch of off-roadmap states without editing the graph (rules A1 - A4 in
+        include/tendon_hip.h): per state its validity, its k nearest valid roadmap vertices (nearest_states' rows; -1 / +inf for an
+        invalid state) and checkMotion on every connection -- direction 'out': state -> vertex, 'in': vertex -> state -- in one
+        device-resident pass.  -> dict(valid (n,) bool, vertices (n, k) int32, cost (n, k), edge_ok (n, k) bool, n_fk (n, k) int32,
+        n_domain_errors)."""
+        C = self._C
+        self._refuse_loaded("attach_states")
+        q = self._state_rows(states, "states")
+        n, k = len(q), int(k)
+        ap, sp = self._attach_params(k, max_distance, motion_validator)
+        kk = max(k, 0)
+        valid, ok = np.zeros(n, dtype=np.uint8), np.zeros((n, kk), dtype=np.uint8)
+        idx, cost, nfk = np.full((n, kk), -1, dtype=np.int32), np.full((n, kk), np.inf), np.zeros((n, kk), dtype=np.int32)
+        nd = C.c_int64(0)
+        u8, i32, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        self._check(self.lib.tr_roadmap_attach_states(self._rm, C.byref(sp), C.byref(ap), self._direction(direction), q.ctypes.data_as(dp), n,
+                                                      valid.ctypes.data_as(u8), idx.ctypes.data_as(i32), cost.ctypes.data_as(dp),
+                                                      ok.ctypes.data_as(u8), nfk.ctypes.data_as(i32), C.byref(nd)))
+        return dict(valid=valid.astype(bool), vertices=idx, cost=cost, edge_ok=ok.astype(bool), n_fk=nfk, n_domain_errors=int(nd.value))
+
+    def attach_states_dev(self, d_states, n, d_valid, d_vertices, d_cost, d_edge_ok, d_n_fk=None, direction="out", k=10, max_distance=np.inf,
+                          motion_validator=None):
+        """attach_states on device tensors of the checker's GPU: float64 (n, S) -> uint8 (n,), int32 (n, k), float64 (n, k), uint8 (n, k)
+        [, int32 (n, k)]; returns n_domain_errors."""
+        import torch
+        C, eng = self._C, self.engine
+        self._refuse_loaded("attach_states_dev")
+        n, k = int(n), int(k)
+        ap, sp = self._attach_params(k, max_distance, motion_validator)
+        ps = eng._check_dev(d_states, torch.float64, eng.state_size * n, "d_states")
+        pv = eng._check_dev(d_valid, torch.uint8, n, "d_valid")
+        pi = eng._check_dev(d_vertices, torch.int32, n * k, "d_vertices")
+        pc = eng._check_dev(d_cost, torch.float64, n * k, "d_cost")
+        po = eng._check_dev(d_edge_ok, torch.uint8, n * k, "d_edge_ok")
+        pn = eng._check_dev(d_n_fk, torch.int32, n * k, "d_n_fk") if d_n_fk is not None else None
+        nd = C.c_int64(0)
+        self._check(self.lib.tr_roadmap_attach_states_dev(self._rm, C.byref(sp), C.byref(ap), self._direction(direction), ps, n, pv, pi, pc, po,
+                                                          pn, C.byref(nd)))
+        return int(nd.value)
+
+    def _seed_csr(self, seeds, what):
+        """Seeds as CSR: a triple (offsets, vertices, costs), or per query a pair (vertices, costs)."""
+        if isinstance(seeds, tuple) and len(seeds) == 3:
+            off, v, c = seeds
+            off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        else:
+            off = np.zeros(len(seeds) + 1, dtype=np.int64)
+            for q, (vq, cq) in enumerate(seeds):
+                if len(vq) != len(cq):
+                    raise self._L.InvalidArgument("%s: a query's vertices and costs differ in length" % what)
+                off[q + 1] = off[q] + len(vq)
+            v = np.concatenate([np.asarray(vq, dtype=np.int32).reshape(-1) for vq, _ in seeds]) if len(seeds) else np.zeros(0, np.int32)
+            c = np.concatenate([np.asarray(cq, dtype=np.float64).reshape(-1) for _, cq in seeds]) if len(seeds) else np.zeros(0)
+        v = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+        c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+        if len(off) < 1 or len(v) != len(c) or (len(off) and off[-1] != len(v)):
+            raise self._L.InvalidArgument("%s: offsets, vertices and costs do not match" % what)
+        return off, v, c
+
+    def _solve_result(self, status, cost, off, st):
+        C = self._C
+        pv = np.zeros(int(off[-1]), dtype=np.int32)
+        self._check(self.lib.tr_roadmap_fetch_paths(self._rm, pv.ctypes.data_as(C.POINTER(C.c_int32)), len(pv)))
+        self.stats = dict(rounds=st.rounds, items_checked=st.items_checked, astar_runs=st.astar_runs, expanded=st.expanded)
+        return dict(status=status, cost=cost, path_offsets=off, path_vertices=pv, paths=_Paths(pv, off))
+
+    def solve_seeded(self, src, dst, direct_cost=None, n_threads=0):
+        """Searches from several weighted sources to several weighted targets per query (tr_roadmap_solve_seeded; rules S1 - S4): src /
+        dst are per query a pair (vertices, costs), or CSR triples (offsets, vertices, costs); direct_cost (n,), optional: the cost of a
+        connection that bypasses the roadmap (inf: none).  The answer minimises c_i + dist(u_i, v_j) + d_j over the roadmap minus what is
+        invalid in the current grid.  -> solveWithRoadmap's fields plus src_pick, dst_pick (indices into the query's seed lists; -1
+        when the direct connection won or there is no path) and direct (bool)."""
+        C, L_ = self._C, self._L
+        self._refuse_loaded("solve_seeded")
+        so, sv, sc = self._seed_csr(src, "src")
+        do, dv, dc = self._seed_csr(dst, "dst")
+        if len(so) != len(do):
+            raise L_.InvalidArgument("src and dst differ in their number of queries")
+        n = len(so) - 1
+        d = None
+        if direct_cost is not None:
+            d = np.ascontiguousarray(direct_cost, dtype=np.float64).reshape(-1)
+            if len(d) != n:
+                raise L_.InvalidArgument("direct_cost must be (n_queries,)")
+        status, cost, off = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n + 1, dtype=np.int64)
+        sp_, dp_ = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+        st = L_.TrRoadmapStats()
+        i32, i64, dp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        self._check(self.lib.tr_roadmap_solve_seeded(
+            self._rm, n, so.ctypes.data_as(i64), sv.ctypes.data_as(i32), sc.ctypes.data_as(dp), do.ctypes.data_as(i64), dv.ctypes.data_as(i32),
+            dc.ctypes.data_as(dp), d.ctypes.data_as(dp) if d is not None else None, int(n_threads), status.ctypes.data_as(i32),
+            cost.ctypes.data_as(dp), sp_.ctypes.data_as(i32), dp_.ctypes.data_as(i32), off.ctypes.data_as(i64), C.byref(st)))
+        o = self._solve_result(status, cost, off, st)
+        o.update(src_pick=sp_, dst_pick=dp_, direct=(status == L_.TR_QUERY_SOLVED) & (sp_ < 0))
+        return o
+
+    def solve_states(self, starts, goals, k=10, max_distance=np.inf, motion_validator=None, n_threads=0):
+        """solvePrep + solveWithRoadmap between arbitrary STATES (tr_roadmap_solve_states; rules T1 - T3), e.g. Problem.start_state() and
+        goal_state(): the starts attached 'out', the goals 'in' and the direct edges in one attach pass, then the seeded search.
+        -> solveWithRoadmap's fields plus start_vertex, goal_vertex (the picked connection vertices; -1 for a direct answer or none),
+        direct (bool), src_pick, dst_pick (the picked slots of the attach rows).  A solved query's motion is start state, paths[q],
+        goal state; cost includes both connections."""
+        C, L_ = self._C, self._L
+        self._refuse_loaded("solve_states")
+        s, g = self._state_rows(starts, "starts"), self._state_rows(goals, "goals")
+        if len(s) != len(g):
+            raise L_.InvalidArgument("starts and goals differ in length")
+        n = len(s)
+        ap, sp = self._attach_params(k, max_distance, motion_validator)
+        status, cost, off = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n + 1, dtype=np.int64)
+        sv, gv, sp_, dp_ = (np.full(n, -1, dtype=np.int32) for _ in range(4))
+        direct = np.zeros(n, dtype=np.uint8)
+        st = L_.TrRoadmapStats()
+        i32, i64, dp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        self._check(self.lib.tr_roadmap_solve_states(
+            self._rm, C.byref(sp), C.byref(ap), s.ctypes.data_as(dp), g.ctypes.data_as(dp), n, int(n_threads), status.ctypes.data_as(i32),
+            cost.ctypes.data_as(dp), sv.ctypes.data_as(i32), gv.ctypes.data_as(i32), direct.ctypes.data_as(C.POINTER(C.c_uint8)),
+            sp_.ctypes.data_as(i32), dp_.ctypes.data_as(i32), off.ctypes.data_as(i64), C.byref(st)))
+        o = self._solve_result(status, cost, off, st)
+        o.update(start_vertex=sv, goal_vertex=gv, direct=direct.astype(bool), src_pick=sp_, dst_pick=dp_)
+        return o
+
+    def state_query_profile(self):
+        """Host wall time (ms) of the phases of the last solve_states (tr_roadmap_state_query_profile)."""
+        o = (self._C.c_double * 4)()
+        self._check(self.lib.tr_roadmap_state_query_profile(self._rm, o))
+        return dict(nearest_ms=o[0], edges_ms=o[1], search_ms=o[2], results_ms=o[3])
+
     def _connect_stats(self):
         o = (self._C.c_int64 * 4)()
         self._check(self.lib.tr_roadmap_tip_connect_stats(self._rm, o))
@@ -880,6 +1032,78 @@ def chained_plan_loaded(prm, start_vertex, waypoints, wrench=None, dist=None, fr
     return _chain_hops(prm, start_vertex, waypoints, lambda at, req: prm.solve_to_tips_loaded(
         at, req, wrench=wrench, dist=dist, frame=frame, tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, shoot=shoot,
         n_threads=n_threads, connect_k=connect_k, connect_max_distance=connect_max_distance))
+
+
+def chained_plan_from_states(prm, start_states, waypoints, tolerance=1e-4, k=5, motion_validator=None, ik=None, n_threads=0, connect_k=0,
+                             connect_max_distance=np.inf, attach_k=10, attach_max_distance=np.inf):
+    """The loop of apps/roadmap_chained_plan.cpp:533-679 from the robot's actual STATE (pdef->getStartState(0), then the state every
+    hop ends in): chain c starts at start_states[c] -- any valid state, a roadmap vertex or not -- and visits the tips waypoints[c, 0],
+    waypoints[c, 1], ...  Hop h of EVERY chain is one roadmap_ik_batch (the goal state and its connection vertex), one attach_states of
+    the current states (direction 'out', attach_k neighbours) and one solve_seeded: the sources are the current state's valid
+    connections at their distances -- and, after a hop, the connection vertex that hop ended at when it is not among them, provided
+    checkMotion(state, vertex) holds (one validate_edges call per hop over such chains: the IK checked vertex -> state only, and no
+    symmetry of checkMotion is assumed) -- the single target is the request's connection vertex at the connecting edge's distance.  No
+    start vertex is needed and no hop is FORCED through the previous hop's reversed edge, as chained_plan's prefix is: that edge is
+    one source among the others, and the search picks the cheapest way onto the roadmap.  A chain stops at its first hop that is not solved.
+    -> dict(hops: per hop roadmap_ik_batch's and solve_seeded's fields plus start_state (C, S), start_vertex (C,: the picked source
+            vertex), total_cost (C,), active (C,), chains; cost (C,), solved (C,), final_state, final_vertex)."""
+    prm._refuse_loaded("chained_plan_from_states")
+    eng = prm.engine
+    wp = np.asarray(waypoints, dtype=np.float64)
+    if wp.ndim == 2:
+        wp = wp[None]
+    if wp.ndim != 3 or wp.shape[2] != 3:
+        raise L.InvalidArgument("waypoints must be (chains, hops, 3)")
+    C_, H = wp.shape[0], wp.shape[1]
+    state = np.array(prm._state_rows(start_states, "start_states"))
+    if len(state) != C_:
+        raise L.InvalidArgument("one start state per chain")
+    at = np.full(C_, -1, dtype=np.int32)                     # the connection vertex the chain's last hop ended at
+    active = np.ones(C_, dtype=bool)
+    total = np.zeros(C_)
+    hops = []
+    for h in range(H):
+        idx = np.flatnonzero(active)
+        res = dict(active=active.copy(), start_state=state.copy(), start_vertex=np.full(C_, -1, dtype=np.int32),
+                   total_cost=np.full(C_, np.inf), chains=idx)
+        if len(idx):
+            ikr = prm.roadmap_ik_batch(wp[idx, h], tolerance=tolerance, k=k, motion_validator=motion_validator, ik=ik, connect_k=connect_k,
+                                       connect_max_distance=connect_max_distance)
+            att = prm.attach_states(state[idx], "out", k=attach_k, max_distance=attach_max_distance, motion_validator=motion_validator)
+            nv = ikr["neighbor_vertex"]
+            has_goal = ikr["outcome"] != L.TR_TIPQ_NO_NEIGHBOR
+            # the way back onto the roadmap through the last hop's connection vertex: the IK checked that edge vertex -> state only, so
+            # where the vertex is not in the attach row (whose slot carries its own verdict) the edge state -> vertex is checked here
+            back = [j for j, c in enumerate(idx) if at[c] >= 0 and at[c] not in att["vertices"][j]]
+            back_ok = np.zeros(len(idx), dtype=bool)
+            if back:
+                mv = motion_validator
+                tol = () if mv is None else (mv.min_tension_change, mv.min_rotation_change, mv.min_retraction_change)
+                back_ok[back] = eng.validate_edges(state[idx[back]], prm.states[at[idx[back]]], *tol)["valid"]
+            src, dst = [], []
+            for j, c in enumerate(idx):
+                ok = att["edge_ok"][j]
+                sv, sc = att["vertices"][j][ok], att["cost"][j][ok]
+                if back_ok[j]:
+                    sv = np.append(sv, at[c])
+                    sc = np.append(sc, eng.state_distance(state[c:c + 1], prm.states[at[c]:at[c] + 1])[0])
+                src.append((sv, sc))
+                dst.append(((nv[j:j + 1], eng.state_distance(prm.states[nv[j]:nv[j] + 1], ikr["controls"][j:j + 1])) if has_goal[j]
+                            else (np.zeros(0, np.int32), np.zeros(0))))
+            r = prm.solve_seeded(src, dst, n_threads=n_threads)
+            r["status"] = np.where(has_goal, r["status"], L.TR_QUERY_INVALID_GOAL).astype(np.int32)     # as solve_to_tips ends such a request
+            res.update(ikr)
+            res.update(r)
+            ok = r["status"] == L.TR_QUERY_SOLVED
+            res["total_cost"][idx] = np.where(ok, r["cost"], np.inf)
+            pick = np.array([src[j][0][r["src_pick"][j]] if ok[j] else -1 for j in range(len(idx))], dtype=np.int32)
+            res["start_vertex"][idx] = pick
+            total[idx[ok]] += r["cost"][ok]
+            state[idx[ok]] = ikr["controls"][ok]
+            at[idx[ok]] = nv[ok]
+            active[idx[~ok]] = False
+        hops.append(res)
+    return dict(hops=hops, cost=np.where(active, total, np.inf), solved=active.copy(), final_state=state, final_vertex=at)
 
 
 def _chain_hops(prm, start_vertex, waypoints, solve):
