@@ -88,6 +88,13 @@ int tr_state_size(const tr_ctx *ctx);           /* TendonRobot::state_size, Tend
 int tr_num_points(const tr_ctx *ctx);           /* |t_range(0, L, dL)| = max backbone points    */
 int tr_device(const tr_ctx *ctx);
 
+/* Opens (on != 0) or closes the context to LOADED shapes of a robot with retraction.  A context never opened refuses such a robot in
+ * every loaded call with one message, TR_ERR_UNSUPPORTED, as it always did.  Opened: tr_fk_loaded_batch*, tr_fk_loaded_tips* (and with
+ * them general_shape and the validity of loaded shapes) take the robot, see tr_fk_loaded_batch; the loaded calls built on them --
+ * edges, roadmap builds, IK, Jacobian and compliance, tip queries, load profiles -- keep answering TR_ERR_UNSUPPORTED, now each under
+ * its own name.  No effect on a robot without retraction. */
+int tr_set_loaded_retraction(tr_ctx *ctx, int on);
+
 /* Home shape tendon lengths at s_start = 0 (TendonRobot::home_shape, tendon/TendonRobot.cpp:249-314) */
 int tr_home_lengths(const tr_ctx *ctx, double *L_i /*[n_tendons]*/);
 
@@ -262,7 +269,14 @@ typedef struct {
  *   fk_calls_out n: integrations of the solve (1 for the start, 13 per round after it; the launch that writes the outputs
  *   is not counted); rounds_out: rounds run, a host pointer in both forms.
  * Every output may be NULL.  A problem's result does not depend on the other problems of the call, their order or the chunking.
- * Robots with retraction: TR_ERR_UNSUPPORTED. */
+ * Robots with retraction: TR_ERR_UNSUPPORTED unless the context was opened to them (tr_set_loaded_retraction).  Then
+ * (general_tension_shape's s_start, TendonRobot.cpp:689-952, read from the state as general_shape reads it,
+ * TendonRobot.h:177-208): a problem shoots on t_range(s_start, L, dL) from the unloaded solution AT its s_start; it has
+ * n_points[i] <= P points, p and R start at row 0 and are NaN in the rows past n_points[i], as tr_fk_batch's.  s_start >= L (it is
+ * truncated to L): one point at the origin, L = L_i = 0, n_points = 1, converged = 1 after zero iterations (the reference's early
+ * return); s_start < 0: the same with converged = 0, as tr_fk_batch reports it.  The loaded calls built on this one -- edges, roadmap
+ * builds, IK, Jacobian and compliance, tip queries, load profiles -- answer TR_ERR_UNSUPPORTED on such a robot, each under its own
+ * name; on a context that was never opened every loaded call answers with the one message it always had. */
 int tr_fk_loaded_batch(tr_ctx *ctx, const tr_shoot_params *params, const double *states, int64_t n,
                        const double *wrench, int64_t wrench_ld, const double *dist, int64_t dist_ld, const double *guess,
                        double *p, double *R, double *L, double *L_i, uint8_t *converged, int32_t *n_points,
@@ -270,12 +284,25 @@ int tr_fk_loaded_batch(tr_ctx *ctx, const tr_shoot_params *params, const double 
                        int64_t *rounds_out);
 /* Device form: device arrays in tr_fk_batch_dev's layout (d_px[j*ld + i], d_R [9][P][ld], d_Li [N][ld]; ld >= n, a multiple of 64),
  * host params / rounds_out.  d_px, d_py, d_pz, d_Li, d_converged feed tr_validate_shapes_dev unchanged.  It synchronises `stream`
- * once per round to read the number of problems still active (4 bytes through pinned memory). */
+ * once per round to read the number of problems still active (4 bytes through pinned memory).
+ * With retraction enabled a configuration has d_n_points[i] <= P points and its rows are aligned at the tip, as tr_fk_batch_dev
+ * describes: point j is in row j + (P - d_n_points[i]) of the planes and of d_R; the rows before it are not written. */
 int tr_fk_loaded_batch_dev(tr_ctx *ctx, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
                            const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess,
                            double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L, double *d_Li, uint8_t *d_converged,
                            int32_t *d_n_points, double *d_vu0_out, double *d_vuL_out, double *d_residual_out, int32_t *d_iters_out,
                            int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
+
+/* The same for retraction-enabled robots, whose home-shape tendon lengths depend on the configuration (home_shape(s_start).L_i,
+ * d_home_Li [N][ld]): the loaded twin of tr_fk_batch_retraction_dev.  d_n_points and d_home_Li are mandatory outputs; d_px, d_py,
+ * d_pz, d_n_points, d_Li, d_home_Li and d_converged feed tr_validate_shapes_retraction_dev unchanged.  The call's name says what it
+ * is for: it needs no tr_set_loaded_retraction.  A robot without retraction: TR_ERR_INVALID_ARG. */
+int tr_fk_loaded_batch_retraction_dev(tr_ctx *ctx, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
+                                      const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld,
+                                      const double *d_guess, double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L,
+                                      double *d_Li, uint8_t *d_converged, int32_t *d_n_points, double *d_home_Li, double *d_vu0_out,
+                                      double *d_vuL_out, double *d_residual_out, int32_t *d_iters_out, int32_t *d_fk_calls_out,
+                                      int64_t *rounds_out, void *stream);
 
 /* A load profile: a scalar weight w(s) along arc length that every loaded call of the context applies to its distributed load.  At
  * every RK4 stage a problem sees w(s) f_e, w(s) l_e, where (f_e, l_e) is the row the call would use without a profile (per-problem
@@ -291,7 +318,8 @@ int tr_fk_loaded_batch_dev(tr_ctx *ctx, const tr_shoot_params *params, const dou
  * stage's weight from it and form w * f_e[q], w * l_e[q], each product rounded once.
  * tr_set_load_profile first waits for the context's device work (a queued *_dev call keeps the profile it was issued under), then
  * installs the table; tr_clear_load_profile removes it (the calls run as without one).  Robots with retraction:
- * TR_ERR_UNSUPPORTED.  Bad knots or weights: TR_ERR_INVALID_ARG. */
+ * TR_ERR_UNSUPPORTED (the table has no entries for a configuration's own first interval).  Bad knots or weights:
+ * TR_ERR_INVALID_ARG. */
 int tr_set_load_profile(tr_ctx *ctx, int64_t n_knots, const double *s, const double *w);
 int tr_clear_load_profile(tr_ctx *ctx);
 /* The installed table: *n_out = its length (0: no profile installed); table_out (may be NULL) receives min(capacity, *n_out) entries. */
@@ -510,7 +538,8 @@ int tr_connect_edges_loaded_indexed(tr_ctx *ctx, const tr_space_params *sp, cons
  *   tips n x 3, converged n, vu0 n x 6 (the accepted base strains) -- all optional
  *   rounds_out  optional int64[2]: shooting rounds (one host synchronisation each), the sum of the problems' integrations
  * A state whose shooting does not converge has converged = 0 and the tip of its last strains: never an error of the call.  Robots with
- * retraction: TR_ERR_UNSUPPORTED; n == 0: TR_OK.  The _dev form takes device arrays; its run is the null stream's (the device is
+ * retraction: TR_ERR_UNSUPPORTED, or, on a context opened by tr_set_loaded_retraction, taken as tr_fk_loaded_batch takes them
+ * (s_start >= L or < 0: the origin); n == 0: TR_OK.  The _dev form takes device arrays; its run is the null stream's (the device is
  * drained before it) and ends synchronised.  A state's result does not depend on the batch or on TENDON_HIP_SHOOT_CHUNK. */
 int tr_fk_loaded_tips(tr_ctx *ctx, const tr_shoot_params *shoot, const double *states, int64_t n, const double *wrench, int64_t wrench_ld,
                       const double *dist, int64_t dist_ld, const double *guess, double *tips, uint8_t *converged, double *vu0,

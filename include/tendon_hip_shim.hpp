@@ -235,7 +235,8 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     std::vector<int32_t> np(n);
     if (iters) iters->resize(n);
     if (fk_calls) fk_calls->resize(n);
-    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error)
+    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error, unless set_loaded_retraction() opened the
+    // context to it; then every result has the state's own point count np[i], its points from row 0)
     check(c, tr_fk_loaded_batch(c, &prm, states.data(), (int64_t)n, wrench.data(), wrench.size() == 6 ? 0 : 6,
                                 dist.empty() ? nullptr : dist.data(), dist.size() == 6 ? 0 : 6,
                                 guess.empty() ? nullptr : guess.data(), p.data(), R.data(), L.data(), Li.data(), conv.data(), np.data(),
@@ -246,7 +247,13 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     for (size_t i = 0; i < n; i++) {
       TendonResult &res = out[i];
       const size_t m = (size_t)np[i];
-      res.t.assign(tg.begin(), tg.begin() + m);
+      if (enable_retraction) {
+        // t_range(s_start, L, dL) spaces its abscissae from the tip: the shared grid's last m - 1 behind the state's own s_start
+        res.t.assign(tg.end() - m, tg.end());
+        res.t[0] = std::min(states[i * S + S - 1], specs.L);
+      } else {
+        res.t.assign(tg.begin(), tg.begin() + m);
+      }
       res.p.resize(m); res.R.resize(m);
       for (size_t j = 0; j < m; j++) {
         for (int k = 0; k < 3; k++) res.p[j][k] = p[(i * P + j) * 3 + k];
@@ -262,6 +269,10 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     }
     return out;
   }
+
+  /// tr_set_loaded_retraction: opens (or closes) this robot's context to LOADED shapes of a robot with retraction -- general_shape,
+  /// generalShapeBatch and loaded_tips_batch then take it; the loaded calls above them keep throwing std::runtime_error.
+  void set_loaded_retraction(bool on = true) const { tr_ctx *c = context(); check(c, tr_set_loaded_retraction(c, on ? 1 : 0)); }
 
   /// A load profile (tr_set_load_profile): the piecewise-linear weight w(arc length) over the knots (s[k], w[k]) that every loaded
   /// call of this robot's context applies to its distributed load from now on: general_shape, generalShapeBatch, the loaded tip
@@ -342,7 +353,7 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
     LoadedTips out;
     out.tips.resize(3 * n); out.vu0.resize(6 * n); out.converged.resize(n);
     int64_t r2[2] = {0, 0};
-    // (a retraction-enabled robot: TR_ERR_UNSUPPORTED, rethrown as std::runtime_error)
+    // (a retraction-enabled robot: as in generalShapeBatch; opened, s_start >= L gives the origin)
     check(c, tr_fk_loaded_tips(c, &prm, states.data(), (int64_t)n, w.data(), turn ? 6 : 0, d.data(), turn ? 6 : 0, nullptr, out.tips.data(),
                                out.converged.data(), out.vu0.data(), r2));
     out.rounds = r2[0]; out.n_integrations = r2[1];

@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "tr_roadmap_tip_query_profile",
     "tr_roadmap_nearest_states", "tr_roadmap_nearest_states_dev", "tr_roadmap_ik_batch_connect", "tr_roadmap_solve_tips_connect",
     "tr_roadmap_tip_connect_stats",
-    "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev",
+    "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev", "tr_fk_loaded_batch_retraction_dev", "tr_set_loaded_retraction",
     "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
     "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
     "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
@@ -156,7 +156,7 @@ OBJ_DIR = os.path.join(SRC_DIR, "_obj")
 def _units():
     """(object name, source, extra flags): the C ABI + K2..K6, the cache merge, and K1 once per
     (tendon count, kernel: shared grid / retraction / fused with K2 / verdict-only / verdict-only with retraction / edge queue /
-    loaded / loaded under a load profile) so its instantiations compile in parallel, and the linearisation kernel of the loaded IK
+    loaded / loaded under a load profile / loaded with retraction) so its instantiations compile in parallel, and the linearisation kernel of the loaded IK
     once per tendon count and form (fk_lin_inst.hip: files of its own, so the K1 units keep their dependencies)."""
     fk_deps = ["fk_inst.hip", "fk_launch.hpp", "fk_kernel.hpp", "fk_retract_kernel.hpp", "fused_kernel.hpp", "verdict_kernel.hpp",
                "sweep_kernel.hpp", "sphere_kernel.hpp", "tr_types.hpp"]
@@ -164,7 +164,7 @@ def _units():
     roadmap_deps = ["roadmap.hip", "roadmap_kernel.hpp", "search_kernel.hpp", "handback_feed.hpp", "roadmap_infra_host.inc", "roadmap_astar_host.inc",
                     "roadmap_components_host.inc", "roadmap_search_host.inc", "roadmap_solve_host.inc", "roadmap_tips_host.inc", "tipq_kernel.hpp", "stateq_kernel.hpp",
                     "tipq_loaded_kernel.hpp", "attach_kernel.hpp", "roadmap_attach_host.inc"]
-    fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
+    fk_only = ["fk_inst.hip", "fk_kernel.hpp", "fk_retract_kernel.hpp", "fk_loaded_retract_kernel.hpp", "cache_merge.hip", "sample.hip", "edge_queue_kernel.hpp",
                "fk_lin_inst.hip", "fk_loaded_lin_kernel.hpp", "fk_loaded_body.inc", "fk_loaded_lin_body.inc"] + roadmap_deps
     main_deps = [f for f in os.listdir(SRC_DIR) if not f.startswith("_") and f not in fk_only]
     u = [("tendon_hip.o", "tendon_hip.hip", [], main_deps + [HEADER]),
@@ -173,10 +173,11 @@ def _units():
          ("sample.o", "sample.hip", [], ["sample.hip", "sample.hpp", "tr_types.hpp"])]
     q_deps = fk_deps + ["edge_queue_kernel.hpp", "edge_kernel.hpp"]
     l_deps = fk_deps + ["fk_loaded_kernel.hpp", "fk_loaded_body.inc"]
+    lr_deps = l_deps + ["fk_loaded_retract_kernel.hpp"]
     for n in range(1, 9):
-        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l"), (7, "p")):
+        for kind, tag in ((0, "u"), (1, "r"), (2, "f"), (3, "v"), (4, "w"), (5, "q"), (6, "l"), (7, "p"), (8, "m")):
             u.append(("fk_%s%d.o" % (tag, n), "fk_inst.hip", ["-DTRK_INST_N=%d" % n, "-DTRK_INST_KIND=%d" % kind],
-                      q_deps if kind == 5 else (l_deps if kind in (6, 7) else fk_deps)))
+                      q_deps if kind == 5 else (l_deps if kind in (6, 7) else (lr_deps if kind == 8 else fk_deps))))
     lin_deps = ["fk_lin_inst.hip", "fk_lin_launch.hpp", "fk_loaded_lin_kernel.hpp", "fk_loaded_kernel.hpp", "edge_sincos.hpp", "fk_launch.hpp",
                 "fk_kernel.hpp", "tr_types.hpp", "fk_loaded_body.inc", "fk_loaded_lin_body.inc"]
     for n in range(1, 9):
@@ -380,6 +381,8 @@ def lib():
     shp = P(TrShootParams)
     L.tr_fk_loaded_batch.argtypes = [vp, shp, dp, i64, dp, i64, dp, i64, dp, dp, dp, dp, dp, P(C.c_uint8), i32p, dp, dp, dp, i32p, i32p, P(i64)]
     L.tr_fk_loaded_batch_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
+    L.tr_set_loaded_retraction.argtypes = [vp, C.c_int]
+    L.tr_fk_loaded_batch_retraction_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     elp = P(TrEdgeLoads)
     L.tr_validate_edges_loaded.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, dp, i64, P(C.c_uint64), dp, i32p, P(i64), P(i64), P(i64)]
     L.tr_validate_edges_loaded_indexed.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, i64, i32p, i64, P(C.c_uint64), i32p, P(i64), P(i64), P(i64)]

@@ -1,5 +1,5 @@
 // fk_inst.hip -- one K1 instantiation set per object file: compiled once per tendon count and
-// kernel with -DTRK_INST_N=<1..8> -DTRK_INST_KIND=<0 uniform | 1 retract | 2 fused with K2 | 3 verdict-only | 4 verdict-only, retraction | 5 edge queue | 6 loaded | 7 loaded under a load profile>
+// kernel with -DTRK_INST_N=<1..8> -DTRK_INST_KIND=<0 uniform | 1 retract | 2 fused with K2 | 3 verdict-only | 4 verdict-only, retraction | 5 edge queue | 6 loaded | 7 loaded under a load profile | 8 loaded, retraction>
 // (see _lib.py: build()).
 #include "fk_launch.hpp"
 #include "fk_kernel.hpp"
@@ -18,6 +18,8 @@
 #elif TRK_INST_KIND == 6 || TRK_INST_KIND == 7
 #define TRK_LOADED_WITH_INTEGRATOR
 #include "fk_loaded_kernel.hpp"
+#elif TRK_INST_KIND == 8
+#include "fk_loaded_retract_kernel.hpp"
 #endif
 
 namespace trk {
@@ -78,6 +80,21 @@ static void go(const FkLaunch &a, const LoadedIn &in) {
 template <> void launch_fk_loaded_profile<TRK_INST_N>(const FkLaunch &a, const LoadedIn &in) {
   if (a.rotation) { if (a.write_R) go<true, true>(a, in); else go<true, false>(a, in); }
   else            { if (a.write_R) go<false, true>(a, in); else go<false, false>(a, in); }
+}
+#elif TRK_INST_KIND == 8
+template <bool ROT, bool WR>
+static void go(const FkLaunch &a, const LoadedIn &in) {
+  const unsigned grid = (unsigned)((a.n + 63) / 64);
+  hipLaunchKernelGGL((fk_loaded_retract<TRK_INST_N, ROT, WR>), dim3(grid), dim3(64), 0, a.stream, a.d_states, a.n, a.ld, a.K, a.d_poly,
+                     a.d_tab, a.d_steps, a.n_steps, a.k_first, a.d_tgrid, a.d_hl, a.out, in);
+}
+template <> void launch_fk_loaded_retract<TRK_INST_N>(const FkLaunch &a, const LoadedIn &in) {
+  if (a.rotation) { if (a.write_R) go<true, true>(a, in); else go<true, false>(a, in); }
+  else            { if (a.write_R) go<false, true>(a, in); else go<false, false>(a, in); }
+}
+template <> void launch_shoot_start_retract<TRK_INST_N>(const FkLaunch &a, const double *guess, double *vu) {
+  const unsigned grid = (unsigned)((a.n + 63) / 64);
+  hipLaunchKernelGGL((shoot_start_retract<TRK_INST_N>), dim3(grid), dim3(64), 0, a.stream, a.d_states, a.n, a.K, a.d_poly, guess, vu);
 }
 #elif TRK_INST_KIND == 4
 template <bool ROT, bool SPH, bool SIG>

@@ -415,10 +415,15 @@ __device__ __forceinline__ void frame_rate(int st, const double (&sR)[9], const 
 // produced on demand, tendon by tendon, by `route(t, j, r6)` at t, t + h/2 (stages 2 and 3) and t + h.
 // Used by the retraction kernel; the shared-grid kernel below carries the same statements inline
 // (as a function taking three table rows it made hipcc hoist all scalar loads and spill ~100 VGPRs).
-template <int N, class Route>
+// stage_load(sR) yields the distributed load of a stage from the STAGE's frame sR (a Load of strain_rates_routed); the default
+// yields NoLoad, and every unloaded instantiation compiles to the instructions it had before the hook existed.
+struct NoStageLoad {
+  __device__ __forceinline__ NoLoad operator()(const double (&)[9]) const { return NoLoad(); }
+};
+template <int N, class Route, class StageLoad = NoStageLoad>
 __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], double (&u)[3], double (&p)[3], double &Lb,
                                                 double (&Li)[N], const double (&tau)[N], const RobotK &K, double t, double h,
-                                                Route &&route) {
+                                                Route &&route, const StageLoad &stage_load = StageLoad()) {
 #pragma clang fp contract(fast)
   const double hh = h * 0.5;
   const double b1 = h * (1.0 / 6.0), b2 = h * (1.0 / 3.0);
@@ -440,7 +445,7 @@ __device__ __forceinline__ void rk4_step_routed(double (&R)[9], double (&v)[3], 
     const double bw = (st == 0 || st == 3) ? b1 : b2;
     const double aw = (st == 2) ? h : hh;
     double dv[3], du[3], sd[N];
-    strain_rates_routed<N>(sv, su, tau, [&](int j, double (&r6)[6]) { route(ts, j, r6); }, K, dv, du, sd);
+    strain_rates_routed<N>(sv, su, tau, [&](int j, double (&r6)[6]) { route(ts, j, r6); }, K, dv, du, sd, stage_load(sR));
     position_quadrature(st, sR, sv, b1, qs, qm, p);
     {
       const double v2 = __builtin_fma(sv[2], sv[2], __builtin_fma(sv[1], sv[1], sv[0] * sv[0]));

@@ -68,10 +68,17 @@ template <int N> void launch_fk_loaded(const FkLaunch &a, const LoadedIn &in);
 template <int N> void launch_fk_loaded_profile(const FkLaunch &a, const LoadedIn &in);
 // start strains of a.n problems: `guess` rows (v, u), or (guess null) the unloaded solution of the problem's tensions
 template <int N> void launch_shoot_start(const FkLaunch &a, const double *guess, double *vu);
+// the same two for retraction-enabled robots (fk_loaded_retract_kernel.hpp, kind 8): every lane on its own grid t_range(s_start, L, dL),
+// rows aligned at the tip, a.out.n_points per lane and, where a.out.home_Li is set, home_shape(s_start).L_i; the start is the
+// unloaded solution at the problem's own s_start.  in.weights is not read: there is no form under a load profile.
+template <int N> void launch_fk_loaded_retract(const FkLaunch &a, const LoadedIn &in);
+template <int N> void launch_shoot_start_retract(const FkLaunch &a, const double *guess, double *vu);
 
 #define TRK_DECL_FK(N) template <> void launch_fk_uniform<N>(const FkLaunch &); template <> void launch_fk_retract<N>(const FkLaunch &); \
   template <> void launch_fk_loaded<N>(const FkLaunch &, const LoadedIn &); template <> void launch_fk_loaded_profile<N>(const FkLaunch &, const LoadedIn &); \
   template <> void launch_shoot_start<N>(const FkLaunch &, const double *, double *); \
+  template <> void launch_fk_loaded_retract<N>(const FkLaunch &, const LoadedIn &); \
+  template <> void launch_shoot_start_retract<N>(const FkLaunch &, const double *, double *); \
   template <> void launch_fk_sweep_fused<N>(const FkLaunch &, const FusedSweepArgs *, size_t); \
   template <> void launch_fk_sweep_fused_list<N>(const FkLaunch &, const FusedSweepArgs *, size_t, const int32_t *, const uint32_t *); \
   template <> void launch_fk_verdict<N>(const FkLaunch &, const VerdictArgs *, size_t, bool, bool); \

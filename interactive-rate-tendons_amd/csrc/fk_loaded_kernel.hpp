@@ -16,7 +16,8 @@
 //   shoot_finish       strains, |e|, counters and the converged flag of every problem
 // The distributed load is a constant vector per problem in the robot's base frame (gravity), scaled by the context's load profile
 // w(s) where one is installed (fk_loaded_profile); the reference takes functions of (t, p).
-// Robots with retraction are refused by the host (loaded_host.inc).  The LM iteration is this library's own (the scheme of
+// Robots with retraction have an integrator of their own (fk_loaded_retract_kernel.hpp: per-lane first interval, point count and
+// tip-aligned rows) and share the per-problem kernels below, which never look at the grid.  The LM iteration is this library's own (the scheme of
 // ik_lm_step without bounds; the Cholesky solve and the mu / nu updates are lm_dense.hpp's, whose header lists what differs), not
 // levmar's code path; it is compiled without contraction.
 // The file has two halves: the per-problem kernels (included by tendon_hip.hip), and, under TRK_LOADED_WITH_INTEGRATOR, the kernels that
@@ -221,6 +222,14 @@ __global__ void shoot_finish(ShootParams prm, ShootState st, int64_t n, double *
   if (converged) converged[i] = err2 <= prm.eps3_sq ? 1 : 0;
 }
 
+// A robot with retraction: a problem whose s_start is negative lies outside the state space's bounds and integrates nothing (its
+// residual row is zero); it is reported unconverged, as the unloaded kernels report it (fk_retract_kernel.hpp).
+__global__ void shoot_negative_start(const double *__restrict__ states, int S, int64_t n, uint8_t *__restrict__ converged) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (states[i * S + S - 1] < 0.0) converged[i] = 0;
+}
+
 }  // namespace trk
 
 #else  // TRK_LOADED_WITH_INTEGRATOR
@@ -277,6 +286,46 @@ __device__ __forceinline__ void profile_row(const double *__restrict__ w, int en
   const double ws = w[entry];
 #pragma unroll
   for (int q = 0; q < 3; q++) { f[q] = ws * fe[q]; l[q] = ws * le[q]; }
+}
+
+// The tip residual e = (F_e_est - F_e, L_e_est - L_e) of one lane from its tip frame R (column-major) and tip strains v, u:
+// PointForces::calc_point_forces at the tip, every term in the base frame as the reference forms it: n = R K_se (v - e3),
+// m = R K_bt u, F_t = sum -tau_i unit(R pd_i), L_t = sum (R r_i) x F_t,i.  rb: [N][6] the routing at s = L; wrench: the lane's row
+// (F_e, L_e).  The tendon directions are normalised AFTER the rotation: the integrated frame is orthonormal to ~3e-9 only, and a unit
+// vector rotated by it is that far from unit length -- 2e-7 N at 56 N of tension, which the balance of a converged problem
+// (|e| <= 5e-6 N) would see.  Without contraction, whatever the caller compiles with.  The statements are those of the tip block of
+// fk_loaded_body.inc, which keeps them inline: as a call the shared-grid kernels' register allocation moved (fk_loaded_profile<8> spilled
+// 20 VGPRs where tests/test_load_profile_kernel_resources.py budgets 16); fk_loaded_retract (fk_loaded_retract_kernel.hpp) calls this.
+template <int N>
+__device__ __forceinline__ void tip_residual(const double (&R)[9], const double (&v)[3], const double (&u)[3], const double (&tau)[N],
+                                             const RobotK &K, const double *__restrict__ rb, const double *__restrict__ wrench,
+                                             double (&e)[6]) {
+#pragma clang fp contract(off)
+  auto rot = [&](double x, double y, double z, double (&o)[3]) {       // o = R (x, y, z)
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] = R[0 + r] * x + R[3 + r] * y + R[6 + r] * z;
+  };
+  double Ft[3] = {0, 0, 0}, Lt[3] = {0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const double rx = rb[6 * k + 0], ry = rb[6 * k + 1], rdx = rb[6 * k + 2], rdy = rb[6 * k + 3];
+    double pd[3], rw[3];
+    rot((-u[2] * ry) + rdx + v[0], (u[2] * rx) + rdy + v[1], (u[0] * ry - u[1] * rx) + v[2], pd);
+    rot(rx, ry, 0.0, rw);
+    const double z = pd[0] * pd[0] + pd[1] * pd[1] + pd[2] * pd[2];
+    if (z > 0.0) { const double s = sqrt(z); pd[0] = pd[0] / s; pd[1] = pd[1] / s; pd[2] = pd[2] / s; }
+    const double fx = -tau[k] * pd[0], fy = -tau[k] * pd[1], fz = -tau[k] * pd[2];
+    Ft[0] += fx; Ft[1] += fy; Ft[2] += fz;
+    Lt[0] += rw[1] * fz - rw[2] * fy; Lt[1] += rw[2] * fx - rw[0] * fz; Lt[2] += rw[0] * fy - rw[1] * fx;
+  }
+  double nw[3], mw[3];
+  rot(K.ks0 * v[0], K.ks0 * v[1], K.ks2 * (v[2] - 1.0), nw);
+  rot(K.kb0 * u[0], K.kb0 * u[1], K.kb2 * u[2], mw);
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    e[r] = (nw[r] - Ft[r]) - wrench[r];
+    e[3 + r] = (mw[r] - Lt[r]) - wrench[3 + r];
+  }
 }
 
 // K1's loop (fk_kernel.hpp: fk_uniform_body) from given base strains, with the distributed load in the right-hand side and the tip

@@ -90,6 +90,68 @@ __device__ __forceinline__ double home_ldot(const PolyK *__restrict__ pk, int j,
   return sqrt(dd * dd + (d * d) * (cd * cd) + 1);
 }
 
+// home_shape(s_start).L_i of one lane (TendonRobot.cpp:249-314), shared by the unloaded and the loaded retraction kernels: home_shape
+// clamps s_start into [0, L] (:257-258); composite Simpson over the lane's points with a trapezoid for a trailing odd interval (see
+// tendon_hip.hip: home_lengths).  s: s_start clamped from above, `single` and P_lane as the kernels form them, shift = P - P_lane; hl:
+// [P][N] the integrand at the shared abscissae.  The sums are formed in every call (wave-uniform control flow); `finish` false leaves
+// `home` unset.
+// Guarded per lane by tests/test_gpu_fk_truth.py: a 40-digit evaluation of the same rule over the lane's abscissae, within
+// (P_lane + 2) ulp -- a weight, a row of hl[] or the end the trapezoid sits at shows there, not in a comparison of flags.
+template <int N>
+__device__ __forceinline__ void home_lengths_lane(const PolyK *__restrict__ pk, const RobotK &K, const double *__restrict__ hl, double s_raw,
+                                                  double s, bool single, int P_lane, int shift, bool finish, double (&home)[N]) {
+#pragma clang fp contract(fast)
+  const int Pmax = K.n_points;
+  const double L = K.L, dL = K.dL;
+  bool any_general = false;
+#pragma unroll
+  for (int j = 0; j < N; j++) any_general = any_general || (pk->home_kind[j] == 2);
+  const int nint = P_lane - 1;
+  const int ne = (nint % 2 != 0) ? nint - 1 : nint;  // intervals covered by Simpson's rule
+  double hsum[N], hodd[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) { hsum[j] = 0; hodd[j] = 0; }
+  auto home_add = [&](int jpt, int j, double val) {
+    if (ne > 0 && jpt <= ne) hsum[j] += ((jpt == 0 || jpt == ne) ? 1.0 : ((jpt & 1) ? 4.0 : 2.0)) * val;
+    if (nint % 2 != 0 && jpt >= P_lane - 2) hodd[j] += val;
+  };
+  if (any_general && __any(!single)) {
+    // the integrand at the lane's points: its own base abscissa, then the shared grid (a pass of its own after
+    // the RK4 loop, so that the sums are not live -- 2 N more registers -- across it)
+    if (!single) {
+#pragma unroll
+      for (int j = 0; j < N; j++)
+        if (pk->home_kind[j] == 2) home_add(0, j, home_ldot(pk, j, K.n_a, K.n_m, L - (L - s)));
+    }
+    for (int ipt = 1; ipt < Pmax; ipt++) {
+      const bool on = !single && ipt < P_lane;
+      if (!__any(on)) break;
+      if (on) {
+#pragma unroll
+        for (int j = 0; j < N; j++)
+          if (pk->home_kind[j] == 2) home_add(ipt, j, hl[(int64_t)(ipt + shift) * N + j]);
+      }
+    }
+  }
+  if (!finish) return;
+  double sh = s_raw;
+  if (sh < 0.0) sh = 0.0;
+  if (sh > L) sh = L;
+  const double Lh = L - sh;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    double val;
+    if (sh == L) val = 0.0;
+    else if (pk->home_kind[j] == 0) val = Lh;
+    else if (pk->home_kind[j] == 1) val = Lh * pk->helix_scale[j];
+    else {
+      const double odd = (nint % 2 != 0) ? 0.5 * dL * hodd[j] : 0.0;
+      val = (P_lane < 2) ? 0.0 : ((ne == 0) ? odd : odd + (hsum[j] * dL / 3.0));
+    }
+    home[j] = val;
+  }
+}
+
 // Waves per SIMD (measured, profiles/r02/retract_widths_v1.txt: ms per 2^18 configurations, s_start ~ U[0, L), rotation and
 // general routing; one wave | two waves).  K1r with stored points: two waves pay up to 4 tendons (N=4 3.31 | 3.15, N=5
 // 3.68 | 3.77, N=6 4.16 | 4.31, N=8 5.93 | 6.37).  The verdict-only form (fk_verdict_retract: no stores, the sweep's loads
@@ -350,62 +412,9 @@ __device__ __forceinline__ void fk_retract_body(
     store_point(obs, act, false, true);
   }
 
-  // home-shape tendon lengths: home_shape clamps s_start into [0, L] (TendonRobot.cpp:257-258); composite
-  // Simpson over the lane's points with a trapezoid for a trailing odd interval (see tendon_hip.hip: home_lengths).
-  // Guarded per lane by tests/test_gpu_fk_truth.py: a 40-digit evaluation of the same rule over the lane's abscissae, within
-  // (P_lane + 2) ulp -- a weight, a row of hl[] or the end the trapezoid sits at shows there, not in a comparison of flags.
-  bool any_general = false;
-#pragma unroll
-  for (int j = 0; j < N; j++) any_general = any_general || (pk->home_kind[j] == 2);
-  const int nint = P_lane - 1;
-  const int ne = (nint % 2 != 0) ? nint - 1 : nint;  // intervals covered by Simpson's rule
-  double hsum[N], hodd[N];
-#pragma unroll
-  for (int j = 0; j < N; j++) { hsum[j] = 0; hodd[j] = 0; }
-  auto home_add = [&](int jpt, int j, double val) {
-    if (ne > 0 && jpt <= ne) hsum[j] += ((jpt == 0 || jpt == ne) ? 1.0 : ((jpt & 1) ? 4.0 : 2.0)) * val;
-    if (nint % 2 != 0 && jpt >= P_lane - 2) hodd[j] += val;
-  };
-  if (any_general && __any(!single)) {
-    // the integrand at the lane's points: its own base abscissa, then the shared grid (a pass of its own after
-    // the RK4 loop, so that the sums are not live -- 2 N more registers -- across it)
-    if (!single) {
-#pragma unroll
-      for (int j = 0; j < N; j++)
-        if (pk->home_kind[j] == 2) home_add(0, j, home_ldot(pk, j, K.n_a, K.n_m, L - (L - s)));
-    }
-    for (int ipt = 1; ipt < Pmax; ipt++) {
-      const bool on = !single && ipt < P_lane;
-      if (!__any(on)) break;
-      if (on) {
-#pragma unroll
-        for (int j = 0; j < N; j++)
-          if (pk->home_kind[j] == 2) home_add(ipt, j, hl[(int64_t)(ipt + shift) * N + j]);
-      }
-    }
-  }
-
-
   // home_shape(s_start).L_i (TendonRobot.cpp:249-314)
   double home[N];
-  if (out.home_Li || lane_out) {
-    double sh = s_raw;
-    if (sh < 0.0) sh = 0.0;
-    if (sh > L) sh = L;
-    const double Lh = L - sh;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-      double val;
-      if (sh == L) val = 0.0;
-      else if (pk->home_kind[j] == 0) val = Lh;
-      else if (pk->home_kind[j] == 1) val = Lh * pk->helix_scale[j];
-      else {
-        const double odd = (nint % 2 != 0) ? 0.5 * dL * hodd[j] : 0.0;
-        val = (P_lane < 2) ? 0.0 : ((ne == 0) ? odd : odd + (hsum[j] * dL / 3.0));
-      }
-      home[j] = val;
-    }
-  }
+  home_lengths_lane<N>(pk, K, hl, s_raw, s, single, P_lane, shift, out.home_Li || lane_out, home);
   if (live) {
     if (out.L) out.L[oc] = Lb;
     if (out.Li) {

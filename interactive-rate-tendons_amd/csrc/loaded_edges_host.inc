@@ -149,7 +149,7 @@ int loaded_edges_begin(tr_ctx *c, const tr_space_params *sp, const tr_shoot_para
   le.c = c;
   if ((rc = parse_loads(c, loads, le.loads))) return rc;
   le.warm = loads && loads->warm_start != 0;
-  if ((rc = shoot_check(c, n_edges, 0, 0))) return rc;
+  if ((rc = shoot_check(c, n_edges, 0, 0)) || (rc = refuse_retraction(c, "loaded edges (tr_validate_edges_loaded*, tr_*_edges_loaded_indexed)"))) return rc;
   if ((rc = shoot_params(c, shoot, le.prm))) return rc;
   if (n_edges == 0) { empty = true; return TR_OK; }
   if ((rc = edge_call_begin(c, sp))) return rc;

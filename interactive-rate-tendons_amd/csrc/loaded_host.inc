@@ -91,14 +91,25 @@ int shoot_params(tr_ctx *c, const tr_shoot_params *sp, trk::ShootParams &prm) {
   return TR_OK;
 }
 
-// what both forms refuse
-int shoot_check(tr_ctx *c, int64_t n, int64_t wrench_ld, int64_t dist_ld) {
+// What both forms refuse.  A robot with retraction is refused by EVERY loaded call, in these words, until the caller opens the context
+// to it (tr_set_loaded_retraction) -- contexts that never ask behave as they always did; retraction_ok: the call is one whose name
+// says retraction (tr_fk_loaded_batch_retraction_dev).
+int shoot_check(tr_ctx *c, int64_t n, int64_t wrench_ld, int64_t dist_ld, bool retraction_ok = false) {
   if (n < 0) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
   if (wrench_ld != 0 && wrench_ld < 6) return fail(c, TR_ERR_INVALID_ARG, "bad argument (wrench_ld: 0 or >= 6)");
   if (dist_ld != 0 && dist_ld < 6) return fail(c, TR_ERR_INVALID_ARG, "bad argument (dist_ld: 0 or >= 6)");
-  if (c->K.enable_retraction)
+  if (c->K.enable_retraction && !c->loaded_retraction && !retraction_ok)
     return fail(c, TR_ERR_UNSUPPORTED, "loaded FK (general_shape) is not built for robots with retraction");
   return TR_OK;
+}
+
+// On a context opened by tr_set_loaded_retraction the loaded FK, the loaded tips and the validity of loaded shapes take robots with
+// retraction (fk_loaded_retract_kernel.hpp); every loaded call above them still refuses such a robot here, under its own name `call`:
+// it needs more than the integrator (the loaded IK, for one, the tip's derivative along s_start through the shooting).
+int refuse_retraction(tr_ctx *c, const char *call) {
+  if (!c->K.enable_retraction) return TR_OK;
+  return fail(c, TR_ERR_UNSUPPORTED, std::string(call) + ": loaded FK (general_shape) is not built for robots with retraction in this call "
+                                     "(tr_fk_loaded_batch*, tr_fk_loaded_tips* and the validity of loaded shapes are)");
 }
 
 // The one load set of a call (the edge, roadmap, IK and Jacobian calls on loaded shapes) in the form its kernels take: Loads is
@@ -127,12 +138,14 @@ double profile_at(int64_t K, const double *s, const double *w, double x) {
   return w[k] + (w[k + 1] - w[k]) * ((x - s[k]) / (s[k + 1] - s[k]));
 }
 
-// `lanes` integrations: lane t is problem list[t / Q] (list null: t / Q) of d_states from strains vu[t]
+// `lanes` integrations: lane t is problem list[t / Q] (list null: t / Q) of d_states from strains vu[t].  A robot with retraction:
+// every lane on its own grid, rows aligned at the tip (fk_loaded_retract; no load profile can be installed on such a robot).
 int shoot_fk(tr_ctx *c, const double *d_states, int64_t lanes, int64_t ld, const trk::FkOut &out, trk::LoadedIn in, hipStream_t s) {
   in.tip_route = c->shoot.tip_route;
   in.weights = profile_weights(c);
   const trk::FkLaunch a = fk_launch_args(c, d_states, lanes, ld, out, out.R != nullptr, s);
-  TRK_FOR_TENDONS(c, trk::launch_fk_loaded<N>(a, in));
+  const bool ret = c->K.enable_retraction;
+  TRK_FOR_TENDONS(c, if (ret) trk::launch_fk_loaded_retract<N>(a, in); else trk::launch_fk_loaded<N>(a, in));
   HIP_TRY(c, hipGetLastError());
   return TR_OK;
 }
@@ -150,7 +163,8 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
   int rc;
   {
     const trk::FkLaunch a = fk_launch_args(c, d_states, m, ld, kFkOutNone, false, s);
-    TRK_FOR_TENDONS(c, trk::launch_shoot_start<N>(a, d_guess, k.pn));
+    const bool ret = c->K.enable_retraction;      // (the unloaded solution at the problem's own s_start)
+    TRK_FOR_TENDONS(c, if (ret) trk::launch_shoot_start_retract<N>(a, d_guess, k.pn); else trk::launch_shoot_start<N>(a, d_guess, k.pn));
     HIP_TRY(c, hipGetLastError());
   }
   // the start of every problem: one lane each
@@ -191,6 +205,10 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
   }
   hipLaunchKernelGGL(trk::shoot_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_vu0, d_res, d_iters, d_calls, d_conv);
   HIP_TRY(c, hipGetLastError());
+  if (c->K.enable_retraction && d_conv) {
+    hipLaunchKernelGGL(trk::shoot_negative_start, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_states, (int)c->K.state_size, m, d_conv);
+    HIP_TRY(c, hipGetLastError());
+  }
   return TR_OK;
 }
 
@@ -206,7 +224,7 @@ int shoot_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, in
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
     const trk::FkOut o{rows_at(out.px, off), rows_at(out.py, off), rows_at(out.pz, off), rows_at(out.R, off), rows_at(out.L, off),
-                       rows_at(out.Li, off), nullptr, nullptr, rows_at(out.n_points, off), nullptr};
+                       rows_at(out.Li, off), nullptr, nullptr, rows_at(out.n_points, off), rows_at(out.home_Li, off)};
     if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, m, ld, d_wrench ? d_wrench + off * wrench_ld : c->shoot.zero6,
                                 d_wrench ? wrench_ld : 0, rows_at(d_dist, off, dist_ld), dist_ld, rows_at(d_guess, off, 6), o,
                                 rows_at(d_conv, off), rows_at(d_vu0, off, 6), rows_at(d_vuL, off, 6), rows_at(d_res, off),
@@ -214,6 +232,12 @@ int shoot_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, in
   }
   return TR_OK;
 }
+
+int fk_loaded_dev_impl(tr_ctx *c, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
+                       const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess,
+                       double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L, double *d_Li, uint8_t *d_converged,
+                       int32_t *d_n_points, double *d_home_Li, double *d_vu0_out, double *d_vuL_out, double *d_residual_out,
+                       int32_t *d_iters_out, int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream);
 
 }  // namespace
 
@@ -227,7 +251,9 @@ int tr_set_load_profile(tr_ctx *c, int64_t n_knots, const double *s, const doubl
     if (!std::isfinite(s[k]) || !std::isfinite(w[k])) return fail(c, TR_ERR_INVALID_ARG, "bad argument (load profile: knots and weights must be finite)");
     if (k > 0 && !(s[k] > s[k - 1])) return fail(c, TR_ERR_INVALID_ARG, "bad argument (load profile: knots must be strictly increasing)");
   }
+  // the table is indexed like the shared routing table and has no entries for a lane's own first interval
   if (const int rc = shoot_check(c, 0, 0, 0)) return rc;
+  if (const int rc = refuse_retraction(c, "load profiles (tr_set_load_profile)")) return rc;
   const size_t n = 1 + 3 * c->steps.size();
   std::vector<double> table(n);
   table[0] = profile_at(n_knots, s, w, 0.0);
@@ -272,9 +298,40 @@ int tr_fk_loaded_batch_dev(tr_ctx *c, const tr_shoot_params *params, const doubl
                            int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream) {
   if (!c) return TR_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  return fk_loaded_dev_impl(c, params, d_states, n, ld, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, d_px, d_py, d_pz, d_R, d_L, d_Li,
+                            d_converged, d_n_points, nullptr, d_vu0_out, d_vuL_out, d_residual_out, d_iters_out, d_fk_calls_out, rounds_out,
+                            stream);
+}
+
+int tr_fk_loaded_batch_retraction_dev(tr_ctx *c, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
+                                      const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld,
+                                      const double *d_guess, double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L,
+                                      double *d_Li, uint8_t *d_converged, int32_t *d_n_points, double *d_home_Li, double *d_vu0_out,
+                                      double *d_vuL_out, double *d_residual_out, int32_t *d_iters_out, int32_t *d_fk_calls_out,
+                                      int64_t *rounds_out, void *stream) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  if (rounds_out) *rounds_out = 0;
+  if (!c->K.enable_retraction) return fail(c, TR_ERR_INVALID_ARG, "robot has no retraction: use tr_fk_loaded_batch_dev (home lengths: tr_home_lengths)");
+  if (n < 0) return fail(c, TR_ERR_INVALID_ARG, "bad argument");
+  if (n == 0) return TR_OK;
+  if (!d_n_points || !d_home_Li) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
+  return fk_loaded_dev_impl(c, params, d_states, n, ld, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, d_px, d_py, d_pz, d_R, d_L, d_Li,
+                            d_converged, d_n_points, d_home_Li, d_vu0_out, d_vuL_out, d_residual_out, d_iters_out, d_fk_calls_out,
+                            rounds_out, stream);
+}
+
+}  // extern "C"
+namespace {
+// the device forms' body (d_home_Li: tr_fk_loaded_batch_retraction_dev's, else null); the caller holds the lock
+int fk_loaded_dev_impl(tr_ctx *c, const tr_shoot_params *params, const double *d_states, int64_t n, int64_t ld,
+                       const double *d_wrench, int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess,
+                       double *d_px, double *d_py, double *d_pz, double *d_R, double *d_L, double *d_Li, uint8_t *d_converged,
+                       int32_t *d_n_points, double *d_home_Li, double *d_vu0_out, double *d_vuL_out, double *d_residual_out,
+                       int32_t *d_iters_out, int32_t *d_fk_calls_out, int64_t *rounds_out, void *stream) {
   if (rounds_out) *rounds_out = 0;
   int rc;
-  if ((rc = shoot_check(c, n, wrench_ld, dist_ld))) return rc;
+  if ((rc = shoot_check(c, n, wrench_ld, dist_ld, d_home_Li != nullptr))) return rc;
   if (ld < n || (ld & 63)) return fail(c, TR_ERR_INVALID_ARG, "ld must be a multiple of 64 and >= n");
   if (n == 0) return TR_OK;
   if (!d_states) return fail(c, TR_ERR_INVALID_ARG, "null device pointer");
@@ -285,13 +342,15 @@ int tr_fk_loaded_batch_dev(tr_ctx *c, const tr_shoot_params *params, const doubl
   trk::ShootParams prm;
   if ((rc = shoot_params(c, params, prm))) return rc;
   if ((rc = begin_dev_work(c, s))) return rc;
-  const trk::FkOut out{d_px, d_py, d_pz, d_R, d_L, d_Li, nullptr, nullptr, d_n_points, nullptr};
+  const trk::FkOut out{d_px, d_py, d_pz, d_R, d_L, d_Li, nullptr, nullptr, d_n_points, d_home_Li};
   int64_t rounds = 0;
   if ((rc = shoot_run(c, prm, d_states, n, ld, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, out, d_converged, d_vu0_out, d_vuL_out,
                       d_residual_out, d_iters_out, d_fk_calls_out, s, rounds))) return rc;
   if (rounds_out) *rounds_out = rounds;
   return note_dev_work(c, s);
 }
+}  // namespace
+extern "C" {
 
 int tr_fk_loaded_batch(tr_ctx *c, const tr_shoot_params *params, const double *states, int64_t n, const double *wrench,
                        int64_t wrench_ld, const double *dist, int64_t dist_ld, const double *guess, double *p, double *R, double *L,
@@ -313,6 +372,8 @@ int tr_fk_loaded_batch(tr_ctx *c, const tr_shoot_params *params, const double *s
   if ((rc = shoot_reserve_io(c, n, R != nullptr))) return rc;
   tr_ctx::ShootDev &k = c->shoot;
   std::vector<double> hx, hy, hz, hR, hLi;
+  std::vector<int32_t> hn;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
   int64_t rounds = 0;
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off), ld = round_up(m, 64);
@@ -325,24 +386,33 @@ int tr_fk_loaded_batch(tr_ctx *c, const tr_shoot_params *params, const double *s
     if ((rc = shoot_run(c, prm, k.io_states, m, ld, wrench ? k.io_w : nullptr, wrench_ld ? 6 : 0, dist ? k.io_d : nullptr, dist_ld ? 6 : 0,
                         guess ? k.io_g : nullptr, out, k.io_conv, k.io_vu, k.io_vuL, k.io_e, k.io_it, k.io_fc, nullptr, rounds))) return rc;
     HIP_TRY(c, hipDeviceSynchronize());
+    // point counts of THIS chunk (a robot with retraction: device rows are aligned at the tip, point j is in row j + (P - n_points);
+    // the host arrays start at row 0 and are NaN past n_points, as tr_fk_batch's)
+    hn.assign((size_t)m, P);
+    if ((p || R) && c->K.enable_retraction) HIP_TRY(c, hipMemcpy(hn.data(), k.io_np, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
     // device planes are [P][ld]; only the first m columns are copied (2-D copies, host pitch m)
     if (p) {
       hx.resize((size_t)P * m); hy.resize((size_t)P * m); hz.resize((size_t)P * m);
       HIP_TRY(c, hipMemcpy2D(hx.data(), (size_t)m * 8, k.io_px, (size_t)ld * 8, (size_t)m * 8, (size_t)P, hipMemcpyDeviceToHost));
       HIP_TRY(c, hipMemcpy2D(hy.data(), (size_t)m * 8, k.io_py, (size_t)ld * 8, (size_t)m * 8, (size_t)P, hipMemcpyDeviceToHost));
       HIP_TRY(c, hipMemcpy2D(hz.data(), (size_t)m * 8, k.io_pz, (size_t)ld * 8, (size_t)m * 8, (size_t)P, hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < m; i++)
+      for (int64_t i = 0; i < m; i++) {
+        const int np_i = hn[(size_t)i], sh = P - np_i;
         for (int j = 0; j < P; j++) {
           double *o = p + ((size_t)(off + i) * P + j) * 3;
-          o[0] = hx[(size_t)j * m + i]; o[1] = hy[(size_t)j * m + i]; o[2] = hz[(size_t)j * m + i];
+          if (j < np_i) { o[0] = hx[(size_t)(j + sh) * m + i]; o[1] = hy[(size_t)(j + sh) * m + i]; o[2] = hz[(size_t)(j + sh) * m + i]; }
+          else o[0] = o[1] = o[2] = nan;
         }
+      }
     }
     if (R) {
       hR.resize((size_t)9 * P * m);
       HIP_TRY(c, hipMemcpy2D(hR.data(), (size_t)m * 8, k.io_R, (size_t)ld * 8, (size_t)m * 8, (size_t)9 * P, hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < m; i++)
+      for (int64_t i = 0; i < m; i++) {
+        const int np_i = hn[(size_t)i], sh = P - np_i;
         for (int j = 0; j < P; j++)
-          for (int q = 0; q < 9; q++) R[((size_t)(off + i) * P + j) * 9 + q] = hR[((size_t)q * P + j) * m + i];
+          for (int q = 0; q < 9; q++) R[((size_t)(off + i) * P + j) * 9 + q] = j < np_i ? hR[((size_t)q * P + j + sh) * m + i] : nan;
+      }
     }
     if ((rc = download_rows(c, L, k.io_L, off, m))) return rc;
     if (L_i) {

@@ -51,9 +51,10 @@ struct IklCall {
   bool has_loads;
 };
 
-// what every call on loaded tips refuses first, and its load set
-int ikl_begin_loads(tr_ctx *c, const tr_edge_loads *loads, int64_t n, IklCall &call) {
-  if (const int rc = shoot_check(c, n, 0, 0)) return rc;
+// what every call on loaded tips refuses first (`what` names the call to a robot with retraction), and its load set
+int ikl_begin_loads(tr_ctx *c, const tr_edge_loads *loads, int64_t n, IklCall &call, const char *what) {
+  int rc;
+  if ((rc = shoot_check(c, n, 0, 0)) || (rc = refuse_retraction(c, what))) return rc;
   call.has_loads = loads != nullptr;
   return parse_loads(c, loads, call.loads);
 }
@@ -62,7 +63,7 @@ int ikl_begin_loads(tr_ctx *c, const tr_edge_loads *loads, int64_t n, IklCall &c
 int ikl_begin(tr_ctx *c, const tr_ik_params *params, const tr_shoot_params *shoot, const tr_edge_loads *loads, int64_t n, int64_t des_ld,
               const double *lo, const double *hi, IklCall &call) {
   int rc;
-  if ((rc = ikl_begin_loads(c, loads, n, call))) return rc;
+  if ((rc = ikl_begin_loads(c, loads, n, call, "loaded tip IK (tr_ik_loaded_batch*)"))) return rc;
   if (des_ld != 0 && des_ld < 3) return fail(c, TR_ERR_INVALID_ARG, "bad argument (des_ld: 0 or >= 3)");
   if ((rc = ik_params(c, params, lo, hi, call.prm))) return rc;
   for (int d = 0; d < call.prm.S; d++)

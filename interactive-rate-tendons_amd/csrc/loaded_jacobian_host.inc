@@ -28,7 +28,7 @@ int sens_reserve_io(tr_ctx *c) {
 // iteration, at the caller's difference step and tr_fk_loaded_batch's shooting defaults
 int sens_params(tr_ctx *c, const tr_shoot_params *shoot, const tr_edge_loads *loads, int64_t n, double delta, IklCall &call) {
   int rc;
-  if ((rc = ikl_begin_loads(c, loads, n, call))) return rc;
+  if ((rc = ikl_begin_loads(c, loads, n, call, "loaded tip Jacobian and compliance (tr_tip_jacobian_loaded*)"))) return rc;
   if (!(delta > 0.0)) return fail(c, TR_ERR_INVALID_ARG, "bad argument (delta must be > 0)");
   if ((rc = ik_params(c, nullptr, nullptr, nullptr, call.prm))) return rc;
   call.prm.delta = delta;

@@ -21,7 +21,7 @@ int loaded_states_begin(tr_ctx *c, const tr_shoot_params *shoot, const tr_edge_l
   le.c = c;
   if ((rc = parse_loads(c, loads, le.loads))) return rc;
   le.warm = false;                             // every vertex is solved cold
-  if ((rc = shoot_check(c, n, 0, 0))) return rc;
+  if ((rc = shoot_check(c, n, 0, 0)) || (rc = refuse_retraction(c, "loaded roadmap builds (tr_sample_valid_vertices_loaded*, tr_voxelize_batch_loaded)"))) return rc;
   if ((rc = shoot_params(c, shoot, le.prm))) return rc;
   if (n == 0) { empty = true; return TR_OK; }
   if (!c->has_grid) return fail(c, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");

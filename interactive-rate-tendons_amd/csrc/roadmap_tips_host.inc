@@ -445,6 +445,11 @@ int tip_loaded_begin(tr_roadmap *r, const tr_shoot_params *shoot, const tr_edge_
   L.k.world = L.loads.frame == TR_LOAD_FRAME_WORLD;
   if (const int rc = tr_fk_loaded_tips_dev(r->ctx, shoot, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
     return rfail(r, rc, tr_last_error(r->ctx));
+  // tr_fk_loaded_tips* takes a robot with retraction; the queries do not: their IK needs the tip's derivative along s_start
+  if (r->ret)
+    return rfail(r, TR_ERR_UNSUPPORTED, "loaded tip queries (tr_roadmap_ik_batch_loaded, tr_roadmap_solve_tips_loaded, tr_roadmap_set_tips_loaded): "
+                                        "loaded FK (general_shape) is not built for robots with retraction in this call "
+                                        "(tr_fk_loaded_batch*, tr_fk_loaded_tips* and the validity of loaded shapes are)");
   if (n == 0) { empty = true; return TR_OK; }
   if (r->dt.set && r->dt.own_tips)
     return rfail(r, TR_ERR_INVALID_ARG, "the roadmap's tips are those of UNLOADED shapes (tr_roadmap_set_tips computed them with tr_fk_tips_dev): "

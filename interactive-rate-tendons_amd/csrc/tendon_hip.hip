@@ -353,6 +353,7 @@ struct tr_ctx {
     double *d_table = nullptr;
   } profile;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
+  bool loaded_retraction = false;    // tr_set_loaded_retraction: the loaded FK, tips and validity take this (retraction) robot
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
   bool profiling = false;
@@ -1263,6 +1264,12 @@ void tr_destroy(tr_ctx *c) {
 }
 
 int tr_state_size(const tr_ctx *c) { return c ? c->K.state_size : -1; }
+int tr_set_loaded_retraction(tr_ctx *c, int on) {
+  if (!c) return TR_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lock_(c->mu);
+  c->loaded_retraction = on != 0;
+  return TR_OK;
+}
 int tr_num_points(const tr_ctx *c) { return c ? c->K.n_points : -1; }
 int tr_device(const tr_ctx *c) { return c ? c->device : -1; }
 

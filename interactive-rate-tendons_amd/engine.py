@@ -135,6 +135,7 @@ class Engine:
         self.n_tendons = n
         self.state_size = lib.tr_state_size(ctx)
         self.num_points = lib.tr_num_points(ctx)
+        self.enable_retraction = bool(robot.enable_retraction)
         self.has_grid = False
         self._load_profile = None
 
@@ -342,6 +343,14 @@ class Engine:
             return a, 6
         raise L.InvalidArgument("%s must be (6,) or (n, 6)" % name)
 
+    def set_loaded_retraction(self, on=True):
+        """tr_set_loaded_retraction: open (or close) this engine to LOADED shapes of its robot with retraction.  Never opened, every
+        loaded call refuses such a robot as it always did; opened, fk_loaded_batch*, fk_loaded_tips* and with them
+        robot.general_shape take it, and the loaded calls above them (edges, roadmap builds, IK, Jacobian, tip queries, load
+        profiles) still raise Unsupported, each under its own name.  validate_loaded and fk_loaded_batch_retraction_dev need no
+        opening."""
+        L.check(self._ctx, self.lib.tr_set_loaded_retraction(self._ctx, int(bool(on))))
+
     # ---- the load profile of every loaded call (tr_set_load_profile): a weight w(s) on the distributed load ------------------------
     def set_load_profile(self, knots, weights):
         """Install the piecewise-linear weight w(s) over (knots, weights): from now on every loaded call of this engine integrates
@@ -390,7 +399,9 @@ class Engine:
                         stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6):
         """Batched general_shape on the device: wrench = (F_e, L_e) and dist = (f_e, l_e) are (6,) for all states or (n, 6), in the
         robot's base frame before the state's rotation (None: zero); guess (n, 6) rows (v, u) or None = the unloaded solution.
-        Returns dict(p, R, L, L_i, converged, n_points, vu0, vuL (tip strains), residual, iters, num_fk_calls, rounds)."""
+        Returns dict(p, R, L, L_i, converged, n_points, vu0, vuL (tip strains), residual, iters, num_fk_calls, rounds).
+        A robot with retraction (after set_loaded_retraction()): state i has n_points[i] points from row 0 of p and R, NaN in the rows after them (fk_batch's
+        layout); s_start >= L gives one point at the origin."""
         st = self._states(states)
         n, P, N = st.shape[0], self.num_points, self.n_tendons
         w, wld = self._load_rows(wrench, n, "wrench")
@@ -422,22 +433,42 @@ class Engine:
                             d_fk_calls=None, max_iters=100, mu_init=0.1, stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4,
                             finite_difference_delta=1e-6, stream=None):
         """tr_fk_loaded_batch_dev: device tensors in tr_fk_batch_dev's layout (wrench_ld / dist_ld = 0: one row for all); d_px, d_py,
-        d_pz, d_Li, d_conv feed validate_shapes_dev.  Returns the number of rounds."""
+        d_pz, d_Li, d_conv feed validate_shapes_dev.  A robot with retraction: rows are aligned at the tip (state i's point j in row
+        j + P - d_npts[i]).  Returns the number of rounds."""
+        return self._fk_loaded_dev(self.lib.tr_fk_loaded_batch_dev, False, d_states, n, ld, d_px, d_py, d_pz, d_wrench, wrench_ld, d_dist,
+                                   dist_ld, d_guess, d_L, d_Li, d_conv, d_R, d_npts, None, d_vu0, d_vuL, d_residual, d_iters, d_fk_calls,
+                                   (max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta), stream)
+
+    def fk_loaded_batch_retraction_dev(self, d_states, n, ld, d_px, d_py, d_pz, d_Li, d_conv, d_npts, d_home_Li, d_wrench=None,
+                                       wrench_ld=6, d_dist=None, dist_ld=6, d_guess=None, d_L=None, d_R=None, d_vu0=None, d_vuL=None,
+                                       d_residual=None, d_iters=None, d_fk_calls=None, max_iters=100, mu_init=0.1,
+                                       stop_threshold_JT_err_inf=1e-9, stop_threshold_Dp=1e-4, finite_difference_delta=1e-6, stream=None):
+        """tr_fk_loaded_batch_retraction_dev: fk_loaded_batch_dev for a robot with retraction, with the per-configuration point counts
+        d_npts (int32, n) and home lengths d_home_Li ([N][ld]) that validate_shapes_retraction_dev takes.  Returns the number of
+        rounds."""
+        return self._fk_loaded_dev(self.lib.tr_fk_loaded_batch_retraction_dev, True, d_states, n, ld, d_px, d_py, d_pz, d_wrench, wrench_ld,
+                                   d_dist, dist_ld, d_guess, d_L, d_Li, d_conv, d_R, d_npts, d_home_Li, d_vu0, d_vuL, d_residual, d_iters,
+                                   d_fk_calls, (max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta),
+                                   stream)
+
+    def _fk_loaded_dev(self, call, with_home, d_states, n, ld, d_px, d_py, d_pz, d_wrench, wrench_ld, d_dist, dist_ld, d_guess, d_L, d_Li,
+                       d_conv, d_R, d_npts, d_home_Li, d_vu0, d_vuL, d_residual, d_iters, d_fk_calls, shoot, stream):
         torch = _torch()
         P = self.num_points
         f64 = torch.float64
         opt = lambda t, dt, m, nm: self._check_dev(t, dt, m, nm) if t is not None else None
         rows = lambda rl: 6 if rl == 0 else (n - 1) * rl + 6
-        prm = self._shoot_params(max_iters, mu_init, stop_threshold_JT_err_inf, stop_threshold_Dp, finite_difference_delta)
+        prm = self._shoot_params(*shoot)
         rounds = C.c_int64(0)
-        L.check(self._ctx, self.lib.tr_fk_loaded_batch_dev(
+        home = (opt(d_home_Li, f64, self.n_tendons * ld, "d_home_Li"),) if with_home else ()
+        L.check(self._ctx, call(
             self._ctx, C.byref(prm), self._check_dev(d_states, f64, n * self.state_size, "d_states"), int(n), int(ld),
             opt(d_wrench, f64, rows(wrench_ld), "d_wrench"), int(wrench_ld), opt(d_dist, f64, rows(dist_ld), "d_dist"), int(dist_ld),
             opt(d_guess, f64, 6 * n, "d_guess"), opt(d_px, f64, P * ld, "d_px"), opt(d_py, f64, P * ld, "d_py"),
             opt(d_pz, f64, P * ld, "d_pz"), opt(d_R, f64, 9 * P * ld, "d_R"), opt(d_L, f64, n, "d_L"),
             opt(d_Li, f64, self.n_tendons * ld, "d_Li"), opt(d_conv, torch.uint8, n, "d_conv"), opt(d_npts, torch.int32, n, "d_npts"),
-            opt(d_vu0, f64, 6 * n, "d_vu0"), opt(d_vuL, f64, 6 * n, "d_vuL"), opt(d_residual, f64, n, "d_residual"), opt(d_iters, torch.int32, n, "d_iters"),
-            opt(d_fk_calls, torch.int32, n, "d_fk_calls"), C.byref(rounds), self._stream_ptr(stream)))
+            *home, opt(d_vu0, f64, 6 * n, "d_vu0"), opt(d_vuL, f64, 6 * n, "d_vuL"), opt(d_residual, f64, n, "d_residual"),
+            opt(d_iters, torch.int32, n, "d_iters"), opt(d_fk_calls, torch.int32, n, "d_fk_calls"), C.byref(rounds), self._stream_ptr(stream)))
         return int(rounds.value)
 
     def fk_loaded_tips(self, states, wrench=None, dist=None, frame="base", guess=None, **shoot):
@@ -484,7 +515,9 @@ class Engine:
 
     def validate_loaded(self, states, wrench=None, dist=None, guess=None, check_voxels=True, **shoot):
         """isValid of the LOADED shapes: fk_loaded_batch_dev into validate_shapes_dev (converged = the shooting's, tendon-length
-        limits, self-collision, the backbone or sphere sweep against the grid).  Returns dict(valid, bits, flags)."""
+        limits, self-collision, the backbone or sphere sweep against the grid); a robot with retraction:
+        fk_loaded_batch_retraction_dev into validate_shapes_retraction_dev (the length limits against home_shape(s_start).L_i).
+        Returns dict(valid, bits, flags)."""
         torch = _torch()
         st = self._states(states)
         n, P, N = st.shape[0], self.num_points, self.n_tendons
@@ -499,9 +532,17 @@ class Engine:
         bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device=dev)
         flags = torch.zeros(n, dtype=torch.uint8, device=dev)
         g = None if guess is None else _f64(guess).reshape(n, 6)
-        self.fk_loaded_batch_dev(up(st), n, ld, planes[0], planes[1], planes[2], d_wrench=up(w), wrench_ld=wld, d_dist=up(d), dist_ld=dld,
-                                 d_guess=up(g), d_Li=Li, d_conv=conv, **shoot)
-        self.validate_shapes_dev(n, ld, planes[0], planes[1], planes[2], Li, conv, bits, flags, check_voxels=check_voxels)
+        if self.enable_retraction:
+            npts = torch.empty(n, dtype=torch.int32, device=dev)
+            home = torch.empty((N, ld), dtype=torch.float64, device=dev)
+            self.fk_loaded_batch_retraction_dev(up(st), n, ld, planes[0], planes[1], planes[2], Li, conv, npts, home, d_wrench=up(w),
+                                                wrench_ld=wld, d_dist=up(d), dist_ld=dld, d_guess=up(g), **shoot)
+            self.validate_shapes_retraction_dev(n, ld, planes[0], planes[1], planes[2], npts, Li, home, conv, bits, flags,
+                                                check_voxels=check_voxels)
+        else:
+            self.fk_loaded_batch_dev(up(st), n, ld, planes[0], planes[1], planes[2], d_wrench=up(w), wrench_ld=wld, d_dist=up(d),
+                                     dist_ld=dld, d_guess=up(g), d_Li=Li, d_conv=conv, **shoot)
+            self.validate_shapes_dev(n, ld, planes[0], planes[1], planes[2], Li, conv, bits, flags, check_voxels=check_voxels)
         torch.cuda.synchronize(self.device)
         words = bits.cpu().numpy().view(np.uint64)
         return dict(valid=unpack_bits(words, n), bits=words, flags=flags.cpu().numpy())

@@ -167,6 +167,11 @@ class VoxelBackboneValidityChecker:
         weight w(s) along the backbone on `dist` (Engine.set_load_profile), installed on the checker's engine until clear_loads() or
         the next set_loads; load_profile() reports it."""
         self.engine._edge_loads(wrench, dist, frame, warm_start)              # argument checks
+        if self._robot.enable_retraction:
+            # Engine.validate_loaded judges the loaded STATES of such a robot; the motion validators behind this checker cannot judge
+            # its edges yet, and a checker that is loaded for one of the two would plan on mixed shapes
+            raise L.Unsupported("checker.set_loads: loaded FK (general_shape) is not built for robots with retraction in this call "
+                                "(Engine.fk_loaded_batch, fk_loaded_tips and validate_loaded are)")
         if profile is not None:
             self.engine.set_load_profile(*profile)
         elif self._profile is not None:

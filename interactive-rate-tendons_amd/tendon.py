@@ -175,7 +175,9 @@ class TendonRobot:
                                        finite_difference_delta=finite_difference_delta, device=device, load_profile=load_profile)
         n = int(out["n_points"][0])
         R = out["R"][0, :n].reshape(n, 3, 3).transpose(0, 2, 1)
-        return TendonResult(t=self._t(0.0)[:n], p=out["p"][0, :n], R=R, L=float(out["L"][0]), L_i=out["L_i"][0],
+        s_start = float(state[-1]) if self.enable_retraction else 0.0        # (general_shape reads it from the state, TendonRobot.h:177-208)
+        t = self._t(s_start) if n > 1 else np.array([min(s_start, self.specs.L)])
+        return TendonResult(t=t[:n], p=out["p"][0, :n], R=R, L=float(out["L"][0]), L_i=out["L_i"][0],
                             converged=bool(out["converged"][0]), v_i=out["vu0"][0, :3].copy(), u_i=out["vu0"][0, 3:].copy(),
                             v_f=out["vuL"][0, :3].copy(), u_f=out["vuL"][0, 3:].copy())
 
