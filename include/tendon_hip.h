@@ -92,8 +92,22 @@ int tr_device(const tr_ctx *ctx);
  * every loaded call with one message, TR_ERR_UNSUPPORTED, as it always did.  Opened: tr_fk_loaded_batch*, tr_fk_loaded_tips* (and with
  * them general_shape and the validity of loaded shapes) take the robot, see tr_fk_loaded_batch; the loaded calls built on them --
  * edges, roadmap builds, IK, Jacobian and compliance, tip queries, load profiles -- keep answering TR_ERR_UNSUPPORTED, now each under
- * its own name.  No effect on a robot without retraction. */
+ * its own name.  No effect on a robot without retraction.
+ * on == TR_LOADED_RETRACTION_EDGES (2) opens what 1 opens plus the loaded edge checks (tr_validate_edges_loaded with and without
+ * last_valid_t, tr_validate_edges_loaded_indexed and its pairwise fall-back, tr_edges_loaded_vertex_strains, tr_edges_loaded_last; see
+ * tr_validate_edges_loaded for what a sample of such a robot is).  The voxel forms of the loaded edges, the loaded roadmap builds, IK,
+ * Jacobian and compliance, tip queries and load profiles refuse at this level too.  Any other non-zero value means 1.
+ * tr_loaded_retraction returns the level (-1: ctx == NULL). */
+enum { TR_LOADED_RETRACTION_OFF = 0, TR_LOADED_RETRACTION_FK = 1, TR_LOADED_RETRACTION_EDGES = 2 };
 int tr_set_loaded_retraction(tr_ctx *ctx, int on);
+int tr_loaded_retraction(const tr_ctx *ctx);
+/* A robot with retraction: a wave of the loaded FK runs from its longest backbone's base to the tip while its shorter lanes idle, so a
+ * call of at least TENDON_HIP_LOADED_RETRACT_SORT problems (read at tr_create; 0: never) is solved in the order of its problems'
+ * s_start -- inside the call: every input row is read and every output row written at the caller's index, and the results are the
+ * bits of the arrival-order solve.  This holds for every caller of the shooting: tr_fk_loaded_batch*, tr_fk_loaded_tips* (per chunk),
+ * the validity of loaded shapes, every level of the loaded edge calls and the indexed form's vertex block.
+ * stats = problems of the context's last shooting run (one such call, chunk or level), how many of them were solved in order. */
+int tr_loaded_order_last(const tr_ctx *ctx, int64_t stats[2]);
 
 /* Home shape tendon lengths at s_start = 0 (TendonRobot::home_shape, tendon/TendonRobot.cpp:249-314) */
 int tr_home_lengths(const tr_ctx *ctx, double *L_i /*[n_tendons]*/);
@@ -470,9 +484,20 @@ typedef struct tr_edge_loads {
  *   n_unconverged   (optional) samples whose shooting did not converge
  *   n_integrations  (optional) the sum of the samples' fk_calls (tr_fk_loaded_batch's fk_calls_out)
  * The rotation of WORLD loads uses a fixed sequence of IEEE operations for sine and cosine (csrc/loaded_edge_kernel.hpp), so a
- * host restatement reproduces the per-sample rows bit for bit.  Robots with retraction: TR_ERR_UNSUPPORTED; no grid or a
+ * host restatement reproduces the per-sample rows bit for bit.  No grid or a
  * non-positive resolution: TR_ERR_INVALID_ARG; n_edges == 0: TR_OK.  The verdicts do not depend on the chunking
- * (TENDON_HIP_SHOOT_CHUNK, TENDON_HIP_EDGE_POOL), the order of the edges or the other edges of the call. */
+ * (TENDON_HIP_SHOOT_CHUNK, TENDON_HIP_EDGE_POOL), the order of the edges or the other edges of the call.
+ * Robots with retraction: TR_ERR_UNSUPPORTED unless the context is at TR_LOADED_RETRACTION_EDGES (tr_set_loaded_retraction).  Then
+ *   - a sample's state is the unloaded edge check's interpolation, s_start linear;
+ *   - its shape is tr_fk_loaded_batch's for that state: its own grid t_range(s_start, L, dL), rows aligned at the tip, the sample's
+ *     own loads under frame WORLD;
+ *   - it is valid if it converged, its lengths are within the limits against home_shape(s_start).L_i, it has no self collision and
+ *     it passes the sample test the run chose (the sphere checker under last_valid_t included);
+ *   - s_start >= L: one point at the origin, converged, judged as the unloaded stored-point check of such a robot judges that shape;
+ *     s_start < 0: unconverged, so invalid;
+ *   - the interval test compares stored points with the samples' own point counts, as the unloaded voxelize forms of such a robot do;
+ *   - warm_start is allowed: the guess is the accepted base strains of the interval's sample at t_a, unchanged -- strains at another
+ *     arc length, a heuristic about which nothing is promised. */
 int tr_validate_edges_loaded(tr_ctx *ctx, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads,
                              const double *a, const double *b, int64_t n_edges, uint64_t *valid_bits, double *last_valid_t,
                              int32_t *n_fk, int64_t *n_domain_errors, int64_t *n_unconverged, int64_t *n_integrations);
@@ -1133,6 +1158,8 @@ int tr_edge_schedule_last(const tr_ctx *ctx, uint32_t stats[4]);
  *                                   tr_voxelize_batch_loaded (tests: several batches; default: 2^16, what the workspace is grown to)
  *   TENDON_HIP_RETRACT_SORT=n       retraction robots: batches of at least n configurations are ordered by backbone length
  *                                   (0 = never); TENDON_HIP_RETRACT_KBEGIN_OFF: no per-wave loop start in that order
+ *   TENDON_HIP_LOADED_RETRACT_SORT=n  retraction robots: a shooting run (tr_loaded_order_last) of at least n problems is solved in
+ *                                   backbone-length order (0 = never); the results are the bits of the arrival-order solve
  *   TENDON_HIP_ROUTING=table        the general (table) form of the strain right-hand side for every robot.  Unset: a robot without
  *                                   retraction whose tendons all have constant radius and at most linear angle, with ONE pitch and
  *                                   ONE radius (compared bit for bit; straight tendons: pitch 0), of at most six tendons, gets the

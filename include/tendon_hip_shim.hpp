@@ -272,7 +272,13 @@ class TendonRobot {                 // tendon/TendonRobot.h:52-355
 
   /// tr_set_loaded_retraction: opens (or closes) this robot's context to LOADED shapes of a robot with retraction -- general_shape,
   /// generalShapeBatch and loaded_tips_batch then take it; the loaded calls above them keep throwing std::runtime_error.
-  void set_loaded_retraction(bool on = true) const { tr_ctx *c = context(); check(c, tr_set_loaded_retraction(c, on ? 1 : 0)); }
+  /// edges: the loaded edge checks as well (TR_LOADED_RETRACTION_EDGES) -- checkMotion of the motion validators on a checker of this
+  /// robot after setLoads.  loaded_retraction() returns the level (0, 1 or 2).
+  void set_loaded_retraction(bool on = true, bool edges = false) const {
+    tr_ctx *c = context();
+    check(c, tr_set_loaded_retraction(c, on ? (edges ? TR_LOADED_RETRACTION_EDGES : TR_LOADED_RETRACTION_FK) : TR_LOADED_RETRACTION_OFF));
+  }
+  int loaded_retraction() const { return tr_loaded_retraction(context()); }
 
   /// A load profile (tr_set_load_profile): the piecewise-linear weight w(arc length) over the knots (s[k], w[k]) that every loaded
   /// call of this robot's context applies to its distributed load from now on: general_shape, generalShapeBatch, the loaded tip
@@ -686,8 +692,11 @@ class VoxelBackboneValidityChecker {
   // loaded FK (tr_validate_edges_loaded*); clearLoads() restores the unloaded checks. ----
   /// wrench = (F_e, L_e), dist = (f_e, l_e) per unit length, 6 values each (empty: zero); world: the loads are fixed behind the
   /// state's rotation (every sample's rows are turned by Rz(-theta)), else before it (tr_fk_loaded_batch's frame)
+  /// A robot with retraction: std::runtime_error unless its context is open to the loaded edge checks
+  /// (robot.set_loaded_retraction(true, true)) -- the motion validators behind a loaded checker must be able to judge its edges.
   void setLoads(const std::vector<double> &wrench, const std::vector<double> &dist, bool world = false, bool warm_start = false) {
     check_load_sizes(wrench, dist);
+    check_retraction_open();
     if (has_profile_) check(ctx_, tr_clear_load_profile(ctx_));     // (a profile belongs to the setLoads that gave it)
     has_profile_ = false;
     store_loads(wrench, dist, world, warm_start);
@@ -700,6 +709,7 @@ class VoxelBackboneValidityChecker {
                 const std::vector<double> &profile_w, bool world = false, bool warm_start = false) {
     if (profile_s.size() != profile_w.size()) throw std::invalid_argument("load profile: one weight per knot");
     check_load_sizes(wrench, dist);
+    check_retraction_open();
     check(ctx_, tr_set_load_profile(ctx_, (int64_t)profile_s.size(), profile_s.data(), profile_w.data()));
     has_profile_ = true;
     store_loads(wrench, dist, world, warm_start);
@@ -746,6 +756,11 @@ class VoxelBackboneValidityChecker {
   static void check_load_sizes(const std::vector<double> &wrench, const std::vector<double> &dist) {
     if ((!wrench.empty() && wrench.size() != 6) || (!dist.empty() && dist.size() != 6))
       throw std::invalid_argument("wrench and dist hold 6 values each: one load set");
+  }
+  void check_retraction_open() const {
+    if (robot_.enable_retraction && tr_loaded_retraction(ctx_) < TR_LOADED_RETRACTION_EDGES)
+      throw std::runtime_error("checker.setLoads: loaded FK (general_shape) is not built for robots with retraction in this call "
+                               "(TendonRobot::set_loaded_retraction(true, true) opens the loaded edge checks)");
   }
   void store_loads(const std::vector<double> &wrench, const std::vector<double> &dist, bool world, bool warm_start) {
     loads_ = tr_edge_loads{};

@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "tr_roadmap_tip_query_profile",
     "tr_roadmap_nearest_states", "tr_roadmap_nearest_states_dev", "tr_roadmap_ik_batch_connect", "tr_roadmap_solve_tips_connect",
     "tr_roadmap_tip_connect_stats",
-    "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev", "tr_fk_loaded_batch_retraction_dev", "tr_set_loaded_retraction",
+    "tr_fk_loaded_batch", "tr_fk_loaded_batch_dev", "tr_fk_loaded_batch_retraction_dev", "tr_set_loaded_retraction", "tr_loaded_retraction", "tr_loaded_order_last",
     "tr_validate_edges_loaded", "tr_validate_edges_loaded_indexed", "tr_edges_loaded_vertex_strains", "tr_edges_loaded_last",
     "tr_sample_valid_vertices_loaded", "tr_sample_valid_vertices_loaded_dev", "tr_voxelize_batch_loaded",
     "tr_voxelize_edges_loaded_indexed", "tr_connect_edges_loaded_indexed",
@@ -382,6 +382,9 @@ def lib():
     L.tr_fk_loaded_batch.argtypes = [vp, shp, dp, i64, dp, i64, dp, i64, dp, dp, dp, dp, dp, P(C.c_uint8), i32p, dp, dp, dp, i32p, i32p, P(i64)]
     L.tr_fk_loaded_batch_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     L.tr_set_loaded_retraction.argtypes = [vp, C.c_int]
+    L.tr_loaded_retraction.argtypes = [vp]
+    L.tr_loaded_retraction.restype = C.c_int
+    L.tr_loaded_order_last.argtypes = [vp, P(i64)]
     L.tr_fk_loaded_batch_retraction_dev.argtypes = [vp, shp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, P(i64), vp]
     elp = P(TrEdgeLoads)
     L.tr_validate_edges_loaded.argtypes = [vp, P(TrSpaceParams), shp, elp, dp, dp, i64, P(C.c_uint64), dp, i32p, P(i64), P(i64), P(i64)]

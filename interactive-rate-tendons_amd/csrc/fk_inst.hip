@@ -92,9 +92,9 @@ template <> void launch_fk_loaded_retract<TRK_INST_N>(const FkLaunch &a, const L
   if (a.rotation) { if (a.write_R) go<true, true>(a, in); else go<true, false>(a, in); }
   else            { if (a.write_R) go<false, true>(a, in); else go<false, false>(a, in); }
 }
-template <> void launch_shoot_start_retract<TRK_INST_N>(const FkLaunch &a, const double *guess, double *vu) {
+template <> void launch_shoot_start_retract<TRK_INST_N>(const FkLaunch &a, const double *guess, double *vu, const int32_t *perm) {
   const unsigned grid = (unsigned)((a.n + 63) / 64);
-  hipLaunchKernelGGL((shoot_start_retract<TRK_INST_N>), dim3(grid), dim3(64), 0, a.stream, a.d_states, a.n, a.K, a.d_poly, guess, vu);
+  hipLaunchKernelGGL((shoot_start_retract<TRK_INST_N>), dim3(grid), dim3(64), 0, a.stream, a.d_states, a.n, a.K, a.d_poly, guess, vu, perm);
 }
 #elif TRK_INST_KIND == 4
 template <bool ROT, bool SPH, bool SIG>

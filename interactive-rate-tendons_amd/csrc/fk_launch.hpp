@@ -34,6 +34,10 @@ struct LoadedIn {
   double *res; int64_t ldr;                    // [6][ldr] tip residual of every lane (structure of arrays), or null
   double *vu_tip;                              // [lanes][6] strains (v, u) at the tip, or null
   const double *weights = nullptr;             // the load profile's table, [1 + 3 n_steps] weights indexed like the routing table; null: none
+  // fk_loaded_retract only (the shared-grid kernels never read it): problem q of the launch (q = list[t / Q], or t / Q) is column
+  // perm[q] of the caller's arrays -- its state, wrench and dist rows, and, in a one-lane-per-problem launch, every output column and
+  // its vu_tip row; vu, res and list stay indexed by the launch.  Null: arrival order, q itself.
+  const int32_t *perm = nullptr;
 };
 
 struct FusedSweepArgs;
@@ -72,13 +76,14 @@ template <int N> void launch_shoot_start(const FkLaunch &a, const double *guess,
 // rows aligned at the tip, a.out.n_points per lane and, where a.out.home_Li is set, home_shape(s_start).L_i; the start is the
 // unloaded solution at the problem's own s_start.  in.weights is not read: there is no form under a load profile.
 template <int N> void launch_fk_loaded_retract(const FkLaunch &a, const LoadedIn &in);
-template <int N> void launch_shoot_start_retract(const FkLaunch &a, const double *guess, double *vu);
+// perm: problem i's state and guess row are the caller's row perm[i] (null: i); vu stays indexed by i
+template <int N> void launch_shoot_start_retract(const FkLaunch &a, const double *guess, double *vu, const int32_t *perm = nullptr);
 
 #define TRK_DECL_FK(N) template <> void launch_fk_uniform<N>(const FkLaunch &); template <> void launch_fk_retract<N>(const FkLaunch &); \
   template <> void launch_fk_loaded<N>(const FkLaunch &, const LoadedIn &); template <> void launch_fk_loaded_profile<N>(const FkLaunch &, const LoadedIn &); \
   template <> void launch_shoot_start<N>(const FkLaunch &, const double *, double *); \
   template <> void launch_fk_loaded_retract<N>(const FkLaunch &, const LoadedIn &); \
-  template <> void launch_shoot_start_retract<N>(const FkLaunch &, const double *, double *); \
+  template <> void launch_shoot_start_retract<N>(const FkLaunch &, const double *, double *, const int32_t *); \
   template <> void launch_fk_sweep_fused<N>(const FkLaunch &, const FusedSweepArgs *, size_t); \
   template <> void launch_fk_sweep_fused_list<N>(const FkLaunch &, const FusedSweepArgs *, size_t, const int32_t *, const uint32_t *); \
   template <> void launch_fk_verdict<N>(const FkLaunch &, const VerdictArgs *, size_t, bool, bool); \

@@ -208,26 +208,31 @@ __global__ __launch_bounds__(64) void shoot_lm_step(ShootParams prm, ShootState 
   st.mu[i] = mu; st.nu[i] = nu; st.iters[i] = iters; st.calls[i] = calls;
 }
 
-// results of a chunk (any output may be null); converged: |e| <= residual_threshold at the accepted strains
+// results of a chunk (any output may be null); converged: |e| <= residual_threshold at the accepted strains.  perm (a robot with
+// retraction solved in backbone-length order, loaded_host.inc: shoot_run): problem i's results go to row perm[i] of the outputs
 __global__ void shoot_finish(ShootParams prm, ShootState st, int64_t n, double *__restrict__ vu0, double *__restrict__ residual,
-                             int32_t *__restrict__ iters, int32_t *__restrict__ fk_calls, uint8_t *__restrict__ converged) {
+                             int32_t *__restrict__ iters, int32_t *__restrict__ fk_calls, uint8_t *__restrict__ converged,
+                             const int32_t *__restrict__ perm) {
 #pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (vu0) for (int j = 0; j < 6; j++) vu0[i * 6 + j] = st.p[i * 6 + j];
+  const int64_t o = perm ? (int64_t)perm[i] : i;
+  if (vu0) for (int j = 0; j < 6; j++) vu0[o * 6 + j] = st.p[i * 6 + j];
   const double err2 = st.err2[i];
-  if (residual) residual[i] = sqrt(err2);
-  if (iters) iters[i] = st.iters[i];
-  if (fk_calls) fk_calls[i] = st.calls[i];
-  if (converged) converged[i] = err2 <= prm.eps3_sq ? 1 : 0;
+  if (residual) residual[o] = sqrt(err2);
+  if (iters) iters[o] = st.iters[i];
+  if (fk_calls) fk_calls[o] = st.calls[i];
+  if (converged) converged[o] = err2 <= prm.eps3_sq ? 1 : 0;
 }
 
 // A robot with retraction: a problem whose s_start is negative lies outside the state space's bounds and integrates nothing (its
 // residual row is zero); it is reported unconverged, as the unloaded kernels report it (fk_retract_kernel.hpp).
-__global__ void shoot_negative_start(const double *__restrict__ states, int S, int64_t n, uint8_t *__restrict__ converged) {
+__global__ void shoot_negative_start(const double *__restrict__ states, int S, int64_t n, uint8_t *__restrict__ converged,
+                                     const int32_t *__restrict__ perm) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  if (states[i * S + S - 1] < 0.0) converged[i] = 0;
+  const int64_t o = perm ? (int64_t)perm[i] : i;       // (perm: the chunk's problems as rows of the caller's arrays)
+  if (states[o * S + S - 1] < 0.0) converged[o] = 0;
 }
 
 }  // namespace trk

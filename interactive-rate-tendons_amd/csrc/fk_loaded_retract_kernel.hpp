@@ -53,20 +53,22 @@ struct FrameLoad {
 
 template <int N>
 __global__ __launch_bounds__(64) void shoot_start_retract(const double *__restrict__ states, int64_t n, RobotK K, const PolyK *__restrict__ pk,
-                                                          const double *__restrict__ guess, double *__restrict__ vu) {
+                                                          const double *__restrict__ guess, double *__restrict__ vu,
+                                                          const int32_t *__restrict__ perm) {
   const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
   const bool live = i < n;
   const int64_t il = live ? i : (n - 1);       // tail lanes repeat the last problem (initial_bending votes across the wave)
+  const int64_t ig = perm ? (int64_t)perm[il] : il;      // the caller's row of this problem (the clamped index: perm holds n entries)
   double v[3], u[3];
   if (guess) {
 #pragma unroll
-    for (int q = 0; q < 3; q++) { v[q] = guess[il * 6 + q]; u[q] = guess[il * 6 + 3 + q]; }
+    for (int q = 0; q < 3; q++) { v[q] = guess[ig * 6 + q]; u[q] = guess[ig * 6 + 3 + q]; }
   } else {
     const int S = K.state_size;
     double tau[N];
 #pragma unroll
-    for (int j = 0; j < N; j++) tau[j] = states[il * S + j];
-    double s = states[il * S + S - 1];
+    for (int j = 0; j < N; j++) tau[j] = states[ig * S + j];
+    double s = states[ig * S + S - 1];
     if (s > K.L) s = K.L;                      // TendonRobot.cpp:359
     RouteCarry<N> rcy;
     route_anchor<N>(pk, K.n_a, s, rcy);
@@ -98,7 +100,10 @@ __global__ __launch_bounds__(64, (N <= TRK_LR_TWO_WAVE_MAXN ? 2 : 1)) void fk_lo
   const bool live = i < n;
   const int64_t il = live ? i : (n - 1);       // tail lanes recompute the last lane, stores masked
   const int64_t ir = il / in.Q;
-  const int64_t ic = in.list ? (int64_t)in.list[ir] : ir;
+  const int64_t iq = in.list ? (int64_t)in.list[ir] : ir;      // the launch's problem (chunk-local, from the clamped lane)
+  const int64_t ic = in.perm ? (int64_t)in.perm[iq] : iq;      // ... and its column of the caller's arrays
+  // outputs (one lane per problem: iq == i on live lanes) go to the caller's column; the launch's own arrays (vu, res) stay on i
+  const int64_t io = in.perm ? ic : i;
   const int S = K.state_size, Pmax = K.n_points;
   const double L = K.L, dL = K.dL;
   double tau[N];
@@ -149,7 +154,7 @@ __global__ __launch_bounds__(64, (N <= TRK_LR_TWO_WAVE_MAXN ? 2 : 1)) void fk_lo
   // `row` may differ from lane to lane (the lane's first two points) or be wave-uniform (the tip-aligned loop); always in [0, P)
   auto store_point = [&](int row, bool on) {
     if (!(on && live) || !out.px) return;
-    const int64_t o = (int64_t)row * ld + i;
+    const int64_t o = (int64_t)row * ld + io;
     double x = p[0], y = p[1], z = p[2];
     if (ROT) { const double x2 = __builtin_fma(rc, x, -(rs * y)), y2 = __builtin_fma(rs, x, rc * y); x = x2; y = y2; z = r22 * z; }
     out.px[o] = x; out.py[o] = y; out.pz[o] = z;
@@ -251,19 +256,19 @@ __global__ __launch_bounds__(64, (N <= TRK_LR_TWO_WAVE_MAXN ? 2 : 1)) void fk_lo
   double home[N];
   if (out.home_Li) home_lengths_lane<N>(pk, K, hl, s_raw, s, single, P_lane, shift, true, home);
   if (live) {
-    if (out.L) out.L[i] = Lb;
+    if (out.L) out.L[io] = Lb;
     if (out.Li) {
 #pragma unroll
-      for (int j = 0; j < N; j++) out.Li[(int64_t)j * ld + i] = Li[j];
+      for (int j = 0; j < N; j++) out.Li[(int64_t)j * ld + io] = Li[j];
     }
-    if (out.n_points) out.n_points[i] = P_lane;
+    if (out.n_points) out.n_points[io] = P_lane;
     if (out.home_Li) {
 #pragma unroll
-      for (int j = 0; j < N; j++) out.home_Li[(int64_t)j * ld + i] = home[j];
+      for (int j = 0; j < N; j++) out.home_Li[(int64_t)j * ld + io] = home[j];
     }
     if (in.vu_tip) {
 #pragma unroll
-      for (int q = 0; q < 3; q++) { in.vu_tip[i * 6 + q] = v[q]; in.vu_tip[i * 6 + 3 + q] = u[q]; }
+      for (int q = 0; q < 3; q++) { in.vu_tip[io * 6 + q] = v[q]; in.vu_tip[io * 6 + 3 + q] = u[q]; }
     }
   }
 }

@@ -7,7 +7,7 @@
 //   loaded_sample_loads  -> the level's wrench / distributed-load rows (frame BASE: the call's; WORLD: turned by Rz(-theta))
 //   loaded_sample_guess  -> with warm start, the start strains of a midpoint = the accepted base strains of its interval's sample
 //                           at t_a, from vu_pool (level 0 and the indexed form's vertices start cold)
-//   shoot_chunk_solve    -> over the level in chunks of shoot_chunk_size: points and L_i into the pool's workspace columns, the
+//   shoot_run            -> over the level in chunks of shoot_chunk_size: points and L_i into the pool's workspace columns, the
 //                           shooting's converged flag into the column K2 reads, the accepted strains into vu_pool
 //   launch_sweep         -> K2 on the stored planes with the sample test the run chose (+ the sphere test under that checker)
 // A sample whose shooting does not converge is an invalid sample (is_valid_shape rejects res.converged == false), never an error.
@@ -77,13 +77,9 @@ struct LoadedEdges {
       HIP_TRY(c, hipGetLastError());
     }
     const bool guess = warm && open != nullptr;
-    const int64_t chunk = shoot_chunk_size(c);
-    for (int64_t off = 0; off < m; off += chunk) {
-      const int64_t mm = std::min(chunk, m - off);
-      if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, mm, cap, le.w + off * 6, 6, le.d + off * 6, 6, guess ? le.g + off * 6 : nullptr,
-                                  ws_fk_out(c, s0 + off), c->ws.conv + s0 + off, le.vu_pool + (s0 + off) * 6, nullptr, nullptr, nullptr,
-                                  le.calls + off, nullptr, rounds))) return rc;
-    }
+    // (in chunks of shoot_chunk_size; a robot with retraction: the level's samples in the order of their backbone lengths, shoot_run)
+    if ((rc = shoot_run(c, prm, d_states, m, cap, le.w, 6, le.d, 6, guess ? le.g : nullptr, ws_fk_out(c, s0), c->ws.conv + s0,
+                        le.vu_pool + s0 * 6, nullptr, nullptr, nullptr, le.calls, nullptr, rounds))) return rc;
     {
       ProfScope ps(c, 3, nullptr);
       hipLaunchKernelGGL(trk::loaded_sample_tally, blocks(m), th, 0, nullptr, (const uint8_t *)(c->ws.conv + s0), (const int32_t *)le.calls, m, le.tally);
@@ -141,15 +137,23 @@ struct LoadedEdges {
 };
 
 // what both entry points check after their own arguments, in this order: the load set, the robot, an empty call, the grid and the
-// space's resolutions (edge_call_begin)
+// space's resolutions (edge_call_begin).  A robot with retraction: the verdict calls take it on a context opened with
+// TR_LOADED_RETRACTION_EDGES -- the run's evaluator writes through ws_fk_out / ws_sweep_in (point counts and per-sample home lengths)
+// and the interval test reads the stored point counts (EdgeRun::filter_np = ws.np), the path of the unloaded voxelize forms of such a
+// robot; `voxel_form` (the voxelize / connect forms) keeps refusing at every level, under its own name at that one.
 int loaded_edges_begin(tr_ctx *c, const tr_space_params *sp, const tr_shoot_params *shoot, const tr_edge_loads *loads, int64_t n_edges,
-                       LoadedEdges &le, bool &empty) {
+                       LoadedEdges &le, bool &empty, bool voxel_form = false) {
   empty = false;
   int rc;
   le.c = c;
   if ((rc = parse_loads(c, loads, le.loads))) return rc;
   le.warm = loads && loads->warm_start != 0;
-  if ((rc = shoot_check(c, n_edges, 0, 0)) || (rc = refuse_retraction(c, "loaded edges (tr_validate_edges_loaded*, tr_*_edges_loaded_indexed)"))) return rc;
+  if ((rc = shoot_check(c, n_edges, 0, 0))) return rc;
+  if (c->loaded_retraction != TR_LOADED_RETRACTION_EDGES)
+    rc = refuse_retraction(c, "loaded edges (tr_validate_edges_loaded*, tr_*_edges_loaded_indexed)");
+  else if (voxel_form)
+    rc = refuse_retraction(c, "loaded voxel forms of the edges (tr_voxelize_edges_loaded_indexed, tr_connect_edges_loaded_indexed)");
+  if (rc) return rc;
   if ((rc = shoot_params(c, shoot, le.prm))) return rc;
   if (n_edges == 0) { empty = true; return TR_OK; }
   if ((rc = edge_call_begin(c, sp))) return rc;

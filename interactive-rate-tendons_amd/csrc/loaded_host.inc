@@ -12,7 +12,8 @@ int64_t shoot_io_chunk(const tr_ctx *c) { return std::min<int64_t>(shoot_chunk_s
 
 void shoot_release(tr_ctx *c) {
   tr_ctx::ShootDev &k = c->shoot;
-  k.chunk.release(); k.once.release(); k.io.release(); k.io_frames.release(); k.count.release();
+  k.chunk.release(); k.once.release(); k.io.release(); k.io_frames.release(); k.count.release(); k.order.release();
+  trk::merge_free(k.ord_ms);
   k = tr_ctx::ShootDev{};
 }
 
@@ -152,19 +153,22 @@ int shoot_fk(tr_ctx *c, const double *d_states, int64_t lanes, int64_t ld, const
 
 // One chunk of m problems to the end.  d_wrench / d_dist / d_guess: the chunk's first row (d_wrench never null here).  `out`: K1's
 // outputs with column 0 = the chunk's first problem; the other outputs may be null.
+// `perm` (a robot with retraction, shoot_run's order): problem i of the chunk is column perm[i] of the CALL's arrays -- states, load and
+// guess rows, and every output are then the call's own, not offset to the chunk; the chunk's workspace stays indexed by i.
 int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, int64_t m, int64_t ld, const double *d_wrench,
                       int64_t wrench_ld, const double *d_dist, int64_t dist_ld, const double *d_guess, const trk::FkOut &out,
                       uint8_t *d_conv, double *d_vu0, double *d_vuL, double *d_res, int32_t *d_iters, int32_t *d_calls, hipStream_t s,
-                      int64_t &rounds, bool final_launch = true) {
+                      int64_t &rounds, bool final_launch = true, const int32_t *perm = nullptr) {
   tr_ctx::ShootDev &k = c->shoot;
   constexpr int Q = trk::kShootQ;
   const trk::ShootState st{k.p, k.pn, k.e, k.J, k.err2, k.mu, k.nu, k.iters, k.calls};
-  const trk::LoadedIn base{d_wrench, wrench_ld, d_dist, dist_ld, nullptr, nullptr, 1, nullptr, k.res, k.lanes, nullptr};
+  trk::LoadedIn base{d_wrench, wrench_ld, d_dist, dist_ld, nullptr, nullptr, 1, nullptr, k.res, k.lanes, nullptr};
+  base.perm = perm;
   int rc;
   {
     const trk::FkLaunch a = fk_launch_args(c, d_states, m, ld, kFkOutNone, false, s);
     const bool ret = c->K.enable_retraction;      // (the unloaded solution at the problem's own s_start)
-    TRK_FOR_TENDONS(c, if (ret) trk::launch_shoot_start_retract<N>(a, d_guess, k.pn); else trk::launch_shoot_start<N>(a, d_guess, k.pn));
+    TRK_FOR_TENDONS(c, if (ret) trk::launch_shoot_start_retract<N>(a, d_guess, k.pn, perm); else trk::launch_shoot_start<N>(a, d_guess, k.pn));
     HIP_TRY(c, hipGetLastError());
   }
   // the start of every problem: one lane each
@@ -203,10 +207,10 @@ int shoot_chunk_solve(tr_ctx *c, const trk::ShootParams &prm, const double *d_st
     in.vu = k.p; in.res = nullptr; in.vu_tip = d_vuL;
     if ((rc = shoot_fk(c, d_states, m, ld, out, in, s))) return rc;
   }
-  hipLaunchKernelGGL(trk::shoot_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_vu0, d_res, d_iters, d_calls, d_conv);
+  hipLaunchKernelGGL(trk::shoot_finish, dim3(ik_grid(m, 64)), dim3(64), 0, s, prm, st, m, d_vu0, d_res, d_iters, d_calls, d_conv, perm);
   HIP_TRY(c, hipGetLastError());
   if (c->K.enable_retraction && d_conv) {
-    hipLaunchKernelGGL(trk::shoot_negative_start, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_states, (int)c->K.state_size, m, d_conv);
+    hipLaunchKernelGGL(trk::shoot_negative_start, dim3(ik_grid(m, 64)), dim3(64), 0, s, d_states, (int)c->K.state_size, m, d_conv, perm);
     HIP_TRY(c, hipGetLastError());
   }
   return TR_OK;
@@ -221,6 +225,32 @@ int shoot_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_states, in
   int rc;
   if ((rc = shoot_reserve(c, n))) return rc;
   const int64_t chunk = shoot_chunk_size(c);
+  tr_ctx::ShootDev &k = c->shoot;
+  k.order_last[0] = n; k.order_last[1] = 0;
+  if (c->K.enable_retraction && c->loaded_retract_sort_min > 0 && n >= c->loaded_retract_sort_min) {
+    // A wave of fk_loaded_retract runs from its longest backbone's base to the tip while its shorter lanes idle: deal the problems to
+    // the chunks -- and with them to the waves -- in the order of their s_start.  Every lane reads and writes the caller's column
+    // perm[.], so nothing is gathered and nothing comes back out of order.
+    if (k.ord_cap < n) {
+      HIP_TRY(c, hipDeviceSynchronize());
+      k.order.release();
+      k.ord_cap = 0;
+      const size_t cap = (size_t)round_up(n + n / 4, 64);
+      for (int q = 0; q < 2; q++)
+        if ((rc = k.order.alloc(c, &k.ord_keys[q], cap)) || (rc = k.order.alloc(c, &k.ord_vals[q], cap))) return rc;
+      k.ord_cap = (int64_t)cap;
+    }
+    const int32_t *perm = nullptr;
+    const hipError_t e = trk::retraction_order(k.ord_ms, d_states, n, S, c->K.L, k.ord_keys, k.ord_vals, &perm, s);
+    if (e != hipSuccess) return fail(c, TR_ERR_HIP, std::string("retraction order (loaded FK): ") + hipGetErrorString(e));
+    for (int64_t off = 0; off < n; off += chunk) {
+      const int64_t m = std::min(chunk, n - off);
+      if ((rc = shoot_chunk_solve(c, prm, d_states, m, ld, d_wrench ? d_wrench : c->shoot.zero6, d_wrench ? wrench_ld : 0, d_dist, dist_ld,
+                                  d_guess, out, d_conv, d_vu0, d_vuL, d_res, d_iters, d_calls, s, rounds, true, perm + off))) return rc;
+    }
+    k.order_last[1] = n;
+    return TR_OK;
+  }
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
     const trk::FkOut o{rows_at(out.px, off), rows_at(out.py, off), rows_at(out.pz, off), rows_at(out.R, off), rows_at(out.L, off),
@@ -270,6 +300,14 @@ int tr_set_load_profile(tr_ctx *c, int64_t n_knots, const double *s, const doubl
   HIP_TRY(c, hipMemcpy(c->profile.d_table, table.data(), n * sizeof(double), hipMemcpyHostToDevice));
   c->profile.table.swap(table);
   c->profile.on = true;
+  return TR_OK;
+}
+
+// The context's last shooting run (shoot_run: one call of tr_fk_loaded_batch*, one chunk of tr_fk_loaded_tips*, one level of a loaded
+// edge call): its problems, and how many of them were solved in backbone-length order (all of them or none).
+int tr_loaded_order_last(const tr_ctx *c, int64_t stats[2]) {
+  if (!c || !stats) return TR_ERR_INVALID_ARG;
+  stats[0] = c->shoot.order_last[0]; stats[1] = c->shoot.order_last[1];
   return TR_OK;
 }
 

@@ -148,7 +148,7 @@ int voxelize_edges_loaded_indexed_impl(tr_ctx *c, const tr_space_params *sp, con
   LoadedEdges le{};
   bool empty;
   int rc;
-  if ((rc = loaded_edges_begin(c, sp, shoot, loads, n_edges, le, empty)) || empty) return rc;
+  if ((rc = loaded_edges_begin(c, sp, shoot, loads, n_edges, le, empty, /*voxel_form=*/true)) || empty) return rc;
   if ((rc = check_edge_indices(c, edges, n_edges, n_states))) return rc;
   if ((rc = ensure_edge_pool(c, n_edges + n_states / 8))) return rc;
   const int S = c->K.state_size;
@@ -213,9 +213,10 @@ int loaded_tips_run(tr_ctx *c, const trk::ShootParams &prm, const double *d_stat
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min(chunk, n - off);
     uint8_t *conv = d_conv ? d_conv + off : c->ws.conv;
-    if ((rc = shoot_chunk_solve(c, prm, d_states + off * S, m, cap, d_wrench ? d_wrench + off * wrench_ld : c->shoot.zero6, d_wrench ? wrench_ld : 0,
-                                rows_at(d_dist, off, dist_ld), dist_ld, rows_at(d_guess, off, 6), ws_fk_out(c, 0), conv, rows_at(d_vu0, off, 6),
-                                nullptr, nullptr, nullptr, c->ledge.calls, nullptr, rounds))) return rc;
+    // (one chunk of the shooting's: m <= shoot_chunk_size; a robot with retraction: the chunk in the order of its backbone lengths)
+    if ((rc = shoot_run(c, prm, d_states + off * S, m, cap, d_wrench ? d_wrench + off * wrench_ld : nullptr, wrench_ld,
+                        rows_at(d_dist, off, dist_ld), dist_ld, rows_at(d_guess, off, 6), ws_fk_out(c, 0), conv, rows_at(d_vu0, off, 6),
+                        nullptr, nullptr, nullptr, c->ledge.calls, nullptr, rounds))) return rc;
     {
       ProfScope ps(c, 3, nullptr);
       hipLaunchKernelGGL(trk::loaded_sample_tally, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, (const uint8_t *)conv,

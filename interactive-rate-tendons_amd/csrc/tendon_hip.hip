@@ -80,6 +80,9 @@ struct Workspace {
 struct EventPair { hipEvent_t a, b; };
 
 constexpr int64_t kRetractSortMin = 8192;   // below this a launch is a few waves per CU at most: ordering them buys nothing
+// the loaded FK's own threshold (tr_ctx::loaded_retract_sort_min): the smallest measured size at which the ordered solve beat arrival
+// order by more than the run-to-run spread: 2^10 problems, 1.94 against 2.01 ms, spread 0.02 ms (README: "Loaded edges of retraction robots")
+constexpr int64_t kLoadedRetractSortMin = 1024;
 constexpr int64_t kSmallBatch = 4096;   // tr_validate_batch: up to here the single-stream path without a device-wide sync
 
 // device state of the edge frontier (edge_kernel.hpp / edge_run_host.inc)
@@ -307,6 +310,12 @@ struct tr_ctx {
     int32_t *io_np = nullptr, *io_it = nullptr, *io_fc = nullptr;
     uint8_t *io_conv = nullptr;
     DevOwner chunk, once, io, io_frames;                            // sized by probs; counter, tip_route, zero6; by io_probs; io_R
+    // a robot with retraction: the call's problems in the order of their backbone lengths (shoot_run; cache_merge.hpp:
+    // retraction_order).  Buffers and radix-sort scratch of the shooting's own: lane 0's may be held by the edge run that calls it
+    uint32_t *ord_keys[2] = {nullptr, nullptr}; int32_t *ord_vals[2] = {nullptr, nullptr}; int64_t ord_cap = 0;
+    trk::MergeScratch ord_ms;
+    DevOwner order;                                                 // sized by ord_cap
+    int64_t order_last[2] = {0, 0};                                 // tr_loaded_order_last
   } shoot;
   // loaded edges (loaded_edges_host.inc): per pool sample the accepted base strains [cap][6]; per level sample the load rows, the
   // start strains [cap][6] each and the integrations [cap]; the run's tally (unconverged samples, integrations)
@@ -353,7 +362,10 @@ struct tr_ctx {
     double *d_table = nullptr;
   } profile;
   int64_t loaded_vertex_batch = 0;   // candidates per batch of the loaded vertex phase (0: what the point workspace holds); TENDON_HIP_LOADED_VERTEX_BATCH, testing only
-  bool loaded_retraction = false;    // tr_set_loaded_retraction: the loaded FK, tips and validity take this (retraction) robot
+  int loaded_retraction = 0;         // tr_set_loaded_retraction's level: 1 the loaded FK, tips and validity take this (retraction) robot, 2 the loaded edge checks too
+  // problems of a call from which the loaded FK of a retraction robot solves them in backbone-length order (0: never, arrival order);
+  // TENDON_HIP_LOADED_RETRACT_SORT=<n>
+  int64_t loaded_retract_sort_min = kLoadedRetractSortMin;
   int64_t shoot_chunk = 0;           // problems per chunk of the loaded FK (0: what kIkLanes holds); TENDON_HIP_SHOOT_CHUNK, testing only
   // instrumentation
   bool profiling = false;
@@ -1091,6 +1103,7 @@ int tr_create(const tr_robot_desc *rb, int device, tr_ctx **out) {
   c->device = device;
   if (const char *e = std::getenv("TENDON_HIP_FUSED")) { const int v = std::atoi(e); c->fuse = v < 0 ? 0 : (v > 2 ? 2 : v); }
   if (const char *e = std::getenv("TENDON_HIP_RETRACT_SORT")) c->retract_sort_min = std::atoll(e);
+  if (const char *e = std::getenv("TENDON_HIP_LOADED_RETRACT_SORT")) c->loaded_retract_sort_min = std::max<long long>(0, std::atoll(e));
   if (std::getenv("TENDON_HIP_RETRACT_KBEGIN_OFF")) c->retract_wave_start = false;
   const char *routing_env = std::getenv("TENDON_HIP_ROUTING");      // "table": the table form of the right-hand side for every robot (A/B)
   if (const char *e = std::getenv("TENDON_HIP_EDGE_LANES")) { c->edge_lanes = std::max(1, std::min(tr_ctx::kMaxLanes, std::atoi(e))); c->edge_lanes_fixed = true; }
@@ -1267,9 +1280,10 @@ int tr_state_size(const tr_ctx *c) { return c ? c->K.state_size : -1; }
 int tr_set_loaded_retraction(tr_ctx *c, int on) {
   if (!c) return TR_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lock_(c->mu);
-  c->loaded_retraction = on != 0;
+  c->loaded_retraction = on == TR_LOADED_RETRACTION_EDGES ? TR_LOADED_RETRACTION_EDGES : (on != 0 ? TR_LOADED_RETRACTION_FK : TR_LOADED_RETRACTION_OFF);
   return TR_OK;
 }
+int tr_loaded_retraction(const tr_ctx *c) { return c ? c->loaded_retraction : -1; }
 int tr_num_points(const tr_ctx *c) { return c ? c->K.n_points : -1; }
 int tr_device(const tr_ctx *c) { return c ? c->device : -1; }
 

@@ -343,13 +343,26 @@ class Engine:
             return a, 6
         raise L.InvalidArgument("%s must be (6,) or (n, 6)" % name)
 
-    def set_loaded_retraction(self, on=True):
+    def set_loaded_retraction(self, on=True, edges=False):
         """tr_set_loaded_retraction: open (or close) this engine to LOADED shapes of its robot with retraction.  Never opened, every
         loaded call refuses such a robot as it always did; opened, fk_loaded_batch*, fk_loaded_tips* and with them
         robot.general_shape take it, and the loaded calls above them (edges, roadmap builds, IK, Jacobian, tip queries, load
         profiles) still raise Unsupported, each under its own name.  validate_loaded and fk_loaded_batch_retraction_dev need no
-        opening."""
-        L.check(self._ctx, self.lib.tr_set_loaded_retraction(self._ctx, int(bool(on))))
+        opening.  edges=True (level 2) opens the loaded edge checks as well: validate_edges_loaded, validate_edges_loaded_indexed,
+        and with them checker.set_loads and the motion validators on a checker that owns this engine."""
+        L.check(self._ctx, self.lib.tr_set_loaded_retraction(self._ctx, (2 if edges else 1) if on else 0))
+
+    def loaded_retraction(self):
+        """The level set_loaded_retraction left: 0 closed, 1 the loaded FK, tips and validity, 2 the loaded edge checks too."""
+        return int(self.lib.tr_loaded_retraction(self._ctx))
+
+    def loaded_order_last(self):
+        """tr_loaded_order_last: dict(problems, ordered) of this engine's last shooting run -- one fk_loaded_batch* call, one chunk of
+        fk_loaded_tips*, one level of a loaded edge call; ordered: how many of the problems were solved in backbone-length order
+        (a robot with retraction and at least TENDON_HIP_LOADED_RETRACT_SORT problems: all of them; else 0)."""
+        q = (C.c_int64 * 2)()
+        L.check(self._ctx, self.lib.tr_loaded_order_last(self._ctx, q))
+        return dict(problems=int(q[0]), ordered=int(q[1]))
 
     # ---- the load profile of every loaded call (tr_set_load_profile): a weight w(s) on the distributed load ------------------------
     def set_load_profile(self, knots, weights):

@@ -165,11 +165,14 @@ class VoxelBackboneValidityChecker:
         is_valid and the motion validators on this checker judge LOADED shapes, and a RoadmapBuilder on it builds on them (vertex
         phase, connect, both voxel caches; roadmap.py); clear_loads() restores the unloaded checks.  profile = (knots, weights): a
         weight w(s) along the backbone on `dist` (Engine.set_load_profile), installed on the checker's engine until clear_loads() or
-        the next set_loads; load_profile() reports it."""
+        the next set_loads; load_profile() reports it.  A robot with retraction: Unsupported unless this checker's engine is open to the
+        loaded edge checks (self.engine.set_loaded_retraction(edges=True)); then is_valid and the motion validators judge loaded shapes,
+        while the discrete validator, a RoadmapBuilder and profile= keep raising Unsupported."""
         self.engine._edge_loads(wrench, dist, frame, warm_start)              # argument checks
-        if self._robot.enable_retraction:
-            # Engine.validate_loaded judges the loaded STATES of such a robot; the motion validators behind this checker cannot judge
-            # its edges yet, and a checker that is loaded for one of the two would plan on mixed shapes
+        if self._robot.enable_retraction and self.engine.loaded_retraction() < 2:
+            # Engine.validate_loaded judges the loaded STATES of such a robot; the motion validators behind this checker judge its
+            # edges only on an engine opened to them (engine.set_loaded_retraction(edges=True)), and a checker that is loaded for one
+            # of the two would plan on mixed shapes
             raise L.Unsupported("checker.set_loads: loaded FK (general_shape) is not built for robots with retraction in this call "
                                 "(Engine.fk_loaded_batch, fk_loaded_tips and validate_loaded are)")
         if profile is not None:
