@@ -78,9 +78,7 @@ unsigned ik_grid(int64_t n, int block) { return (unsigned)((n + block - 1) / blo
 
 // K1 over `lanes` expanded states: tips only
 int ik_fk(tr_ctx *c, int64_t lanes, hipStream_t s) {
-  trk::FkOut out = kFkOutNone;
-  out.tips = c->ik.tips;
-  return launch_fk(c, c->ik.xs, lanes, round_up(lanes, 64), out, s);
+  return launch_fk(c, c->ik.xs, lanes, round_up(lanes, 64), fk_out_tips(c->ik.tips), s);
 }
 
 // f and J of m <= ik_chunk states (device rows)
@@ -195,8 +193,7 @@ int tr_fk_tips_dev(tr_ctx *c, const double *d_states, int64_t n, double *d_tips,
   const hipStream_t s = (hipStream_t)stream;
   int rc;
   if ((rc = begin_dev_work(c, s))) return rc;
-  const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tips, d_converged, nullptr, nullptr};
-  if ((rc = launch_fk(c, d_states, n, round_up(n, 64), out, s))) return rc;
+  if ((rc = launch_fk(c, d_states, n, round_up(n, 64), fk_out_tips(d_tips, d_converged), s))) return rc;
   return note_dev_work(c, s);
 }
 
@@ -215,8 +212,7 @@ int tr_fk_tips(tr_ctx *c, const double *states, int64_t n, double *tips, uint8_t
   for (int64_t off = 0; off < n; off += chunk_max) {
     const int64_t m = std::min(chunk_max, n - off);
     HIP_TRY(c, hipMemcpy(w.states, states + off * S, (size_t)m * S * sizeof(double), hipMemcpyHostToDevice));
-    const trk::FkOut out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w.tips, converged ? w.flags : nullptr, nullptr, nullptr};
-    if ((rc = launch_fk(c, w.states, m, round_up(m, 64), out, nullptr))) return rc;
+    if ((rc = launch_fk(c, w.states, m, round_up(m, 64), fk_out_tips(w.tips, converged ? w.flags : nullptr), nullptr))) return rc;
     HIP_TRY(c, hipMemcpy(tips + off * 3, w.tips, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (converged) HIP_TRY(c, hipMemcpy(converged + off, w.flags, (size_t)m, hipMemcpyDeviceToHost));
   }

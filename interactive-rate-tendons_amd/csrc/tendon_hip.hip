@@ -143,6 +143,23 @@ struct RoundCount {
   void release() { if (h) (void)hipHostFree(h); d = h = nullptr; }   // (d is its owner's)
 };
 
+// The arguments a kernel reads from device memory (trk::VerdictArgs, trk::FusedSweepArgs), for launches that may overlap: a small
+// ring of device slots filled from a pinned host image, each guarded by an event so that a slot is not rewritten while a launch may
+// still read it.  Per launch: acquire (waits for the slot's previous launch), fill the image, push, launch, commit.
+template <typename T>
+struct ArgRing {
+  static constexpr int kSlots = 16;
+  T *d_slots = nullptr, *h_slots = nullptr;   // device ring and its pinned host image
+  hipEvent_t ev[kSlots];
+  bool used[kSlots] = {};
+  int next = 0;
+  int acquire(tr_ctx *ctx, int *slot, T **image);            // (defined in launch_host.inc, as the next three)
+  int push(tr_ctx *ctx, int slot, hipStream_t s);
+  int commit(tr_ctx *ctx, int slot, hipStream_t s);
+  void release();
+  const T *dev(int slot) const { return d_slots + slot; }
+};
+
 }  // namespace
 
 struct tr_ctx {
@@ -228,20 +245,8 @@ struct tr_ctx {
   int64_t retract_sort_min = kRetractSortMin;
   bool rows_one_step = false;           // behind the grid's own first interval every RK4 step ends in the next row
   bool retract_wave_start = true;       // TENDON_HIP_RETRACT_KBEGIN_OFF (A/B switch of profiles/probe_retract.py): +1 - 2 %
-  struct VerdictRing {
-    static constexpr int kSlots = 16;
-    trk::VerdictArgs *d_slots = nullptr, *h_slots = nullptr;
-    hipEvent_t ev[kSlots];
-    bool used[kSlots] = {};
-    int next = 0;
-  } vring;
-  struct FusedRing {
-    static constexpr int kSlots = 16;
-    trk::FusedSweepArgs *d_slots = nullptr, *h_slots = nullptr;   // device ring and its pinned host image
-    hipEvent_t ev[kSlots];
-    bool used[kSlots] = {};
-    int next = 0;
-  } fused;
+  ArgRing<trk::VerdictArgs> vring;       // fk_verdict*, fk_edge_queue
+  ArgRing<trk::FusedSweepArgs> fused;    // fk_sweep_fused*, the fallback pass of the verdict path
   // scratch of the neighbour search (knn_impl), kept between calls: hipMalloc / hipFree of a dozen buffers per call cost more
   // than the search itself inside a process that holds large allocations (33 against 10 ms at 10^5 states)
   struct KnnScratch { void *p[13] = {}; size_t cap[13] = {}; } knn;
@@ -560,6 +565,16 @@ int ensure_staging(tr_ctx *ctx, int64_t n) {
   return TR_OK;
 }
 
+// the context's pinned staging buffer (upload_staged, download_staged), grown to hold `bytes`: waits for the device before it is replaced
+int ensure_stage(tr_ctx *c, size_t bytes) {
+  if (c->h_stage_cap >= bytes) return TR_OK;
+  if (c->h_stage) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; }
+  const size_t want = bytes + bytes / 4;
+  HIP_TRY(c, hipHostMalloc(&c->h_stage, want, hipHostMallocDefault));
+  c->h_stage_cap = want;
+  return TR_OK;
+}
+
 // Host array -> device through a pinned buffer of the context (grow-only): memcpy, then a KERNEL that reads the pinned memory
 // over the bus (hipHostMalloc memory is mapped into the device's address space): the same cost as the runtime's staged copy
 // without its choice between staging and pinning the caller's pages.  `bytes` must be a multiple of 8 (doubles / int64).
@@ -572,12 +587,7 @@ int ensure_staging(tr_ctx *ctx, int64_t n) {
 int upload_staged(tr_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipStream_t s) {
   if (bytes == 0) return TR_OK;
   if (bytes % 8) return fail(c, TR_ERR_INVALID_ARG, "upload_staged: whole 8-byte words only");
-  if (c->h_stage_cap < bytes) {
-    if (c->h_stage) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; }
-    const size_t want = bytes + bytes / 4;
-    HIP_TRY(c, hipHostMalloc(&c->h_stage, want, hipHostMallocDefault));
-    c->h_stage_cap = want;
-  }
+  if (const int rc = ensure_stage(c, bytes)) return rc;
   std::memcpy(c->h_stage, h_src, bytes);
   const int64_t words = (int64_t)(bytes / 8);
   hipLaunchKernelGGL(trk::copy_words, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 2048)), dim3(256), 0, s, (uint64_t *)d_dst,
@@ -593,12 +603,7 @@ int upload_staged(tr_ctx *c, void *d_dst, const void *h_src, size_t bytes, hipSt
 int download_staged(tr_ctx *c, void *h_dst, const void *d_src, size_t bytes, hipStream_t s) {
   if (bytes == 0) return TR_OK;
   const size_t padded = (bytes + 7) / 8 * 8;
-  if (c->h_stage_cap < padded) {
-    if (c->h_stage) { HIP_TRY(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; }
-    const size_t want = padded + padded / 4;
-    HIP_TRY(c, hipHostMalloc(&c->h_stage, want, hipHostMallocDefault));
-    c->h_stage_cap = want;
-  }
+  if (const int rc = ensure_stage(c, padded)) return rc;
   const int64_t words = (int64_t)(padded / 8);
   hipLaunchKernelGGL(trk::copy_words, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 2048)), dim3(256), 0, s, (uint64_t *)c->h_stage,
                      (const uint64_t *)d_src, words);
@@ -608,470 +613,7 @@ int download_staged(tr_ctx *c, void *h_dst, const void *d_src, size_t bytes, hip
   return TR_OK;
 }
 
-struct ProfScope {
-  tr_ctx *ctx; int slot; hipStream_t s; EventPair ev{};
-  bool on;
-  ProfScope(tr_ctx *c, int slot_, hipStream_t s_) : ctx(c), slot(slot_), s(s_), on(c->profiling) {
-    if (on) {
-      (void)hipEventCreate(&ev.a); (void)hipEventCreate(&ev.b);
-      (void)hipEventRecord(ev.a, s);
-    }
-  }
-  ~ProfScope() {
-    if (on) { (void)hipEventRecord(ev.b, s); ctx->events[slot].push_back(ev); }
-  }
-};
-
-// The *_dev entry points that use per-context scratch (fallback list and counter, workspace columns, ordering buffers, argument
-// rings, the sampler's batch) bracket their work with these two.  Calls on ONE stream are ordered by the stream; a call that
-// arrives on a DIFFERENT stream than the previous one first makes its stream wait for that call's work (a device-side
-// dependency, no host synchronisation), so two caller streams can never run on the shared scratch at once -- calls on one
-// context execute in the order they were issued, whichever streams they name.
-int begin_dev_work(tr_ctx *ctx, hipStream_t s) {
-  if (ctx->last_dev_used && ctx->last_dev_stream != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->last_dev_ev, 0));
-  return TR_OK;
-}
-// ... and this after enqueueing their work
-int note_dev_work(tr_ctx *ctx, hipStream_t s) {
-  if (!ctx->last_dev_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->last_dev_ev, hipEventDisableTiming));
-  HIP_TRY(ctx, hipEventRecord(ctx->last_dev_ev, s));
-  ctx->last_dev_used = true;
-  ctx->last_dev_stream = s;
-  return TR_OK;
-}
-
-// A lane's fallback list (with its counter) and its ordering buffers, grown to hold n entries: the caller says how much room it wants
-// (whole waves; the lanes of an edge bisection ask for their share of the pool up front, since growing mid-run would stall all streams)
-int ensure_lane_fallback(tr_ctx *ctx, int lane, int64_t n) {
-  tr_ctx::EdgeLaneDev &ln = ctx->lane[lane];
-  if (ln.fb_list_cap >= n) return TR_OK;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  int rc;
-  if ((rc = dev_alloc(ctx, &ln.fb_list, (size_t)n))) return rc;
-  if (!ln.fb_count && (rc = dev_alloc(ctx, &ln.fb_count, 1))) return rc;
-  ln.fb_list_cap = n;
-  return TR_OK;
-}
-int ensure_lane_order(tr_ctx *ctx, int lane, int64_t n) {
-  tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
-  if (ro.cap >= n) return TR_OK;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  int rc;
-  for (int q = 0; q < 2; q++) {
-    if ((rc = dev_alloc(ctx, &ro.keys[q], (size_t)n))) return rc;
-    if ((rc = dev_alloc(ctx, &ro.vals[q], (size_t)n))) return rc;
-  }
-  if ((rc = dev_alloc(ctx, &ro.kbegin, (size_t)n / 64 + 1))) return rc;
-  ro.cap = n;
-  return TR_OK;
-}
-
-// radix-sort scratch of a lane's ordering: lane 0 sorts in the context's (cache_merge.hip), lanes 1 .. in their own
-trk::MergeScratch &order_scratch(tr_ctx *ctx, int lane) { return lane == 0 ? ctx->merge : ctx->lane[lane].ro.ms; }
-
-// The point workspace from column `col` on, as K1 writes it and as K2 reads it (stored points, no frames, lengths or tips)
-trk::FkOut ws_fk_out(const tr_ctx *ctx, int64_t col) {
-  const Workspace &w = ctx->ws;
-  const bool ret = ctx->K.enable_retraction;
-  return trk::FkOut{w.px + col, w.py + col, w.pz + col, nullptr, nullptr, w.Li + col, nullptr, w.conv + col, ret ? w.np + col : nullptr,
-                    ret ? w.homeLi + col : nullptr};
-}
-trk::SweepIn ws_sweep_in(const tr_ctx *ctx, int64_t col) {
-  const Workspace &w = ctx->ws;
-  const bool ret = ctx->K.enable_retraction;
-  return trk::SweepIn{w.px + col, w.py + col, w.pz + col, ret ? w.np + col : nullptr, w.Li + col, w.conv + col, ret ? w.homeLi + col : nullptr,
-                      w.acc + col};
-}
-
-// ---- K1 launch (instantiations live in fk_inst.hip objects) ------------------------------------
-// this context's launch arguments of a K1-family kernel over n states (the verdict, fused and edge-queue launches set further fields)
-trk::FkLaunch fk_launch_args(const tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, bool write_R,
-                             hipStream_t s) {
-  return trk::FkLaunch{d_states, n, ld, ctx->K, (bool)ctx->K.enable_rotation, write_R, ctx->d_tab, ctx->d_steps,
-                       (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, out, s};
-}
-
-// a launch that stores nothing through FkOut
-const trk::FkOut kFkOutNone{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-
-// The statement(s) given, once per tendon count with N a constant expression: the dispatch to the kernels' instantiations.
-// Returns from the enclosing function when the context's count has none.
-#define TRK_TENDONS_CASE(COUNT, ...) case COUNT: { constexpr int N = COUNT; __VA_ARGS__; } break;
-#define TRK_FOR_TENDONS(ctx, ...)                                                                                          \
-  switch ((ctx)->K.n_tendons) {                                                                                            \
-    TRK_TENDONS_CASE(1, __VA_ARGS__) TRK_TENDONS_CASE(2, __VA_ARGS__) TRK_TENDONS_CASE(3, __VA_ARGS__) TRK_TENDONS_CASE(4, __VA_ARGS__) \
-    TRK_TENDONS_CASE(5, __VA_ARGS__) TRK_TENDONS_CASE(6, __VA_ARGS__) TRK_TENDONS_CASE(7, __VA_ARGS__) TRK_TENDONS_CASE(8, __VA_ARGS__) \
-    default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");                                              \
-  }
-
-// The same over the state size S (1 .. TRK_IK_MAX_S), with SS the constant expression: the step kernels' instantiations.
-#define TRK_STATE_SIZE_CASE(SIZE, ...) case SIZE: { constexpr int SS = SIZE; __VA_ARGS__; } break;
-#define TRK_FOR_STATE_SIZE(ctx, S, ...)                                                                                    \
-  switch (S) {                                                                                                             \
-    TRK_STATE_SIZE_CASE(1, __VA_ARGS__) TRK_STATE_SIZE_CASE(2, __VA_ARGS__) TRK_STATE_SIZE_CASE(3, __VA_ARGS__)              \
-    TRK_STATE_SIZE_CASE(4, __VA_ARGS__) TRK_STATE_SIZE_CASE(5, __VA_ARGS__) TRK_STATE_SIZE_CASE(6, __VA_ARGS__)              \
-    TRK_STATE_SIZE_CASE(7, __VA_ARGS__) TRK_STATE_SIZE_CASE(8, __VA_ARGS__) TRK_STATE_SIZE_CASE(9, __VA_ARGS__)              \
-    TRK_STATE_SIZE_CASE(10, __VA_ARGS__)                                                                                    \
-    default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "state size out of range");                                             \
-  }
-
-int launch_fk(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, hipStream_t s, int lane = 0) {
-  if (n <= 0) return TR_OK;
-  ProfScope ps(ctx, 0, s);
-  const bool ret = ctx->K.enable_retraction;
-  trk::FkLaunch a = fk_launch_args(ctx, d_states, n, ld, out, out.R != nullptr, s);
-  if (ret && ctx->retract_sort_min > 0 && n >= ctx->retract_sort_min) {
-    // A large batch of a retraction robot is integrated in the order of its backbone lengths, as the verdict-only kernels do
-    // (a wave runs from its LONGEST backbone's base to the tip, the shorter ones idle: in arrival order half of the lane-steps
-    // are masked), and every stored output goes to its configuration's own column: same planes, bit for bit.
-    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;      // (a lane of the edge bisection: its own buffers and sort scratch, as launch_verdict's)
-    if (const int rc = ensure_lane_order(ctx, lane, round_up(n, 64))) return rc;
-    const int32_t *perm = nullptr;
-    const hipError_t e = trk::retraction_order(order_scratch(ctx, lane), d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &perm, s,
-                                               ctx->K.dL, ctx->k_first, ctx->rows_one_step, ro.kbegin);
-    if (e != hipSuccess) return fail(ctx, TR_ERR_HIP, std::string("retraction order: ") + hipGetErrorString(e));
-    a.d_perm = perm;
-    a.d_wave_k_begin = ctx->retract_wave_start ? ro.kbegin : nullptr;
-  }
-  TRK_FOR_TENDONS(ctx, if (ret) trk::launch_fk_retract<N>(a); else trk::launch_fk_uniform<N>(a));
-  HIP_TRY(ctx, hipGetLastError());
-  return TR_OK;
-}
-
-// milestone spacing for the LDS self-collision proof: about two robot radii of arc per chunk,
-// coarser if needed to keep the per-wave LDS image (4 * NM * 64 floats) within 48 KiB
-void sweep_geometry(const tr_ctx *ctx, int &CH, int &NM, size_t &lds) {
-  const int P = ctx->K.n_points;
-  CH = (int)std::lround(ctx->ch_scale * ctx->K.radius / ctx->K.dL);
-  if (CH < 1) CH = 1;
-  while ((P - 1 + CH - 1) / CH + 1 > 48) CH++;
-  NM = (P - 1 + CH - 1) / CH + 1;
-  lds = (size_t)4 * NM * 64 * sizeof(float) + (128 + 64) * sizeof(uint32_t) + (size_t)6 * 128 * sizeof(double);   // milestones + deferred-walk ring, flags and the ring's end points
-}
-
-int launch_sweep(tr_ctx *ctx, const trk::SweepIn &in, int64_t n, int64_t ld, int check_voxels,
-                 uint64_t *d_bits, uint8_t *d_flags, hipStream_t s) {
-  if (n <= 0) return TR_OK;
-  if (check_voxels && !ctx->has_grid) return fail(ctx, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");
-  ProfScope ps(ctx, 1, s);
-  int CH, NM; size_t lds;
-  sweep_geometry(ctx, CH, NM, lds);
-  const unsigned grid = (unsigned)((n + 63) / 64);
-  hipLaunchKernelGGL(trk::backbone_voxel_sweep, dim3(grid), dim3(64), lds, s, in, n, ld, ctx->K.n_points, CH, NM, ctx->K,
-                     ctx->G, ctx->d_grid, ctx->d_near, check_voxels, ctx->debug, d_bits, d_flags);
-  HIP_TRY(ctx, hipGetLastError());
-  return TR_OK;
-}
-
-// A device copy of the sweep's arguments for one fused launch: a small ring of device slots filled from pinned host
-// memory (an asynchronous copy on the launch stream), each guarded by an event so a slot is not rewritten while a
-// launch may still read it.  *slot_out receives the slot (record fr.ev[slot] on the stream after the launch).
-int fused_args_slot(tr_ctx *ctx, const trk::SweepIn &in, int check_voxels, uint64_t *d_bits, uint8_t *d_flags, hipStream_t s,
-                    const trk::FusedSweepArgs **d_args, size_t *lds, int *slot_out, uint32_t *sig = nullptr, int64_t sig_stride = 0) {
-  tr_ctx::FusedRing &fr = ctx->fused;
-  if (!fr.d_slots) {
-    HIP_TRY(ctx, hipMalloc((void **)&fr.d_slots, sizeof(trk::FusedSweepArgs) * tr_ctx::FusedRing::kSlots));
-    HIP_TRY(ctx, hipHostMalloc((void **)&fr.h_slots, sizeof(trk::FusedSweepArgs) * tr_ctx::FusedRing::kSlots, hipHostMallocDefault));
-    for (auto &e : fr.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const int slot = fr.next;
-  fr.next = (fr.next + 1) % tr_ctx::FusedRing::kSlots;
-  // the slot's previous launch (kSlots launches ago, possibly on another stream) must be done before its
-  // host image is rewritten and its device copy replaced
-  if (fr.used[slot]) HIP_TRY(ctx, hipEventSynchronize(fr.ev[slot]));
-  trk::FusedSweepArgs &a = fr.h_slots[slot];
-  a = trk::FusedSweepArgs{};
-  a.in = in;
-  sweep_geometry(ctx, a.CH, a.NM, *lds);
-  if (sig) *lds = std::max(*lds, (size_t)trk::SIG_LDS_WORDS * 4);       // the signature tile shares the sweep's image (sweep_kernel.hpp: SigStage)
-  a.P = ctx->K.n_points; a.check_voxels = check_voxels; a.debug = ctx->debug;
-  a.g = ctx->G; a.grid = ctx->d_grid; a.near_grid = ctx->d_near; a.valid_bits = d_bits; a.flags = d_flags;
-  a.sig = sig; a.sig_stride = sig_stride;
-  HIP_TRY(ctx, hipMemcpyAsync(fr.d_slots + slot, &a, sizeof(a), hipMemcpyHostToDevice, s));   // pinned source: asynchronous
-  *d_args = fr.d_slots + slot;
-  *slot_out = slot;
-  return TR_OK;
-}
-
-// K1 + K2 in one launch (fused_kernel.hpp; shared arc-length grid only).
-int launch_fused(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, const trk::SweepIn &in,
-                 int check_voxels, uint64_t *d_bits, uint8_t *d_flags, hipStream_t s, uint32_t *sig = nullptr, int64_t sig_stride = 0) {
-  if (n <= 0) return TR_OK;
-  if (check_voxels && !ctx->has_grid) return fail(ctx, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");
-  const trk::FusedSweepArgs *d_args; size_t lds; int slot, rc;
-  if ((rc = fused_args_slot(ctx, in, check_voxels, d_bits, d_flags, s, &d_args, &lds, &slot, sig, sig_stride))) return rc;
-  {
-    ProfScope ps(ctx, 4, s);
-    const trk::FkLaunch fl{d_states, n, ld, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
-                           (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, out, s};
-    switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: trk::launch_fk_sweep_fused<N>(fl, d_args, lds); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-      default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  HIP_TRY(ctx, hipEventRecord(ctx->fused.ev[slot], s));
-  ctx->fused.used[slot] = true;
-  return TR_OK;
-}
-
-// The verdict path of tr_validate_batch* (verdict_kernel.hpp): fk_verdict over the n configurations -- no backbone point
-// is stored -- then ONE launch of fk_sweep_fused_list, which integrates again, with stored points, the configurations whose
-// self-collision test needs the exact pairwise sweep (their indices and count stay on the device; with an empty list its
-// blocks return at once).  d_bits / d_flags / d_tips as in tr_validate_batch_dev; n <= 2^31.
-int ensure_sphere_near(tr_ctx *c, hipStream_t s);
-int launch_verdict(tr_ctx *ctx, const double *d_states, int64_t n, uint64_t *d_bits, double *d_tips, uint8_t *d_flags, hipStream_t s,
-                   uint32_t *sig = nullptr, int64_t sig_stride = 0, bool spheres = false, int32_t *np_out = nullptr, int lane = 0) {
-  if (n <= 0) return TR_OK;
-  if (!ctx->has_grid) return fail(ctx, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");
-  int rc;
-  if (spheres && (rc = ensure_sphere_near(ctx, s))) return rc;
-  Workspace &w = ctx->ws;
-  // lanes 1 .. (the further lanes of an edge bisection, running concurrently on their own streams): their own list and counter, and
-  // the workspace columns [lane fb_cap, (lane + 1) fb_cap) for their fallback pass
-  if (lane < 0 || lane >= tr_ctx::kMaxLanes) return fail(ctx, TR_ERR_RUNTIME, "bad lane");
-  if ((rc = ensure_lane_fallback(ctx, lane, round_up(n, 64)))) return rc;
-  int32_t *const fb_list = ctx->lane[lane].fb_list;
-  uint32_t *const fb_count = ctx->lane[lane].fb_count;
-  const int64_t cap = std::min<int64_t>(ctx->fb_cap, round_up(n, 64));
-  if ((rc = ensure_workspace(ctx, lane == 0 ? cap : (lane + 1) * ctx->fb_cap))) return rc;
-  const int64_t fcol = lane * ctx->fb_cap;                        // first workspace column of this lane's fallback pass
-  tr_ctx::VerdictRing &vr = ctx->vring;
-  if (!vr.d_slots) {
-    HIP_TRY(ctx, hipMalloc((void **)&vr.d_slots, sizeof(trk::VerdictArgs) * tr_ctx::VerdictRing::kSlots));
-    HIP_TRY(ctx, hipHostMalloc((void **)&vr.h_slots, sizeof(trk::VerdictArgs) * tr_ctx::VerdictRing::kSlots, hipHostMallocDefault));
-    for (auto &e : vr.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const int vslot = vr.next;
-  vr.next = (vr.next + 1) % tr_ctx::VerdictRing::kSlots;
-  if (vr.used[vslot]) HIP_TRY(ctx, hipEventSynchronize(vr.ev[vslot]));
-  trk::VerdictArgs &a = vr.h_slots[vslot];
-  a = trk::VerdictArgs{};
-  size_t lds_k2;
-  sweep_geometry(ctx, a.CH, a.NM, lds_k2);
-  a.P = ctx->K.n_points; a.debug = ctx->debug;
-  a.g = ctx->G; a.grid = ctx->d_grid; a.near_grid = ctx->d_near; a.valid_bits = d_bits; a.flags = d_flags;
-  {
-    const GridK &g = ctx->G;            // sweep_body's margin box, same expressions (this file is compiled without contraction)
-    a.box[0] = g.xmin + 1e-6 * (g.xmax - g.xmin); a.box[1] = g.xmax - 1e-6 * (g.xmax - g.xmin);
-    a.box[2] = g.ymin + 1e-6 * (g.ymax - g.ymin); a.box[3] = g.ymax - 1e-6 * (g.ymax - g.ymin);
-    a.box[4] = g.zmin + 1e-6 * (g.zmax - g.zmin); a.box[5] = g.zmax - 1e-6 * (g.zmax - g.zmin);
-  }
-  a.fb_list = fb_list; a.fb_count = fb_count;
-  a.sig = sig; a.sig_stride = sig_stride; a.np_out = np_out;
-  a.radius = ctx->K.radius;
-  for (int j = 0; j < TRK_MAX_TENDONS; j++) { a.home_Li[j] = ctx->K.home_Li[j]; a.min_len[j] = ctx->K.min_len[j]; a.max_len[j] = ctx->K.max_len[j]; }
-  if (spheres) {                       // classification thresholds (verdict_kernel.hpp: PointSweep<true>)
-    a.field = ctx->d_sph_near; a.radius = ctx->K.radius;
-    a.r_lo = (float)ctx->K.radius - 2e-6f; a.r_hi = (float)ctx->K.radius + 2e-6f;
-  }
-  if (ctx->K.enable_retraction && ctx->retract_sort_min > 0 && n >= ctx->retract_sort_min) {
-    // waves of one backbone length: see retraction_order.  The mask is filled by atomic ORs, so it starts from zero.
-    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
-    if ((rc = ensure_lane_order(ctx, lane, round_up(n, 64)))) return rc;
-    const hipError_t e = trk::retraction_order(order_scratch(ctx, lane), d_states, n, ctx->K.state_size, ctx->K.L, ro.keys, ro.vals, &a.perm, s,
-                                               ctx->K.dL, ctx->k_first, ctx->rows_one_step, ro.kbegin);
-    a.wave_k_begin = ctx->retract_wave_start ? ro.kbegin : nullptr;
-    if (e != hipSuccess) return fail(ctx, TR_ERR_HIP, std::string("retraction order: ") + hipGetErrorString(e));
-    HIP_TRY(ctx, hipMemsetAsync(d_bits, 0, (size_t)((n + 63) / 64) * sizeof(uint64_t), s));
-  }
-  a.finish_hot();
-  HIP_TRY(ctx, hipMemcpyAsync(vr.d_slots + vslot, &a, sizeof(a), hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(uint32_t), s));
-  // the fallback pass sweeps columns of the small point workspace
-  const bool ret = ctx->K.enable_retraction;      // K1r's body in both launches, tip-aligned rows in the fallback workspace
-  const trk::FusedSweepArgs *d_fargs; size_t lds_f; int fslot;
-  if ((rc = fused_args_slot(ctx, ws_sweep_in(ctx, fcol), spheres ? 2 : 1, d_bits, d_flags, s, &d_fargs, &lds_f, &fslot))) return rc;
-  const trk::FkOut vout{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tips, nullptr, nullptr, nullptr};
-  trk::FkLaunch vl{d_states, n, 0, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
-                   (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, vout, s};
-  if (ctx->K.enable_retraction) {
-    // the prologue kernel's hand-over planes (fk_retract_prologue -> fk_verdict_retract), one set per lane of the edge bisection
-    tr_ctx::RetractOrder &ro = ctx->lane[lane].ro;
-    const int64_t hld = round_up(n, 64);
-    if (ro.handoff_cap < hld) {
-      HIP_TRY(ctx, hipDeviceSynchronize());
-      const int64_t want = hld + hld / 8;
-      if ((rc = dev_alloc(ctx, &ro.handoff, (size_t)want * (19 + 2 * TRK_MAX_TENDONS + 3)))) return rc;     // R, v, u, p | L_i | converged | state | L
-      ro.handoff_cap = want;
-    }
-    vl.d_handoff = ro.handoff; vl.handoff_ld = hld; vl.d_perm = a.perm;
-  }
-  const trk::FkOut fout = ws_fk_out(ctx, fcol);
-  const trk::FkLaunch fl{d_states, cap, w.ld, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
-                         (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, fout, s};
-  const size_t lds_v = trk::verdict_lds_bytes(a.NM, sig != nullptr);
-  {
-    ProfScope ps(ctx, 5, s);
-    switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: if (ret) trk::launch_fk_verdict_retract<N>(vl, vr.d_slots + vslot, lds_v, spheres, sig != nullptr); \
-                            else trk::launch_fk_verdict<N>(vl, vr.d_slots + vslot, lds_v, spheres, sig != nullptr); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-      default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  {
-    ProfScope ps(ctx, 4, s);
-    switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: if (ret) trk::launch_fk_sweep_retract_list<N>(fl, d_fargs, lds_f, fb_list, fb_count); \
-                            else trk::launch_fk_sweep_fused_list<N>(fl, d_fargs, lds_f, fb_list, fb_count); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-      default: break;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  HIP_TRY(ctx, hipEventRecord(vr.ev[vslot], s));
-  vr.used[vslot] = true;
-  HIP_TRY(ctx, hipEventRecord(ctx->fused.ev[fslot], s));
-  ctx->fused.used[fslot] = true;
-  return TR_OK;
-}
-
-// The edge queue's launch (edge_queue_kernel.hpp: fk_edge_queue): the verdict-only body's arguments as launch_verdict forms them
-// (backbone checker, signature rows into `sig`), the in-wave fallback's sweep arguments over the waves' own workspace columns, and
-// `waves` persistent workgroups.  qa: the queue's arguments, already on the device.  The workspace must hold 64 x waves columns.
-int launch_edge_queue(tr_ctx *ctx, hipStream_t s, uint32_t *sig, int64_t sig_stride, const trk::EdgeQueueArgs *qa, unsigned waves) {
-  if (!ctx->has_grid) return fail(ctx, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");
-  Workspace &w = ctx->ws;
-  if (w.ld < (int64_t)waves * 64) return fail(ctx, TR_ERR_RUNTIME, "edge queue: workspace smaller than the launch");
-  tr_ctx::VerdictRing &vr = ctx->vring;
-  if (!vr.d_slots) {
-    HIP_TRY(ctx, hipMalloc((void **)&vr.d_slots, sizeof(trk::VerdictArgs) * tr_ctx::VerdictRing::kSlots));
-    HIP_TRY(ctx, hipHostMalloc((void **)&vr.h_slots, sizeof(trk::VerdictArgs) * tr_ctx::VerdictRing::kSlots, hipHostMallocDefault));
-    for (auto &e : vr.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  const int vslot = vr.next;
-  vr.next = (vr.next + 1) % tr_ctx::VerdictRing::kSlots;
-  if (vr.used[vslot]) HIP_TRY(ctx, hipEventSynchronize(vr.ev[vslot]));
-  trk::VerdictArgs &a = vr.h_slots[vslot];
-  a = trk::VerdictArgs{};
-  size_t lds_k2;
-  sweep_geometry(ctx, a.CH, a.NM, lds_k2);
-  a.P = ctx->K.n_points; a.debug = ctx->debug;
-  a.g = ctx->G; a.grid = ctx->d_grid; a.near_grid = ctx->d_near;
-  {
-    const GridK &g = ctx->G;            // sweep_body's margin box, same expressions (this file is compiled without contraction)
-    a.box[0] = g.xmin + 1e-6 * (g.xmax - g.xmin); a.box[1] = g.xmax - 1e-6 * (g.xmax - g.xmin);
-    a.box[2] = g.ymin + 1e-6 * (g.ymax - g.ymin); a.box[3] = g.ymax - 1e-6 * (g.ymax - g.ymin);
-    a.box[4] = g.zmin + 1e-6 * (g.zmax - g.zmin); a.box[5] = g.zmax - 1e-6 * (g.zmax - g.zmin);
-  }
-  a.sig = sig; a.sig_stride = sig_stride;
-  a.radius = ctx->K.radius;
-  for (int j = 0; j < TRK_MAX_TENDONS; j++) { a.home_Li[j] = ctx->K.home_Li[j]; a.min_len[j] = ctx->K.min_len[j]; a.max_len[j] = ctx->K.max_len[j]; }
-  a.finish_hot();
-  HIP_TRY(ctx, hipMemcpyAsync(vr.d_slots + vslot, &a, sizeof(a), hipMemcpyHostToDevice, s));
-  int rc;
-  const trk::FusedSweepArgs *d_fargs; size_t lds_f; int fslot;
-  if ((rc = fused_args_slot(ctx, ws_sweep_in(ctx, 0), 1, nullptr, nullptr, s, &d_fargs, &lds_f, &fslot))) return rc;
-  const size_t lds_v = std::max(trk::verdict_lds_bytes(a.NM, true) + (size_t)trk::EQ_STASH_WORDS * 4, lds_f);   // (+ the waves' stash: edge_queue_kernel.hpp)
-  const trk::FkOut none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  const trk::FkLaunch fl{nullptr, 0, 0, ctx->K, (bool)ctx->K.enable_rotation, false, ctx->d_tab, ctx->d_steps,
-                         (int)ctx->steps.size(), ctx->d_poly, ctx->k_first, ctx->d_tgrid, ctx->d_hl, none, s};
-  {
-    ProfScope ps(ctx, 5, s);
-    switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: trk::launch_fk_edge_queue<N>(fl, vr.d_slots + vslot, lds_v, qa, d_fargs, waves); break;
-      TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-      default: return fail(ctx, TR_ERR_OUT_OF_RANGE, "n_tendons out of range");
-    }
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  HIP_TRY(ctx, hipEventRecord(vr.ev[vslot], s));
-  vr.used[vslot] = true;
-  HIP_TRY(ctx, hipEventRecord(ctx->fused.ev[fslot], s));
-  ctx->fused.used[fslot] = true;
-  return TR_OK;
-}
-
-// persistent workgroups of the edge queue's launch: what the device holds at once (occupancy x CUs)
-int edge_queue_waves(tr_ctx *ctx) {
-  if (ctx->edge_queue_waves > 0) return ctx->edge_queue_waves;
-  int CH, NM; size_t lds_k2;
-  sweep_geometry(ctx, CH, NM, lds_k2);
-  const size_t lds_v = std::max(trk::verdict_lds_bytes(NM, true) + (size_t)trk::EQ_STASH_WORDS * 4, lds_k2);
-  int per_cu = 0;
-  switch (ctx->K.n_tendons) {
-#define TRK_CASE(N) case N: per_cu = trk::fk_edge_queue_waves_per_cu<N>(ctx->K, lds_v); break;
-    TRK_CASE(1) TRK_CASE(2) TRK_CASE(3) TRK_CASE(4) TRK_CASE(5) TRK_CASE(6) TRK_CASE(7) TRK_CASE(8)
-#undef TRK_CASE
-    default: break;
-  }
-  hipDeviceProp_t prop;
-  if (per_cu <= 0 || hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return 0;
-  ctx->edge_queue_waves = per_cu * prop.multiProcessorCount;
-  return ctx->edge_queue_waves;
-}
-
-// Distance from every cell centre to the nearest occupied cell centre, exact within the window that matters
-// (r + a cell diagonal), TRK_EDT_FAR beyond: three separable min-plus passes (x on the bit grid, then y, z).
-int ensure_sphere_near(tr_ctx *c, hipStream_t s) {
-  if (c->sph_near_valid) return TR_OK;
-  HIP_TRY(c, hipDeviceSynchronize());
-  const size_t ncell = (size_t)c->G.N * c->G.N * c->G.N;
-  if (c->d_sph_near) { (void)hipFree(c->d_sph_near); c->d_sph_near = nullptr; }
-  if (c->d_sph_tmp) { (void)hipFree(c->d_sph_tmp); c->d_sph_tmp = nullptr; }
-  HIP_TRY(c, hipMalloc((void **)&c->d_sph_near, ncell * sizeof(float)));
-  HIP_TRY(c, hipMalloc((void **)&c->d_sph_tmp, ncell * sizeof(float)));
-  const double reach = c->K.radius + std::sqrt(c->G.dx * c->G.dx + c->G.dy * c->G.dy + c->G.dz * c->G.dz);
-  const int R[3] = {(int)std::ceil(reach / c->G.dx) + 1, (int)std::ceil(reach / c->G.dy) + 1, (int)std::ceil(reach / c->G.dz) + 1};
-  const unsigned gcell = (unsigned)((ncell + 255) / 256);
-  hipLaunchKernelGGL(trk::obstacle_distance_x, dim3(c->n_blocks), dim3(64), 0, s, c->d_grid, c->d_sph_near, c->G.Nb, R[0], (float)c->G.dx);
-  hipLaunchKernelGGL(trk::obstacle_distance_axis, dim3(gcell), dim3(256), 0, s, c->d_sph_near, c->d_sph_tmp, c->G.N, 1, R[1], (float)c->G.dy, 0);
-  hipLaunchKernelGGL(trk::obstacle_distance_axis, dim3(gcell), dim3(256), 0, s, c->d_sph_tmp, c->d_sph_near, c->G.N, 2, R[2], (float)c->G.dz, 1);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(s));
-  c->sph_near_valid = true;
-  return TR_OK;
-}
-
-// K1 then K2 on one stream: a single fused launch when the robot uses the shared arc-length grid.
-// voxel_test: 0 = is_valid_shape only, 1 = backbone voxels (VoxelBackboneValidityChecker), 2 = sphere-swept
-// robot (VoxelValidityChecker: K2 without the voxel test, then K8 on the survivors).
-// sig (optional, edge samples): the fused launch also writes the samples' cell signatures; use edge_signatures(ctx, ..) to
-// learn whether this context's fused path is active (the separate kernels write none).  points_unused: the caller will not
-// read the points of this launch (out.px .. may then stay unwritten).
-// with_points: the caller also needs the samples' stored points (voxel caches).  Retraction robots then run K1r -> K2 as
-// separate launches, which write no signatures (the interval test reads the points); without points their samples go
-// through fk_verdict_retract, which does.
-bool edge_signatures(const tr_ctx *ctx, bool with_points) {
-  return ctx->K.enable_retraction ? (ctx->fuse == 2 && !with_points) : ctx->fuse != 0;
-}
-
-int launch_fk_sweep(tr_ctx *ctx, const double *d_states, int64_t n, int64_t ld, const trk::FkOut &out, const trk::SweepIn &in,
-                    int voxel_test, uint64_t *d_bits, uint8_t *d_flags, hipStream_t s, uint32_t *sig = nullptr, int64_t sig_stride = 0,
-                    bool points_unused = false, int32_t *sig_np = nullptr /* retraction: the samples' point counts, next to sig */,
-                    int lane = 0) {
-  const int check_voxels = voxel_test == 1 ? 1 : 0;
-  int rc;
-  if (voxel_test == 2) {
-    if (!ctx->has_grid) return fail(ctx, TR_ERR_INVALID_ARG, "no obstacle grid set (tr_set_grid)");
-    if ((rc = ensure_sphere_near(ctx, s))) return rc;
-  }
-  if (ctx->fuse == 2 && voxel_test != 0 && points_unused && !out.R && !out.L && !out.tips) {
-    // nobody reads this launch's backbone points (edge samples of the checkMotion forms: the bisection compares cell
-    // signatures -- of tip-aligned rows for retraction robots, hence the point counts): the verdict-only kernel, which stores none
-    return launch_verdict(ctx, d_states, n, d_bits, nullptr, d_flags, s, sig, sig_stride, voxel_test == 2, sig ? sig_np : nullptr, lane);
-  }
-  if (ctx->fuse != 0 && !ctx->K.enable_retraction && !out.R && !out.L) {      // the fused kernel integrates neither R output nor L
-    if ((rc = launch_fused(ctx, d_states, n, ld, out, in, check_voxels, d_bits, d_flags, s, sig, sig_stride))) return rc;
-  } else {
-    if ((rc = launch_fk(ctx, d_states, n, ld, out, s, lane))) return rc;
-    if ((rc = launch_sweep(ctx, in, n, ld, check_voxels, d_bits, d_flags, s))) return rc;
-  }
-  if (voxel_test == 2) {
-    ProfScope ps(ctx, 3, s);
-    hipLaunchKernelGGL(trk::spheres_vs_grid, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, in.px, in.py, in.pz, in.n_points, n, ld,
-                       (int)ctx->K.n_points, ctx->K.radius, ctx->G, ctx->d_grid, ctx->d_sph_near, d_bits, d_flags);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  return TR_OK;
-}
+#include "launch_host.inc"
 
 }  // namespace
 
@@ -1243,8 +785,7 @@ void tr_destroy(tr_ctx *c) {
                   c->edge.A, c->edge.B, c->edge.rel, c->edge.edge_ok, c->edge.nfk, c->edge.first_inv, c->edge.last_t, c->edge.nd, c->edge.cnt, c->edge.sig, c->edge.sig_np, c->edge.ix_states, c->edge.ix_idx, c->edge.open2, c->edge.lvl_states2, c->edge.q_remaining, c->edge.q_lvl_base, c->edge.q_lvl_cnt, c->edge.q_ctl, c->edge.q_args, c->d_envw[0], c->d_envw[1], c->d_sph_near, c->d_sph_tmp};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   trk::merge_free(c->merge);
-  if (c->fused.d_slots) { (void)hipFree(c->fused.d_slots); (void)hipHostFree(c->fused.h_slots); for (auto &e : c->fused.ev) (void)hipEventDestroy(e); }
-  if (c->vring.d_slots) { (void)hipFree(c->vring.d_slots); (void)hipHostFree(c->vring.h_slots); for (auto &e : c->vring.ev) (void)hipEventDestroy(e); }
+  c->fused.release(); c->vring.release();
   if (c->last_dev_ev) (void)hipEventDestroy(c->last_dev_ev);
   {
     tr_ctx::Sampler &sm = c->samp;

@@ -174,7 +174,7 @@ UNIFORM_HELIX = ("config1", "config2", "config2_dl35") + ftc.NEW_HELIX       # o
 
 @pytest.mark.parametrize("name", NO_RETRACTION)
 def test_fused_stored_point_kernels_against_truth(irt, name):
-    """Which kernel an entry launches (tendon_hip.hip: launch_fk_sweep and launch_fused, validate_batch_dev_impl, tr_voxelize_batch),
+    """Which kernel an entry launches (launch_host.inc: launch_fk_sweep and launch_fused; tendon_hip.hip: validate_batch_dev_impl, tr_voxelize_batch),
     backbone checker, no retraction, empty 64^3 grid:
       TENDON_HIP_FUSED=1  is_valid_detail -> launch_fk_sweep -> launch_fused: fk_sweep_fused<N>, K1 + K2 over stored points in one
                           launch, tips from its own integration; voxelize_batch -> the same kernel with voxel_test = 0 (then
