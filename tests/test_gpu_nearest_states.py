@@ -4,9 +4,14 @@ the order (dist, vertex index), bit for bit against a restatement of CompoundSta
 shape (the vertex array whole, cut into slices, a last wave short of queries), on exact ties, across the shortest-arc branch, on
 small roadmaps, under a distance bound, and against the table tr_knn gives for the roadmap's own states."""
 import ctypes
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from state_metric_reference import distances          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,24 +36,8 @@ def _roadmap(irt, robot, states, status=None):
 
 
 def _distances(eng, vertices, q):
-    """distance(q, every row of `vertices`) as the header states it"""
-    n, rot, ret = eng.state_layout()
-    w_rot, w_ret = eng.space_weights()
-    s2 = np.zeros(len(vertices))
-    for d in range(n):                                                  # left to right, one product and one sum per column
-        t = q[d] - vertices[:, d]
-        s2 = s2 + t * t
-    dist = np.sqrt(s2)
-    c = n
-    if rot:
-        arc = np.abs(q[c] - vertices[:, c])
-        arc = np.where(arc > np.pi, 2.0 * np.pi - arc, arc)
-        dist = dist + w_rot * arc
-        c += 1
-    if ret:
-        t = q[c] - vertices[:, c]
-        dist = dist + w_ret * np.sqrt(t * t)
-    return dist
+    """distance(q, every row of `vertices`) as the header states it (tests/state_metric_reference.py)"""
+    return distances(*eng.state_layout(), *eng.space_weights(), q, vertices)
 
 
 def _nearest(eng, states, ok, queries, k, max_distance=np.inf):

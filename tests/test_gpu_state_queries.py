@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import state_query_reference as ref          # noqa: E402
+from state_metric_reference import distances          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -68,23 +69,9 @@ def world3(irt):
 
 
 def _distance_rows(eng, a, b):
-    """CompoundStateSpace::distance row by row as the header states it: the tension differences squared and summed left to right"""
-    n, rot, ret = eng.state_layout()
-    w_rot, w_ret = eng.space_weights()
-    s2 = np.zeros(len(a))
-    for d in range(n):
-        t = a[:, d] - b[:, d]
-        s2 = s2 + t * t
-    dist = np.sqrt(s2)
-    c = n
-    if rot:
-        arc = np.abs(a[:, c] - b[:, c])
-        dist = dist + w_rot * np.where(arc > np.pi, 2.0 * np.pi - arc, arc)
-        c += 1
-    if ret:
-        t = a[:, c] - b[:, c]
-        dist = dist + w_ret * np.sqrt(t * t)
-    return dist
+    """CompoundStateSpace::distance row by row as the header states it: the tension differences squared and summed left to right
+    (tests/state_metric_reference.py)"""
+    return distances(*eng.state_layout(), *eng.space_weights(), a, b)
 
 
 def _mv_args(mv):
